@@ -13,6 +13,12 @@ Default arithmetic since round 4: f16x2 -- all three MLPs on fp16 MFMA with ever
 because it now meets both bars: sample counts / opacity / depth / rgb BIT-IDENTICAL to the CPU oracle's mode of the same
 name (the oracle restates the matrix instruction, oracle/mfma_f16_model.h) and within 1e-4 of the plain fp32 oracle
 with the same sample counts.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the result line
+(with the field-kernel roofline read from the timed steps themselves).  Everything that takes runs of its own -- the
+further timing windows, the other MLP precisions and table type, the other scaling mode, the one-frame latency, the
+render_image / viewer entries, the multi-rank gather check, the CPU baselines and the oracle parity legs -- runs only
+with --full.  --dump-outputs DIR writes what the last timed step returned as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -49,6 +55,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure (further windows, other precisions / table type / "
+                         "scaling, one-frame latency, render_image and viewer entries, gather check, CPU baselines, oracle "
+                         "parity); without it --also, --min-seconds and the CPU-baseline / oracle / single-frame options "
+                         "have no effect")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--height", type=int, default=800)
     ap.add_argument("--scene", default="dnerf", choices=["dnerf", "hypernerf", "dynerf"])
@@ -105,7 +118,38 @@ def parse():
     ap.add_argument("--cpu-passes", type=int, default=3, help="how many times the CPU baseline renders its sample")
     ap.add_argument("--torch-stride", type=int, default=4,
                     help="pixel stride of the ray sample the PyTorch-fp32 CPU path renders (0 = skip)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline figure only (the other legs gated on --full below read these)
+        args.also, args.min_seconds, args.no_single_frame, args.no_cpu_baseline = "", 0.0, True, True
+    return args
+
+
+DUMP_BYTES = 48 << 20         # --dump-outputs writes at most this much in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, row, height, width):
+    """What the timed path returned in its last step: per lane one gathered result (rgb / opacity / depth of every frame
+    of the lane's call, and the call's sample total).  Written as float32 / float64 .npy files: rgb [frames, n, 3],
+    opacity / depth [frames, n] (frames in lane order), pixel_index [n] (raster index of the n pixels kept, the same for
+    every frame: all of them, or a fixed seeded sample when the whole frames would exceed DUMP_BYTES) and
+    samples_per_call [lanes]."""
+    n_frames = sum(int(o["rgb"].shape[0]) for o in row)
+    n_pix = height * width
+    n_keep = max(1, min(n_pix, DUMP_BYTES // (n_frames * 5 * 4)))
+    idx = (np.arange(n_pix) if n_keep == n_pix else
+           np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, n_keep, replace=False)))
+    it = torch.from_numpy(idx).to(row[0]["rgb"].device)
+    pick = lambda t, c: t.reshape(t.shape[0], n_pix, c)[:, it].cpu().numpy()
+    rgb = np.concatenate([pick(o["rgb"], 3) for o in row]).astype(np.float32)
+    opacity = np.concatenate([pick(o["opacity"], 1)[..., 0] for o in row]).astype(np.float32)
+    depth = np.concatenate([pick(o["depth"], 1)[..., 0] for o in row]).astype(np.float32)
+    totals = [o["total_samples"] if o.get("total_samples") is not None else o["total_samples_tensor"].item() for o in row]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("rgb", rgb), ("opacity", opacity), ("depth", depth), ("pixel_index", idx.astype(np.float64)),
+                    ("samples_per_call", np.asarray(totals, dtype=np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(sc, args):
@@ -306,7 +350,7 @@ def main():
             r.tracer = tracers[l][step_no[0] % len(tracers[l])]
         step_no[0] += 1
         outs = renderer.render(ts)
-        return {"local_samples": sum(o["local_samples"] for o in outs)}
+        return {"local_samples": sum(o["local_samples"] for o in outs), "outs": outs}
 
     for _ in range(args.warmup):
         step()
@@ -323,6 +367,7 @@ def main():
         for _ in range(args.steps):
             out = step()
             samples_local += out["local_samples"]
+        dump_row = out["outs"]
     else:
         # the K steps as a stream: lanes do not wait for each other between steps (PipelinedRenderer.render_steps)
         def before_frame(l, s_):
@@ -331,12 +376,17 @@ def main():
             lane_renderers[l].tracer = tracers[l][s_] if s_ < len(tracers[l]) else None
         rows = renderer.render_steps(ts, args.steps, before_frame=before_frame)
         samples_local = sum(o["local_samples"] for row in rows for o in row)
-        last_row = rows[-1]
+        last_row = dump_row = rows[-1]
         del rows
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        renderer.wait_gathers()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dump_row, args.height, args.width)
 
     def reduce_window(dt_w, samples_w):
         tt_w = torch.tensor([dt_w, float(samples_w)], device=dev, dtype=torch.float64)
@@ -441,7 +491,7 @@ def main():
     field._descriptor()
     # the same step with the hash table stored in the OTHER type (fp16 <-> fp32), briefly: for hash_lookup_hbm_frac
     other_table = None
-    if os.environ.get("CED_BENCH_OTHER_TABLE", "1") != "0":
+    if args.full and os.environ.get("CED_BENCH_OTHER_TABLE", "1") != "0":
         p2 = dict(sc["params"]); h2 = dict(p2["hash"])
         h2["table"] = np.ascontiguousarray(h2["table"].astype(np.float32 if h2["table"].dtype == np.float16 else np.float16))
         p2["hash"] = h2
@@ -468,7 +518,7 @@ def main():
         del field2
     # several GPUs: the same steps in the OTHER scaling mode, briefly (same barrier / max-over-ranks discipline)
     other_scaling = None
-    if world > 1:
+    if world > 1 and args.full:
         other = "weak" if args.scaling == "strong" else "strong"
         fc_o = frames_per_call_of(other)
         lanes_o = make_lanes(fc_o)
@@ -757,7 +807,7 @@ def main():
         for k_, v_ in others.items():
             v_["parity"] = notes[k_]
         line["other_mlp_precisions"] = others
-    if world > 1 and last_row is not None:
+    if world > 1 and last_row is not None and args.full:
         # the exchange, checked: lane 0's gathered frames of the last timed step (every rank's shard on the image-global
         # schedule, all-gathered and un-permuted) against the same frames rendered whole by this rank alone: the same
         # bits and the same sample totals, not a tolerance

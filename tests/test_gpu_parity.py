@@ -1924,7 +1924,7 @@ def _two_rank_bench(extra):
     env = dict(os.environ, CED_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--width", "256", "--height", "256", "--no-cpu-baseline", "--min-seconds", "0.2", "--frames-per-call", "3"] + extra
+           "--width", "256", "--height", "256", "--full", "--no-cpu-baseline", "--min-seconds", "0.2", "--frames-per-call", "3"] + extra
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@
 #        PARITY=1 bash tools/bench_table.sh   also renders frame 0 with the CPU oracle (plain: whole frame; the timed mode's
 #        own oracle mode: every 2nd pixel) and prints parity_vs_oracle / parity_vs_oracle_mode of the timed mode per config
 R=${GRAFT_REPO_ROOT:-.}
-if [ "${PARITY:-0}" = "1" ]; then EXTRA="--cpu-passes 1 --torch-stride 0"; else EXTRA="--no-cpu-baseline"; fi
+if [ "${PARITY:-0}" = "1" ]; then EXTRA="--full --cpu-passes 1 --torch-stride 0"; else EXTRA="--full --no-cpu-baseline"; fi
 run() {
   echo "== $1"
   shift

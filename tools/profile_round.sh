@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export CED_BENCH_OTHER_TABLE=0      # profiled runs: only the timed table type's kernels
 for prec in ${MODES:-f16x2 f32+h16x2}; do
-  ARGS="$R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --also= --min-seconds 0 --mlp-precision $prec"
+  ARGS="$R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --also= --min-seconds 0 --mlp-precision $prec"
   # 1. the bench line itself (not under the profiler)
   timeout -k 10 300 python3 $ARGS > $OUT/${TAG}_${prec}_bench.json 2> $OUT/${TAG}_${prec}_bench.err
   echo "bench $prec done"
@@ -29,5 +29,5 @@ for prec in ${MODES:-f16x2 f32+h16x2}; do
 done
 # the default bench.py line (default mode + the other modes + cpu baselines + oracle-mode parity)
 unset CED_BENCH_OTHER_TABLE
-timeout -k 10 600 python3 $R/bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+timeout -k 10 600 python3 $R/bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 echo "default bench done"
