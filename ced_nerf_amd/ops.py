@@ -336,6 +336,47 @@ def composite_backward(packed_info, t_starts, t_ends, sigmas, rgbs, d_color, d_o
     return d_sig, d_rgb
 
 
+def _distortion_workspace(n_rays: int, S: int, density: bool, dev) -> torch.Tensor:
+    n = _lib.lib().ced_distortion_workspace_bytes(n_rays, S, int(density))
+    _lib.check(0 if n >= 0 else int(n), "distortion_workspace_bytes")
+    return torch.empty(((n + 7) // 8,), device=dev, dtype=torch.float64)      # 8-byte aligned
+
+
+def distortion_loss(packed_info, weights, t_starts, t_ends, want_grad: bool = True):
+    """ced_distortion_loss: (loss [], inv_norm [], ray_loss [n_rays], dL/dw [S] unscaled or None), all on the device."""
+    _chk(packed_info, torch.int64, "packed_info"); _chk(weights, torch.float32, "weights")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
+    n_rays, S = packed_info.shape[0], weights.shape[0]
+    assert weights.dim() == 1 and t_starts.shape == (S,) and t_ends.shape == (S,), "distortion_loss: [S] samples"
+    dev = weights.device
+    loss, inv_norm = torch.empty((), device=dev), torch.empty((), device=dev)
+    ray_loss = torch.empty((n_rays,), device=dev)
+    grad = torch.zeros((S,), device=dev) if want_grad else None
+    ws = _distortion_workspace(n_rays, S, False, dev)
+    rc = _lib.lib().ced_distortion_loss(n_rays, S, _p(packed_info), _p(weights), _p(t_starts), _p(t_ends), _p(ray_loss),
+                                        _p(grad), _p(ws), _p(loss), _p(inv_norm), _stream())
+    _lib.check(rc, "distortion_loss")
+    return loss, inv_norm, ray_loss, grad
+
+
+def distortion_loss_density(packed_info, sigmas, t_starts, t_ends, want_grad: bool = True):
+    """ced_distortion_loss_density: (loss [], inv_norm [], ray_loss [n_rays], dL/dsigma [S] unscaled or None); the
+    weights are those of render_weights(packed_info, t_starts, t_ends, sigmas) bit for bit."""
+    _chk(packed_info, torch.int64, "packed_info"); _chk(sigmas, torch.float32, "sigmas")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
+    n_rays, S = packed_info.shape[0], sigmas.shape[0]
+    assert sigmas.dim() == 1 and t_starts.shape == (S,) and t_ends.shape == (S,), "distortion_loss_density: [S] samples"
+    dev = sigmas.device
+    loss, inv_norm = torch.empty((), device=dev), torch.empty((), device=dev)
+    ray_loss = torch.empty((n_rays,), device=dev)
+    d_sig = torch.zeros((S,), device=dev) if want_grad else None
+    ws = _distortion_workspace(n_rays, S, want_grad, dev)
+    rc = _lib.lib().ced_distortion_loss_density(n_rays, S, _p(packed_info), _p(sigmas), _p(t_starts), _p(t_ends), _p(ray_loss),
+                                                _p(d_sig), _p(ws), _p(loss), _p(inv_norm), _stream())
+    _lib.check(rc, "distortion_loss_density")
+    return loss, inv_norm, ray_loss, d_sig
+
+
 def frame_to_rgb8(rgb, flip_w: bool = True):
     """ced_frame_to_rgb8: [H,W,3] float colours -> [H,W,3] uint8 (x 255, truncated), flipped along the width as the
     reference's video frames are (train_real.py:556)."""

@@ -155,15 +155,19 @@ class _CompositeFunction(torch.autograd.Function):
 
 
 def rendering_train(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_rays: int, rgb_sigma_fn: Callable,
-                    render_bkgd: Optional[Tensor] = None):
+                    render_bkgd: Optional[Tensor] = None, want_weights: bool = False,
+                    packed_info: Optional[Tensor] = None):
     """cednerf/render.py:58-176 with gradients (the training call, train_real.py:339-350): `rgb_sigma_fn` returns
     differentiable (rgbs, sigmas); compositing runs on the HIP kernels in both directions.  First pieces of the
-    training path: returns (colors, opacities, depths, extras) like `rendering`."""
+    training path: returns (colors, opacities, depths, extras) like `rendering`.
+    want_weights: extras also carries the differentiable `weights` and the `ray_indices`, `t_starts`, `t_ends` of the
+    samples -- the per-sample entries the loss lines of train_real.py:379-396 read.  packed_info: the [n_rays, 2] offsets
+    of `ray_indices` when the caller already has them (otherwise computed here)."""
     rgbs, sigma_results = rgb_sigma_fn(t_starts, t_ends, ray_indices)
     sigmas = sigma_results["density"].squeeze(-1) if isinstance(sigma_results, dict) else sigma_results
     assert rgbs.shape[-1] == 3, "rgbs must have 3 channels, got {}".format(rgbs.shape)
     assert sigmas.shape == t_starts.shape, "sigmas must have shape of (N, 1)! Got {}".format(sigmas.shape)
-    packed = _packed_info_from(ray_indices, n_rays)
+    packed = _packed_info_from(ray_indices, n_rays) if packed_info is None else packed_info
     colors, opacities, depths = _CompositeFunction.apply(sigmas, rgbs, t_starts.contiguous(), t_ends.contiguous(), packed)
     depths = depths / opacities.clamp_min(torch.finfo(torch.float32).eps)
     if render_bkgd is not None:
@@ -184,4 +188,8 @@ def rendering_train(t_starts: Tensor, t_ends: Tensor, ray_indices: Tensor, n_ray
             weight_loss = torch.nn.functional.huber_loss(p_weight, target_weights, reduction="none")
             extras["weight_losses"] = reduce_along_rays(ray_indices, values=weight_loss * selector[:, None].to(weight_loss.dtype),
                                                         n_rays=n_rays, weights=weights[:, None])
+    if want_weights:
+        if "weights" not in extras:
+            extras["weights"] = _WeightsFn.apply(sigmas, t_starts.contiguous(), t_ends.contiguous(), packed)[0]
+        extras["ray_indices"], extras["t_starts"], extras["t_ends"] = ray_indices, t_starts, t_ends
     return colors, opacities, depths, extras

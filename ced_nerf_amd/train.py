@@ -11,7 +11,8 @@ What runs where:
   * the pieces between the MLPs (sample positions + Frequency / SH encodings; move / normalise / selector; trunc_exp and
     the head's input) -> HIP, one launch per direction each (ced_train_inputs / _warp / _head_in, csrc/train_glue.hip;
     `fused_glue = False` restores the torch statements they replaced, which the tests compare them with).  Only the
-    sigmoid, the time encoders and the losses (huber, smooth-L1) remain torch element-wise kernels.
+    sigmoid, the time encoders and the losses (huber, smooth-L1 / MSE, the opacity / entropy / weighted-colour
+    regularisers) remain torch element-wise kernels; the distortion regulariser is HIP (ced_distortion_loss_density).
 `TrainableField` keeps the parameter names and layout of `DNGPradianceField` (hash_table, xyz_wrap, mlp_base,
 mlp_head as W[out][in]), so `to_inference()` hands the trained weights to the fused kernels unchanged, and
 `tests/test_gpu_parity.py` checks that the two forwards agree.  Mirrors cednerf/model.py:354-488 (forward) and the
@@ -26,8 +27,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, losses, ops
 from .hashgrid import level_tables
+from .nerfacc_api import _packed_info_from, render_weight_from_density
 from .render import rendering_train
 from .utils import trunc_exp
 
@@ -462,13 +464,41 @@ def refresh_occupancy(field: TrainableField, estimator, step: int, timestamps: t
     estimator.train(was_training)
 
 
+_COLOUR_LOSSES = {"smooth_l1": torch.nn.functional.smooth_l1_loss, "mse": torch.nn.functional.mse_loss}
+
+
+def colour_loss(colors: torch.Tensor, target: torch.Tensor, kind: str = "smooth_l1") -> torch.Tensor:
+    """The colour term of `train_step`: "smooth_l1" (this package's default) or "mse" (train_real.py:369)."""
+    if kind not in _COLOUR_LOSSES:
+        raise ValueError(f"rgb_loss={kind!r}: one of {sorted(_COLOUR_LOSSES)}")
+    return _COLOUR_LOSSES[kind](colors, target)
+
+
 def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor, rays_d: torch.Tensor,
                timestamps: torch.Tensor, target_rgb: torch.Tensor, render_step_size: float, near_plane: float = 0.0,
                far_plane: float = 1e10, cone_angle: float = 0.0, alpha_thre: float = 0.0,
                render_bkgd: Optional[torch.Tensor] = None, grad_scaler=None, native_sampling: bool = True,
-               overlap_table_grad: bool = True) -> Dict:
-    """One optimisation step on a batch of rays (train_real.py:339-380): stratified occupancy-grid sampling with the
-    current density (no gradient), differentiable field + compositing, smooth-L1 colour loss, optimiser step."""
+               overlap_table_grad: bool = True, rgb_loss: str = "smooth_l1", distortion_loss: bool = False,
+               acc_entropy_loss: bool = False, opacity_loss: bool = False, weight_rgbper: bool = False,
+               loss_weights: Optional[Dict[str, float]] = None) -> Dict:
+    """One optimisation step on a batch of rays (train_real.py:339-420): stratified occupancy-grid sampling with the
+    current density (no gradient), differentiable field + compositing, colour loss, the enabled regularisers, optimiser
+    step.
+
+    rgb_loss: "smooth_l1" (this package's default) or "mse" (the reference's, train_real.py:369).  The regularisers of
+    train_real.py:371-396, each off by default and scaled by loss_weights[name] (default 1e-3, the reference's factor):
+      distortion_loss  (-d)   "distortion"     losses.distortion_from_density on the rendered densities (fused HIP route)
+      acc_entropy_loss (-ae)  "acc_entropy"    losses.acc_entropy_loss of the opacities
+      opacity_loss     (-o)   "opacity"        losses.opacity_loss of the opacities
+      weight_rgbper    (-wr)  "weight_rgbper"  losses.weighted_rgb_loss with the (detached) rendering weights
+    Returns {"loss", "n_samples", "loss_terms"}: loss_terms holds the unscaled value of every enabled term."""
+    if rgb_loss not in _COLOUR_LOSSES:
+        raise ValueError(f"rgb_loss={rgb_loss!r}: one of {sorted(_COLOUR_LOSSES)}")
+    weights_of = dict(distortion=1e-3, acc_entropy=1e-3, opacity=1e-3, weight_rgbper=1e-3)
+    unknown = set(loss_weights or {}) - set(weights_of)
+    if unknown:
+        raise ValueError(f"loss_weights: unknown terms {sorted(unknown)} (known: {sorted(weights_of)})")
+    weights_of.update(loss_weights or {})
     n_rays = rays_o.shape[0]
     ts = timestamps.reshape(-1, 1).float()
     if ts.shape[0] == 1:
@@ -494,9 +524,24 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
     def rgb_sigma_fn(t_starts, t_ends, ray_indices):
         return field.forward_rays(rays_o, rays_d, ray_indices, t_starts, t_ends, ts, return_internal=with_heads)
 
+    packed = _packed_info_from(ray_indices, n_rays) if (distortion_loss or weight_rgbper) else None
     colors, opacities, depths, extras = rendering_train(t_starts, t_ends, ray_indices, n_rays, rgb_sigma_fn,
-                                                         render_bkgd=render_bkgd)
-    loss = torch.nn.functional.smooth_l1_loss(colors, target_rgb)
+                                                         render_bkgd=render_bkgd, packed_info=packed)
+    loss = colour_loss(colors, target_rgb, rgb_loss)
+    terms = {}                                             # train_real.py:371-396, in its order
+    if opacity_loss:
+        terms["opacity"] = losses.opacity_loss(opacities)
+    if distortion_loss:
+        terms["distortion"] = losses.distortion_from_density(t_starts, t_ends, extras["sigmas"], packed)
+    if acc_entropy_loss:
+        terms["acc_entropy"] = losses.acc_entropy_loss(opacities)
+    if weight_rgbper:
+        with torch.no_grad():
+            weights, _, _ = render_weight_from_density(t_starts.contiguous(), t_ends.contiguous(),
+                                                       extras["sigmas"].detach().float().contiguous(), packed_info=packed)
+        terms["weight_rgbper"] = losses.weighted_rgb_loss(extras["rgbs"], target_rgb, ray_indices, weights)
+    if terms:
+        loss = loss + sum(v * weights_of[k] for k, v in terms.items())
     if "latent_losses" in extras:                          # train_real.py:400-409
         loss = loss + extras["latent_losses"].mean()
     if "weight_losses" in extras:
@@ -518,4 +563,7 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
     else:
         optimizer.step()
     field.sync_half_table()
-    return {"loss": float(loss.detach()), "n_samples": int(t_starts.shape[0])}
+    if not terms:
+        return {"loss": float(loss.detach()), "n_samples": int(t_starts.shape[0]), "loss_terms": {}}
+    values = torch.stack([loss.detach()] + [v.detach().float() for v in terms.values()]).tolist()     # one read-back
+    return {"loss": values[0], "n_samples": int(t_starts.shape[0]), "loss_terms": dict(zip(terms, values[1:]))}

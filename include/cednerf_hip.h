@@ -300,6 +300,28 @@ int ced_composite_backward(int64_t n_rays, const int64_t *packed_info, const flo
                            const float *d_color, const float *d_opacity, const float *d_depth,
                            float *d_sigmas, float *d_rgbs, void *stream);
 
+/* Distortion loss of the reference's `-d` flag (train_real.py:379-386, cednerf/losses.py:4-11, i.e.
+ * torch_efficient_distloss.flatten_eff_distloss).  Per ray, with s_i = t_end - t_start, m_i = (t_start + t_end) / 2:
+ *   L_ray = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i s_i w_i^2,
+ *   loss = sum_rays L_ray / n_norm,  n_norm = 1 + the largest ray index that has at least one sample.
+ * packed_info [n_rays,2] (start, count), int64; samples grouped by ray and t_starts non-decreasing within a ray.
+ * Outputs: ray_loss [n_rays] (L_ray), *loss (device scalar) and *inv_norm (device scalar, 1 / n_norm, 0 when no ray has a
+ * sample), so that a backward scales the unscaled gradient by grad_out * inv_norm without reading anything on the host.
+ * Deterministic: no float atomics, the per-ray losses summed in a fixed order (fp64).  n_rays == 0 or n_samples == 0:
+ * every output zeroed, no kernel launched.  workspace: ced_distortion_workspace_bytes(n_rays, n_samples, density) bytes
+ * of device scratch, 8-byte aligned (density = 1 for ced_distortion_loss_density with d_sigmas, else 0).
+ * ced_distortion_loss: weights [S] in; grad_weights [S] (may be NULL) = dL_ray/dw, unscaled.
+ * ced_distortion_loss_density: sigmas [S] in; the weights are recomputed with the arithmetic of ced_render_weights (same
+ * bits, hence the same loss as ced_distortion_loss fed by ced_render_weights); d_sigmas [S] (may be NULL) =
+ * dL_ray/dsigma, unscaled, through the weights.  Samples outside every ray are not written. */
+int64_t ced_distortion_workspace_bytes(int64_t n_rays, int64_t n_samples, int32_t density);
+int ced_distortion_loss(int64_t n_rays, int64_t n_samples, const int64_t *packed_info, const float *weights,
+                        const float *t_starts, const float *t_ends, float *ray_loss, float *grad_weights,
+                        void *workspace, float *loss, float *inv_norm, void *stream);
+int ced_distortion_loss_density(int64_t n_rays, int64_t n_samples, const int64_t *packed_info, const float *sigmas,
+                                const float *t_starts, const float *t_ends, float *ray_loss, float *d_sigmas,
+                                void *workspace, float *loss, float *inv_norm, void *stream);
+
 /* Weight gradient of a bias-free dense layer over the sample stream:
  *   dw[o][i] = sum_s dy[s][o] * x[s][i],   x [n, n_in], dy [n, n_out], dw [n_out, n_in], widths 1..64, all fp32,
  * x and dy contiguous and 16-byte aligned.  Replaces the weight-gradient GEMM of tiny-cuda-nn's Network backward
