@@ -10,7 +10,8 @@ from . import encoder, hashgrid, synthetic  # noqa: F401  (no GPU / native code 
 
 def __getattr__(name):
     # torch-facing modules are imported lazily so that `import ced_nerf_amd` stays cheap
-    if name in ("ops", "nerfacc_api", "model", "render", "utils", "dist", "_lib", "cameras", "train", "profiling", "video"):
+    if name in ("ops", "nerfacc_api", "model", "render", "utils", "dist", "_lib", "cameras", "train", "profiling", "video",
+                "metrics"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

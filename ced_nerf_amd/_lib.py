@@ -14,7 +14,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("CED_NERF_LIB", os.path.join(_PKG, "libcednerf_hip.so"))
 SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "field_half.hip", "field_mixed.hip", "frame.hip", "occgrid.hip",
-           "raygen.hip", "wgrad.hip", "pixels.hip", "accel.hip", "linear.hip", "mlp.hip", "train_glue.hip", "losses.hip"]
+           "raygen.hip", "wgrad.hip", "pixels.hip", "accel.hip", "linear.hip", "mlp.hip", "train_glue.hip", "losses.hip",
+           "metrics.hip"]
 MLP_F32, MLP_F16X2, MLP_F16, MLP_F32_HEAD16X2 = 0, 1, 2, 3          # ced_field_desc.mlp_precision
 # "f32+h16x2": sigma chain exact fp32 (counts / opacity / depth bit-identical to "f32"), colour head on split-fp16 MFMAs
 MLP_PRECISIONS = {"f32": MLP_F32, "f16x2": MLP_F16X2, "f16": MLP_F16, "f32+h16x2": MLP_F32_HEAD16X2}
@@ -110,6 +111,10 @@ PROTOTYPES = {
     "ced_distortion_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "ced_distortion_loss": (C.c_int, [_i64, _i64] + [_vp] * 10),
     "ced_distortion_loss_density": (C.c_int, [_i64, _i64] + [_vp] * 10),
+    "ced_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32, _i32]),
+    "ced_ssim": (C.c_int, [_i64, _i64, _i64, _i64, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), C.c_double, C.c_double,
+                           C.c_double, _i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_float), _i32, _vp, _vp, _vp, _vp,
+                           _vp, _vp]),
     "ced_frame_to_rgb8": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp]),
     "ced_depth_to_u8": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ced_scatter_pixels": (C.c_int, [_i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),

@@ -377,6 +377,46 @@ def distortion_loss_density(packed_info, sigmas, t_starts, t_ends, want_grad: bo
     return loss, inv_norm, ray_loss, d_sig
 
 
+def _image_batch(t, name: str):
+    """A [N,C,H,W] float32 CUDA tensor of any strides (read in place through them)."""
+    if not t.is_cuda:
+        raise NotImplementedError(f"Only support cuda inputs ({name} is on {t.device}).")
+    _check_current_device(t.device.index, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    if t.dim() != 4:
+        raise ValueError(f"{name} must be [N,C,H,W], got shape {tuple(t.shape)}")
+    return (C.c_int64 * 4)(*t.stride())
+
+
+def ssim(X, Y, win, levels: int, weights=None, data_range: float = 1.0, K=(0.01, 0.03), nonnegative: bool = False,
+         want_mean: bool = True, want_mse: bool = False, want_levels: bool = False):
+    """ced_ssim on two [N,C,H,W] float32 CUDA tensors (any strides): (per_image [N] f32, mean [] f32 or None,
+    mse [N] f64 or None, level_means [levels,N,C,2] f64 or None), all on the device, no host synchronisation.
+    win: the fp32 window (sequence of win_size floats); weights: None = single-scale SSIM (levels 1), else the MS-SSIM
+    level weights (levels of them); levels 0 = the MSE alone."""
+    sx, sy = _image_batch(X, "X"), _image_batch(Y, "Y")
+    if tuple(X.shape) != tuple(Y.shape):
+        raise ValueError(f"X and Y must have the same shape, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    N, Ch, H, W = X.shape
+    win_arr = None if win is None else (C.c_float * len(win))(*[float(v) for v in win])
+    w_arr = None if weights is None else (C.c_float * len(weights))(*[float(v) for v in weights])
+    win_size = len(win) if win is not None else 1
+    L = _lib.lib()
+    nbytes = L.ced_ssim_workspace_bytes(N, Ch, H, W, win_size, levels)
+    _lib.check(0 if nbytes >= 0 else int(nbytes), "ssim_workspace_bytes")
+    dev = X.device
+    ws = torch.empty(((nbytes + 7) // 8,), device=dev, dtype=torch.float64)      # 8-byte aligned
+    per_image = torch.empty((N,), device=dev) if levels > 0 else None
+    mean = torch.empty((), device=dev) if want_mean and levels > 0 else None
+    mse = torch.empty((N,), device=dev, dtype=torch.float64) if want_mse or levels == 0 else None
+    lvl = torch.empty((levels, N, Ch, 2), device=dev, dtype=torch.float64) if want_levels and levels > 0 else None
+    rc = L.ced_ssim(N, Ch, H, W, _p(X), sx, _p(Y), sy, float(data_range), float(K[0]), float(K[1]), win_size, win_arr,
+                    levels, w_arr, int(bool(nonnegative)), _p(per_image), _p(mean), _p(mse), _p(lvl), _p(ws), _stream())
+    _lib.check(rc, "ssim")
+    return per_image, mean, mse, lvl
+
+
 def frame_to_rgb8(rgb, flip_w: bool = True):
     """ced_frame_to_rgb8: [H,W,3] float colours -> [H,W,3] uint8 (x 255, truncated), flipped along the width as the
     reference's video frames are (train_real.py:556)."""

@@ -322,6 +322,31 @@ int ced_distortion_loss_density(int64_t n_rays, int64_t n_samples, const int64_t
                                 const float *t_starts, const float *t_ends, float *ray_loss, float *d_sigmas,
                                 void *workspace, float *loss, float *inv_norm, void *stream);
 
+/* Image metrics of the reference's evaluation (train_real.py:494-500): single-scale SSIM and MS-SSIM as pytorch_msssim
+ * 1.0.0 computes ssim / ms_ssim, and the per-image MSE of the PSNR, over N images of C channels, H x W, fp32 in.
+ * x, y: level-0 images read through the element strides x_strides / y_strides [4] = (n, c, h, w) (host arrays; an
+ * [H,W,3] frame permuted to [1,3,H,W] is read in place).  win [win_size]: the normalised Gaussian window (host, fp32,
+ * win_size odd, <= 15), applied as a separable valid convolution.  Per level: mu, sigma^2 = E[x^2] - mu^2, ...,
+ *   cs = (2 sigma_xy + C2) / (sigma_x^2 + sigma_y^2 + C2),  ssim = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1) * cs,
+ * C1 = (k1 data_range)^2, C2 = (k2 data_range)^2, each map averaged over the valid region per (image, channel); between
+ * levels both images go through avg_pool2d(2, stride 2, padding (H%2, W%2)) with count_include_pad.
+ * levels: 1..5 pyramid levels; 0 = the MSE alone (any size; per_image, mean, level_means must be NULL, mse required).
+ * weights [levels] (host, fp32): NULL = single-scale SSIM (levels must be 1), the mean of the ssim map, relu'd when
+ * nonnegative != 0; else MS-SSIM = prod_{l<levels-1} relu(cs_l)^w_l * relu(ssim_last)^w_last.  Every level must be at
+ * least win_size on each side (pytorch_msssim's stricter min side > (win_size - 1) * 16 is the caller's check).
+ * Outputs (device): per_image [N] fp32 (the mean over the channels), mean (may be NULL) the mean over the images,
+ * mse [N] fp64 (may be NULL) = sum (x - y)^2 / (C H W) of level 0, level_means [levels][N][C][2] fp64 (may be NULL) =
+ * the means of the cs and ssim maps of every level before any relu.
+ * Precision: the filtered moments and the pooled levels are fp64 (no cancellation of E[x^2] against mu^2 beside C2).
+ * Deterministic: fp64 partials summed in a fixed order, no float atomics; image i's results do not depend on the other
+ * images of the batch.  workspace: ced_ssim_workspace_bytes(n, c, h, w, win_size, levels) bytes, 8-byte aligned.  No
+ * host synchronisation, no allocation; levels + 2 launches on the stream (2 for the MSE alone). */
+int64_t ced_ssim_workspace_bytes(int64_t n, int64_t c, int64_t h, int64_t w, int32_t win_size, int32_t levels);
+int ced_ssim(int64_t n, int64_t c, int64_t h, int64_t w, const float *x, const int64_t *x_strides, const float *y,
+             const int64_t *y_strides, double data_range, double k1, double k2, int32_t win_size, const float *win,
+             int32_t levels, const float *weights, int32_t nonnegative, float *per_image, float *mean, double *mse,
+             double *level_means, void *workspace, void *stream);
+
 /* Weight gradient of a bias-free dense layer over the sample stream:
  *   dw[o][i] = sum_s dy[s][o] * x[s][i],   x [n, n_in], dy [n, n_out], dw [n_out, n_in], widths 1..64, all fp32,
  * x and dy contiguous and 16-byte aligned.  Replaces the weight-gradient GEMM of tiny-cuda-nn's Network backward
