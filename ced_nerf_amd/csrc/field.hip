@@ -5,8 +5,8 @@
 // query_density :367-445, _query_rgb :447-466), i.e. five tiny-cuda-nn launches plus ~12 torch
 // glue kernels per call, and the sigma_fn / rgb_sigma_fn closures of cednerf/utils.py:74-104,181-195.
 //
-// Execution shape (CDNA4): one 768-thread workgroup per CU (3 waves per SIMD; other launch geometries
-// behind ced_set_option("field_variant")), persistent over 32-sample wave tiles.  All nine weight matrices (~86 KB fp32, pre-swizzled by the host into
+// Execution shape (CDNA4): one 1024-thread workgroup per CU (4 waves per SIMD; 512 threads for temporal tables),
+// persistent over 32-sample wave tiles.  All nine weight matrices (~86 KB fp32, pre-swizzled by the host into
 // MFMA A-fragment order) are staged into LDS once per workgroup and read with conflict-free
 // ds_read_b128.  The GEMMs run on v_mfma_f32_16x16x4_f32 with D^T = W * X^T (neurons on the
 // accumulator rows, samples on lanes): exact fp32, an ascending-k fused-multiply-add chain,
@@ -20,7 +20,6 @@
 // 4i + 2(g&1) + (g>>1), i = 0..3, of its 16 samples (128 gathers per sample spread over 4 lanes) and one
 // v_permlane16_swap per level pair puts the features in operand order.
 #include <atomic>
-#include <cstdlib>
 #include <cstring>
 
 #include "ced_common.hpp"
@@ -97,8 +96,8 @@ struct HashBwdArgs {
 // Table gradient, second form (round 2): FOUR adjacent lanes = (x corner, feature) of one sample's entry pair, one level
 // per blockIdx.y.  The two x corners of a (y, z) corner are adjacent table entries whenever the cell's x index is even
 // (dense levels: always adjacent; hashed levels: (x ^ h) and ((x + 1) ^ h) differ in bit 0 only), so the four lanes add
-// into 16 contiguous bytes and the memory side sees ONE request where the first form (hash_backward_kernel<., true>,
-// one corner per instruction) sent two.  Runs of consecutive samples with the same entry are still summed across the
+// into 16 contiguous bytes and the memory side sees ONE request where a form with one corner per instruction sent
+// two.  Runs of consecutive samples with the same entry are still summed across the
 // wave first (segmented scan, stride 4).  The atomics are what bounds this kernel (requests, not bytes).
 __global__ __launch_bounds__(256) void hash_table_grad_kernel(HashBwdArgs A)
 {
@@ -235,24 +234,15 @@ __global__ __launch_bounds__(256) void hash_table_grad_temporal_kernel(HashBwdAr
   }
 }
 
-// LEVEL_MAJOR: blockIdx.y = level, consecutive lanes = consecutive samples -- a wave's atomics then fall into one
-// level's region and, for ray-ordered samples, into few cache lines (used for the table gradient).  Otherwise 16
-// consecutive lanes = the 16 levels of one sample, whose position-gradient contributions are summed inside the
-// 16-lane group in a fixed order and stored without atomics (used for dx).
-template <bool F16, bool LEVEL_MAJOR>
+// Position gradient: 16 consecutive lanes = the 16 levels of one sample, whose contributions are summed inside the
+// 16-lane group in a fixed order and stored without atomics.
+template <bool F16>
 __global__ __launch_bounds__(256) void hash_backward_kernel(HashBwdArgs A)
 {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // LEVEL_MAJOR: two adjacent lanes = the two features of one sample's entries, so one atomic instruction covers
-    // 32 entries x 2 adjacent dwords (half the cache-line requests of 64 entries x 1 dword, twice)
-    const int64_t i = LEVEL_MAJOR ? (gid >> 1) : (gid >> 4);
-    const int feat = (int)(gid & 1);
-    const int l = LEVEL_MAJOR ? (int)blockIdx.y : (int)(gid & 15);
+    const int64_t i = gid >> 4;
+    const int l = (int)(gid & 15);
     float gx[3] = { 0.0f, 0.0f, 0.0f };
-    uint32_t pend_idx[8];
-    float pend_val[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { pend_idx[c] = 0xffffffffu; pend_val[c] = 0.0f; }
     if (i < A.n && l < A.n_levels) {
         const float g0 = A.dy[(i * A.n_levels + l) * 2], g1 = A.dy[(i * A.n_levels + l) * 2 + 1];
         if (g0 != 0.0f || g1 != 0.0f) {
@@ -274,76 +264,41 @@ __global__ __launch_bounds__(256) void hash_backward_kernel(HashBwdArgs A)
             for (int c = 0; c < 8; ++c) {
                 const uint32_t px = g[0] + (c & 1), py = g[1] + ((c >> 1) & 1), pz = g[2] + ((c >> 2) & 1);
                 const float wx = (c & 1) ? fr[0] : om[0], wy = (c & 2) ? fr[1] : om[1], wz = (c & 4) ? fr[2] : om[2];
-                const float w = (wx * wy) * wz;
+                const float wxy = wx * wy;
                 uint32_t idx = hashed ? (px ^ (py * 2654435761u) ^ (pz * 805459861u)) : (px + py * res + pz * res * res);
                 idx = off + idx % size;
-                if constexpr (!LEVEL_MAJOR) {
-                    float f0, f1;
-                    if constexpr (!F16) {
-                        const float2 v = reinterpret_cast<const float2 *>(A.table)[idx];
-                        f0 = v.x; f1 = v.y;
-                    } else {
-                        const uint32_t u = reinterpret_cast<const uint32_t *>(A.table)[idx];
-                        f0 = half_bits_to_float((uint16_t)(u & 0xffffu)); f1 = half_bits_to_float((uint16_t)(u >> 16));
-                    }
-                    // d w / d pos_a = +-(product of the other two factors)
-                    const float dot = (f0 * g0 + f1 * g1) * (A.dx_scaled ? sc : 1.0f);
-                    gx[0] += dot * ((c & 1) ? (wy * wz) : -(wy * wz));
-                    gx[1] += dot * ((c & 2) ? (wx * wz) : -(wx * wz));
-                    gx[2] += dot * ((c & 4) ? (wx * wy) : -(wx * wy));
+                float f0, f1;
+                if constexpr (!F16) {
+                    const float2 v = reinterpret_cast<const float2 *>(A.table)[idx];
+                    f0 = v.x; f1 = v.y;
                 } else {
-                    pend_idx[c] = idx;
-                    pend_val[c] = w * (feat ? g1 : g0);
+                    const uint32_t u = reinterpret_cast<const uint32_t *>(A.table)[idx];
+                    f0 = half_bits_to_float((uint16_t)(u & 0xffffu)); f1 = half_bits_to_float((uint16_t)(u >> 16));
                 }
+                // d w / d pos_a = +-(product of the other two factors)
+                const float dot = (f0 * g0 + f1 * g1) * (A.dx_scaled ? sc : 1.0f);
+                gx[0] += dot * ((c & 1) ? (wy * wz) : -(wy * wz));
+                gx[1] += dot * ((c & 2) ? (wx * wz) : -(wx * wz));
+                gx[2] += dot * ((c & 4) ? wxy : -wxy);
             }
         }
     }
-    if constexpr (LEVEL_MAJOR) {
-        // Consecutive samples of a ray sit in the same cell of the coarse and middle levels: sum the runs of equal
-        // entries across the wave first (segmented scan over same-feature lanes, stride 2) and let the last lane of
-        // a run issue ONE atomic -- the atomics are what bounds this kernel (one L2 request per cache line touched).
-        const int lane = threadIdx.x & 63;
+    // sum over the 16 levels of the sample (lanes 16k..16k+15), fixed order
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t idx = pend_idx[c];
-            float v = pend_val[c];
-            const uint32_t prev = __shfl_up(idx, 2, 64);
-            int head = (lane < 2 || prev != idx) ? 1 : 0;
+    for (int off = 8; off > 0; off >>= 1) {
 #pragma unroll
-            for (int d = 2; d < 64; d <<= 1) {
-                const float v_up = __shfl_up(v, d, 64);
-                const int h_up = __shfl_up(head, d, 64);
-                if (lane >= d && !head) { v += v_up; head |= h_up; }
-            }
-            const uint32_t next = __shfl_down(idx, 2, 64);
-            const bool last = lane >= 62 || next != idx;
-            if (last && idx != 0xffffffffu && v != 0.0f) unsafeAtomicAdd(A.grad_table + (size_t)idx * 2 + feat, v);
-        }
+        for (int a = 0; a < 3; ++a) gx[a] += __shfl_down(gx[a], off, 16);
     }
-    if constexpr (!LEVEL_MAJOR) {
-        // sum over the 16 levels of the sample (lanes 16k..16k+15), fixed order
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) gx[a] += __shfl_down(gx[a], off, 16);
-        }
-        if (l == 0 && i < A.n) {
-            A.dx[3 * i] = gx[0]; A.dx[3 * i + 1] = gx[1]; A.dx[3 * i + 2] = gx[2];
-        }
+    if (l == 0 && i < A.n) {
+        A.dx[3 * i] = gx[0]; A.dx[3 * i + 1] = gx[1]; A.dx[3 * i + 2] = gx[2];
     }
 }
 
-// Diagnostic knobs of ced_set_option: process-wide, read by concurrently rendering threads -> atomics (relaxed: each is
-// an independent launch property; no setting changes a result).
-std::atomic<int> g_field_stagger{ 0 };          // field kernel: start-up phase offset between the waves of a SIMD, in s_sleep(127) units
+// Options of ced_set_option: process-wide, read by concurrently rendering threads -> atomics (relaxed: each is an
+// independent launch property; no setting changes a result).
 std::atomic<int> g_field_spread_tiles{ 2 };     // field kernels: tile -> wave mapping (field_device.hpp: field_tile_range)
-std::atomic<int> g_march_early_out{ 1 };        // frame renderer: conservative brick-level early-out
 std::atomic<int> g_march_two_pass{ -1 };        // frame renderer: first iteration as culling pass + marching of the rest (-1: when there are several grid levels)
-
-// launch-geometry variant of the field kernel (ced_set_option("field_variant", v))
-static std::atomic<int> g_hash_grad_blocks{ [] { const char *e = getenv("CED_HASH_GRAD_BLOCKS"); return e ? atoi(e) : 0; }() };
-static std::atomic<int> g_hash_grad_form{ []  { const char *e = getenv("CED_HASH_GRAD_FORM"); return e ? atoi(e) : 1; }() };   // 0: one corner per instruction
-static std::atomic<int> g_field_variant{ [] { const char *e = getenv("CED_FIELD_VARIANT"); return e ? atoi(e) : 3; }() };
+static std::atomic<int> g_hash_grad_blocks{ 0 }; // table-gradient workgroups per level (0: one per 64 samples)
 
 static int validate_hash(const ced_hash_desc *h, const char *who)
 {
@@ -414,46 +369,25 @@ int launch_field(const ced_field_desc *d, FieldArgs &A, void *stream)
                 "field_forward: hash table larger than 4 GiB");
     CED_REQUIRE(d->max_workgroups >= 0 && d->max_workgroups <= 65536, "field_forward: max_workgroups=%d", d->max_workgroups);
     A.max_blocks = d->max_workgroups;
-    A.stagger = g_field_stagger;
     A.spread_tiles = g_field_spread_tiles;
     if (d->mlp_precision == CED_MLP_F32_HEAD16X2) return launch_field_mixed(A, d->time_mode, stream);
     if (d->mlp_precision != CED_MLP_F32) {
         // the half kernels gather level 4i + g in slot i: the same slot -> level-range mapping as above
         return launch_field_half(A, d->time_mode, d->mlp_precision, stream);
     }
-    // 1024 threads (four waves per SIMD, 128 registers) is the default since the dense levels' pair loads of round 4 (the
-    // kernels fit without scratch: C2 +2.4 %, C3 +2 % over 768 threads); the temporal-table kernels need 250-300 registers
-    // and run two waves per SIMD without scratch instead.
-    const int field_variant = g_field_variant.load(std::memory_order_relaxed);
-    const int variant = (field_variant >= 2 && field_variant <= 3 && A.temporal) ? 1 : field_variant;
-    auto launch = [&](auto kernel, int nt, int threads) {
-        const int64_t n_tiles = (A.n + 16 * nt - 1) / (16 * nt);
-        const int waves = threads / 64;
-        int64_t blocks = A.spread_tiles ? (n_tiles + 3) / 4 : (n_tiles + waves - 1) / waves;
-        const int cap = A.max_blocks > 0 ? A.max_blocks : kFieldBlocksDefault;
-        if (blocks > cap) blocks = cap;                                   // one resident workgroup per CU, persistent over tiles
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, A);
-    };
-    const int sel = (d->time_mode ? 1 : 0) | (A.table_dtype ? 2 : 0) | (A.temporal ? 4 : 0);
-#define CED_FIELD_CASE(NT_, TH_)                                                                                \
-    switch (sel) {                                                                                              \
-    case 0: launch(field_kernel<false, false, false, NT_, TH_>, NT_, TH_); break;                               \
-    case 1: launch(field_kernel<true, false, false, NT_, TH_>, NT_, TH_); break;                                \
-    case 2: launch(field_kernel<false, true, false, NT_, TH_>, NT_, TH_); break;                                \
-    case 3: launch(field_kernel<true, true, false, NT_, TH_>, NT_, TH_); break;                                 \
-    case 4: launch(field_kernel<false, false, true, NT_, TH_>, NT_, TH_); break;                                \
-    case 5: launch(field_kernel<true, false, true, NT_, TH_>, NT_, TH_); break;                                 \
-    case 6: launch(field_kernel<false, true, true, NT_, TH_>, NT_, TH_); break;                                 \
-    default: launch(field_kernel<true, true, true, NT_, TH_>, NT_, TH_); break;                                 \
+    // 2 x 1024 threads (four waves per SIMD, 128 registers) since the dense levels' pair loads of round 4 (the kernels
+    // fit without scratch: C2 +2.4 %, C3 +2 % over 768 threads); the temporal-table kernels need 250-300 registers and
+    // run 2 x 512, two waves per SIMD, without scratch instead.
+    switch ((d->time_mode ? 1 : 0) | (A.table_dtype ? 2 : 0) | (A.temporal ? 4 : 0)) {
+    case 0: launch_field_grid<2, 1024>(field_kernel<false, false, false, 2, 1024>, A, stream); break;
+    case 1: launch_field_grid<2, 1024>(field_kernel<true, false, false, 2, 1024>, A, stream); break;
+    case 2: launch_field_grid<2, 1024>(field_kernel<false, true, false, 2, 1024>, A, stream); break;
+    case 3: launch_field_grid<2, 1024>(field_kernel<true, true, false, 2, 1024>, A, stream); break;
+    case 4: launch_field_grid<2, 512>(field_kernel<false, false, true, 2, 512>, A, stream); break;
+    case 5: launch_field_grid<2, 512>(field_kernel<true, false, true, 2, 512>, A, stream); break;
+    case 6: launch_field_grid<2, 512>(field_kernel<false, true, true, 2, 512>, A, stream); break;
+    default: launch_field_grid<2, 512>(field_kernel<true, true, true, 2, 512>, A, stream); break;
     }
-    switch (variant) {
-    case 1: CED_FIELD_CASE(2, 512) break;
-    case 2: CED_FIELD_CASE(2, 768) break;
-    case 3: CED_FIELD_CASE(2, 1024) break;
-    case 4: CED_FIELD_CASE(1, 1024) break;
-    default: CED_FIELD_CASE(4, 512) break;
-    }
-#undef CED_FIELD_CASE
     return check_launch("field_forward");
 }
 
@@ -462,18 +396,9 @@ int launch_field(const ced_field_desc *d, FieldArgs &A, void *stream)
 extern "C" int ced_set_option(const char *key, int value)
 {
     CED_REQUIRE(key != nullptr, "set_option: null key");
-    if (strcmp(key, "field_stagger") == 0) {
-        CED_REQUIRE(value >= 0 && value <= 64, "set_option: field_stagger must be 0..64");
-        ced::g_field_stagger = value;
-        return CED_OK;
-    }
     if (strcmp(key, "field_spread_tiles") == 0) {
         CED_REQUIRE(value >= 0 && value <= 2, "set_option: field_spread_tiles must be 0, 1 or 2 (field_tile_range)");
         ced::g_field_spread_tiles = value;
-        return CED_OK;
-    }
-    if (strcmp(key, "march_early_out") == 0) {
-        ced::g_march_early_out = value != 0;
         return CED_OK;
     }
     if (strcmp(key, "march_two_pass") == 0) {
@@ -481,29 +406,9 @@ extern "C" int ced_set_option(const char *key, int value)
         ced::g_march_two_pass = value;
         return CED_OK;
     }
-    if (strcmp(key, "half_variant") == 0) {
-        CED_REQUIRE(value >= 0 && value <= 4, "set_option: half_variant must be 0..3 (4: diagnostic builds only)");
-        ced::set_half_variant(value);
-        return CED_OK;
-    }
     if (strcmp(key, "hash_grad_blocks") == 0) {
         CED_REQUIRE(value >= 0 && value <= (1 << 20), "set_option: hash_grad_blocks must be 0 (no cap) .. 2^20");
         ced::g_hash_grad_blocks = value;
-        return CED_OK;
-    }
-    if (strcmp(key, "hash_grad_form") == 0) {
-        CED_REQUIRE(value == 0 || value == 1, "set_option: hash_grad_form must be 0 or 1");
-        ced::g_hash_grad_form = value;
-        return CED_OK;
-    }
-    if (strcmp(key, "mixed_variant") == 0) {
-        CED_REQUIRE(value >= 0 && value <= 2, "set_option: mixed_variant must be 0 (auto), 1 (512 threads) or 2 (768)");
-        ced::set_mixed_variant(value);
-        return CED_OK;
-    }
-    if (strcmp(key, "field_variant") == 0) {
-        CED_REQUIRE(value >= 0 && value <= 4, "set_option: field_variant must be 0..4");
-        ced::g_field_variant = value;
         return CED_OK;
     }
     ced::set_error("set_option: unknown key '%s'", key);
@@ -656,13 +561,9 @@ extern "C" int ced_hash_encode_backward(const ced_hash_desc *desc, int64_t n, co
         A.size[l] = desc->size[l]; A.hashed[l] = desc->hashed[l];
     }
     const dim3 block(256);
-    // table gradient: level-major; position gradient (optional): sample-major, no atomics
-    if (!grad_table) {
-        // position gradient only (the caller runs the table gradient elsewhere, e.g. on another stream)
-    } else if (ced::g_hash_grad_form == 0) {
-        const dim3 grid_t((unsigned)((2 * n + 255) / 256), (unsigned)desc->n_levels);
-        hipLaunchKernelGGL((ced::hash_backward_kernel<false, true>), grid_t, block, 0, (hipStream_t)stream, A);
-    } else {
+    // table gradient: level-major; position gradient (optional): sample-major, no atomics.  Without grad_table only the
+    // position gradient runs (the caller runs the table gradient elsewhere, e.g. on another stream).
+    if (grad_table) {
         int64_t gx = (4 * n + 255) / 256;
         const int cap = ced::g_hash_grad_blocks;                // workgroups per level; <= 0: one per 64 samples
         if (cap > 0 && gx > cap) gx = cap;
@@ -671,8 +572,8 @@ extern "C" int ced_hash_encode_backward(const ced_hash_desc *desc, int64_t n, co
     }
     if (dx) {
         const dim3 grid_x((unsigned)((n * 16 + 255) / 256));
-        if (A.table_dtype) hipLaunchKernelGGL((ced::hash_backward_kernel<true, false>), grid_x, block, 0, (hipStream_t)stream, A);
-        else hipLaunchKernelGGL((ced::hash_backward_kernel<false, false>), grid_x, block, 0, (hipStream_t)stream, A);
+        if (A.table_dtype) hipLaunchKernelGGL(ced::hash_backward_kernel<true>, grid_x, block, 0, (hipStream_t)stream, A);
+        else hipLaunchKernelGGL(ced::hash_backward_kernel<false>, grid_x, block, 0, (hipStream_t)stream, A);
     }
     return ced::check_launch("hash_encode_backward");
 }

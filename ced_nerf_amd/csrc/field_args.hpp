@@ -1,5 +1,6 @@
 // Kernel-argument block of the fused field kernel (field.hip), shared with the frame renderer.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdint>
 
@@ -26,7 +27,6 @@ struct FieldArgs {
     int use_div, time_mode;
     const void *weights;                              // packed blob of the descriptor's mlp_precision
     int table_dtype, temporal;
-    int stagger;                                      // start-up phase offset between SIMD-mates (s_sleep(127) units)
     int spread_tiles;                                 // tile -> wave mapping (field.hip); ced_set_option("field_spread_tiles")
     int level_mode;                                   // 2 bits per gather slot: 0 mixed, 1 all dense, 2 all hashed, 3 all dense and cannot wrap
     int max_blocks;                                   // workgroups of the launch (ced_field_desc.max_workgroups; <= 0: one per CU)
@@ -35,18 +35,28 @@ struct FieldArgs {
     uint32_t res[CED_MAX_LEVELS], offset[CED_MAX_LEVELS], size[CED_MAX_LEVELS], hashed[CED_MAX_LEVELS];
 };
 
-extern std::atomic<int> g_march_early_out;
 extern std::atomic<int> g_march_two_pass;
 extern std::atomic<int> g_field_spread_tiles;
 constexpr int kFieldBlocksDefault = 256;      // one persistent workgroup per CU
+
+// Launches a persistent field kernel of NT 16-sample tiles per wave and THREADS threads per workgroup: enough
+// workgroups for the tiles under A.spread_tiles, at most A.max_blocks (<= 0: one resident workgroup per CU).
+template <int NT, int THREADS, typename Kernel>
+void launch_field_grid(Kernel kernel, const FieldArgs &A, void *stream)
+{
+    const int64_t n_tiles = (A.n + 16 * NT - 1) / (16 * NT);
+    constexpr int waves = THREADS / 64;
+    int64_t blocks = A.spread_tiles ? (n_tiles + 3) / 4 : (n_tiles + waves - 1) / waves;
+    const int cap = A.max_blocks > 0 ? A.max_blocks : kFieldBlocksDefault;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
+}
 
 // Fills the field/hash parts of A from the descriptor, validates, and launches on `stream`.
 int launch_field(const ced_field_desc *d, FieldArgs &A, void *stream);
 // field_half.hip: the f16x2 / f16 MLP variants (A already filled by launch_field)
 int launch_field_half(FieldArgs &A, int time_mode, int precision, void *stream);
-void set_half_variant(int v);
 // field_mixed.hip: exact sigma chain + split-fp16 colour head (CED_MLP_F32_HEAD16X2)
 int launch_field_mixed(FieldArgs &A, int time_mode, void *stream);
-void set_mixed_variant(int v);
 
 }  // namespace ced

@@ -116,14 +116,8 @@ __device__ __forceinline__ void hash_level(const LevelConst &L, const void *__re
     for (int a = 0; a < 3; ++a) {
         // p >= 0.5: the conversion truncates = floor, and p - floor(p) is exact, which is what v_fract_f32 returns
         const float p = x[a] * L.scale + 0.5f;
-#ifdef CED_AB_NO_FRACT
-        const float fl = __builtin_floorf(p);
-        g[a] = (uint32_t)fl;
-        fr[a] = p - fl;
-#else
         g[a] = (uint32_t)p;
         fr[a] = __builtin_amdgcn_fractf(p);
-#endif
         om[a] = 1.0f - fr[a];
     }
     // byte strides: x is the entry size (a power of two: a shift); dense levels have res^2 * EB < 2^24, so
@@ -158,11 +152,7 @@ __device__ __forceinline__ void hash_level(const LevelConst &L, const void *__re
             db = dx < dw ? dx : dw;
         }
         const uint32_t idxb = (MODE == 1 || MODE == 3) ? db : (MODE == 2) ? hb : (hashed ? hb : db);
-#ifdef CED_AB_GATHER_WINDOW            // diagnostic builds (tools/ab_build.sh): the gathers of a level confined to a byte window
-        off[c] = L.offb + (idxb & (uint32_t)(CED_AB_GATHER_WINDOW));
-#else
         off[c] = L.offb + idxb;
-#endif
         w[c] = wxy[cx + 2 * cy] * (cz ? fr[2] : om[2]);
     }
     const char *tb = reinterpret_cast<const char *>(table);

@@ -22,8 +22,6 @@
 // inputs are laid out likewise: lane group g computes the eight Frequency features of dimension g,
 // gathers hash levels {g, 4+g, 8+g, 12+g} (input columns are permuted on the host to match), and the
 // last layer of mlp_base is packed so that a lane's four outputs are its own mlp_head inputs.
-#include <atomic>
-#include <cstdlib>
 #include <cstring>
 
 #include "ced_common.hpp"
@@ -330,64 +328,35 @@ void pack_half_layer(const float *w, int n_out, int n_in, int nb, int ks, int fr
     }
 }
 
-static std::atomic<int> g_half_variant{ [] { const char *e = getenv("CED_HALF_VARIANT"); return e ? atoi(e) : 0; }() };
-void set_half_variant(int v) { g_half_variant = v; }
-
 int launch_field_half(FieldArgs &A, int time_mode, int precision, void *stream)
 {
-    auto launch = [&](auto kernel, int nt, int threads) {
-        const int64_t n_tiles = (A.n + 16 * nt - 1) / (16 * nt);
-        const int waves = threads / 64;
-        int64_t blocks = A.spread_tiles ? (n_tiles + 3) / 4 : (n_tiles + waves - 1) / waves;
-        const int cap = A.max_blocks > 0 ? A.max_blocks : kFieldBlocksDefault;
-        if (blocks > cap) blocks = cap;                                   // one resident workgroup per CU, persistent over tiles
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, A);
-    };
+    // Launch geometry (which kernels fit which register cap without scratch: tools/kernel_schedule.py; the choice follows
+    // the round-4 measurements, profiles/r04_ab_half_geometry.txt): temporal tables 2 x 512 threads (228-248 registers,
+    // scratch above 512 threads); f16x2 2 x 768 with a time encoding, else 2 x 1024; f16 2 x 768.
     const int sel = (time_mode ? 1 : 0) | (A.table_dtype ? 2 : 0) | (A.temporal ? 4 : 0);
-#define CED_HALF_CASE(SP_, NT_, TH_)                                                                            \
-    switch (sel) {                                                                                              \
-    case 0: launch(field_half_kernel<false, false, false, SP_, NT_, TH_>, NT_, TH_); break;                     \
-    case 1: launch(field_half_kernel<true, false, false, SP_, NT_, TH_>, NT_, TH_); break;                      \
-    case 2: launch(field_half_kernel<false, true, false, SP_, NT_, TH_>, NT_, TH_); break;                      \
-    case 3: launch(field_half_kernel<true, true, false, SP_, NT_, TH_>, NT_, TH_); break;                       \
-    case 4: launch(field_half_kernel<false, false, true, SP_, NT_, TH_>, NT_, TH_); break;                      \
-    case 5: launch(field_half_kernel<true, false, true, SP_, NT_, TH_>, NT_, TH_); break;                       \
-    case 6: launch(field_half_kernel<false, true, true, SP_, NT_, TH_>, NT_, TH_); break;                       \
-    default: launch(field_half_kernel<true, true, true, SP_, NT_, TH_>, NT_, TH_); break;                       \
-    }
-    // Launch geometry ("half_variant": 0 = automatic, 1 = 2 x 512, 2 = 2 x 1024, 3 = 2 x 768 threads; env CED_HALF_AUTO_*
-    // override the automatic picks for A/B runs).  Which kernels fit which register cap without scratch is printed by
-    // tools/kernel_schedule.py; the automatic rule follows the round-4 measurements (profiles/r04_ab_half_geometry.txt).
-    static const int auto_plain_split = [] { const char *e = getenv("CED_HALF_AUTO_F16X2"); return e ? atoi(e) : 2; }();
-    static const int auto_plain = [] { const char *e = getenv("CED_HALF_AUTO_F16"); return e ? atoi(e) : 3; }();
-    static const int auto_te = [] { const char *e = getenv("CED_HALF_AUTO_TE"); return e ? atoi(e) : 3; }();
-    const int requested_variant = g_half_variant.load(std::memory_order_relaxed);
-    int half_variant = requested_variant;
-    if (half_variant == 0) {
-        if (A.temporal) half_variant = 1;                    // temporal tables: 228-248 registers, scratch above 512 threads
-        else if (time_mode) half_variant = auto_te;
-        else half_variant = precision == CED_MLP_F16X2 ? auto_plain_split : auto_plain;
-    }
     if (precision == CED_MLP_F16X2) {
-        switch (half_variant) {
-        case 1: CED_HALF_CASE(true, 2, 512) break;
-        case 2: CED_HALF_CASE(true, 2, 1024) break;
-#ifdef CED_AB_HALF_NT1
-        case 4: CED_HALF_CASE(true, 1, 1024) break;
-#endif
-        default: CED_HALF_CASE(true, 2, 768) break;
+        switch (sel) {
+        case 0: launch_field_grid<2, 1024>(field_half_kernel<false, false, false, true, 2, 1024>, A, stream); break;
+        case 1: launch_field_grid<2, 768>(field_half_kernel<true, false, false, true, 2, 768>, A, stream); break;
+        case 2: launch_field_grid<2, 1024>(field_half_kernel<false, true, false, true, 2, 1024>, A, stream); break;
+        case 3: launch_field_grid<2, 768>(field_half_kernel<true, true, false, true, 2, 768>, A, stream); break;
+        case 4: launch_field_grid<2, 512>(field_half_kernel<false, false, true, true, 2, 512>, A, stream); break;
+        case 5: launch_field_grid<2, 512>(field_half_kernel<true, false, true, true, 2, 512>, A, stream); break;
+        case 6: launch_field_grid<2, 512>(field_half_kernel<false, true, true, true, 2, 512>, A, stream); break;
+        default: launch_field_grid<2, 512>(field_half_kernel<true, true, true, true, 2, 512>, A, stream); break;
         }
     } else {
-        switch (half_variant) {
-        case 1: CED_HALF_CASE(false, 2, 512) break;
-        case 2: CED_HALF_CASE(false, 2, 1024) break;
-#ifdef CED_AB_HALF_NT1
-        case 4: CED_HALF_CASE(false, 1, 1024) break;
-#endif
-        default: CED_HALF_CASE(false, 2, 768) break;
+        switch (sel) {
+        case 0: launch_field_grid<2, 768>(field_half_kernel<false, false, false, false, 2, 768>, A, stream); break;
+        case 1: launch_field_grid<2, 768>(field_half_kernel<true, false, false, false, 2, 768>, A, stream); break;
+        case 2: launch_field_grid<2, 768>(field_half_kernel<false, true, false, false, 2, 768>, A, stream); break;
+        case 3: launch_field_grid<2, 768>(field_half_kernel<true, true, false, false, 2, 768>, A, stream); break;
+        case 4: launch_field_grid<2, 512>(field_half_kernel<false, false, true, false, 2, 512>, A, stream); break;
+        case 5: launch_field_grid<2, 512>(field_half_kernel<true, false, true, false, 2, 512>, A, stream); break;
+        case 6: launch_field_grid<2, 512>(field_half_kernel<false, true, true, false, 2, 512>, A, stream); break;
+        default: launch_field_grid<2, 512>(field_half_kernel<true, true, true, false, 2, 512>, A, stream); break;
         }
     }
-#undef CED_HALF_CASE
     return check_launch("field_forward (half-precision MLP)");
 }
 

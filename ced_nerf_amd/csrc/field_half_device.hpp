@@ -24,10 +24,6 @@ __host__ __device__ constexpr int half_base_out_neuron(int p) { return p < 15 ? 
 
 constexpr float kHalfMax = 65504.0f;
 
-#ifndef CED_HALF_MFMA_GUARD
-#define CED_HALF_MFMA_GUARD 3
-#endif
-
 // Elementwise math of the half-precision kernels: since round 4 the SAME deterministic forms as the exact kernel
 // (det_expf, IEEE division and square root).  With the matrix instruction's own summation restated on the CPU
 // (oracle/mfma_f16_model.h) that makes these modes bit-comparable with the oracle's fp16-operand modes: sigma,

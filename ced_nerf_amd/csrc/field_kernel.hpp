@@ -92,11 +92,7 @@ __device__ __forceinline__ void to_operand(const f4 (&D)[NT][4], float (&B)[NT][
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float v = D[j][nb][q];
-#ifdef CED_FIELD_SKELETON
-                if constexpr (false) {
-#else
                 if constexpr (RELU) {
-#endif
                     // ReLU as ONE integer max on the float's bits: non-negative floats order like their bit
                     // patterns, every negative float (and -0) has the sign bit set, i.e. a negative int.
                     // Same result as (v > 0 ? v : 0) for every non-NaN v; the float forms (fmax, compare +
@@ -131,7 +127,6 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
     __shared__ __attribute__((aligned(16))) float lds[BL::TOTAL + 8 * CED_MAX_LEVELS];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
 
     int64_t n_eff = A.n;
@@ -164,12 +159,6 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
     }
     __syncthreads();
 
-    if (A.stagger > 0) {
-        // Waves w, w+4, w+8 of a workgroup share a SIMD and run the same program: offset their phases so
-        // that their MFMA-dense and VALU-dense stretches interleave instead of colliding.
-        const int slot = __builtin_amdgcn_readfirstlane(wave >> 2);
-        for (int k = 0; k < slot * A.stagger; ++k) __builtin_amdgcn_s_sleep(127);
-    }
     const float extent[3] = { A.aabb[3] - A.aabb[0], A.aabb[4] - A.aabb[1], A.aabb[5] - A.aabb[2] };
     // In eval frames every sample carries the same timestamp (cednerf/utils.py:186-193): the two
     // Frequency features of t that this lane feeds to the motion MLP are computed once.
@@ -229,17 +218,6 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
         // Pairs: (S0 | S2) and (S1 | S3) = x | y at the two frequencies, (S4 | S5) = z at both, (S6 | S7) = t at both. ---
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-#ifdef CED_FIELD_SKELETON
-#pragma unroll
-            for (int S = 0; S < 8; ++S) B[j][S] = (S < 6 ? px[j][S >> 1] : tq[j]) * (float)(1 << (2 * (S & 1) + (g >> 1)));
-#elif defined(CED_AB_NO_FREQ_SPLIT)
-#pragma unroll
-            for (int S = 0; S < 8; ++S) {
-                if ((S >> 1) == 3 && shared_time) { B[j][S] = t_feat[S - 6]; continue; }
-                const float v = ((S >> 1) < 3) ? px[j][(S >> 1) < 3 ? (S >> 1) : 0] : tq[j];
-                B[j][S] = det_sinpi_phase(v * (float)(1 << (2 * (S & 1) + (g >> 1))), g & 1);
-            }
-#else
             const bool odd = (g & 1) != 0;
             const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;           // 2^f for the pair's two frequencies
             const float vxy = odd ? px[j][1] : px[j][0];
@@ -262,7 +240,6 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
                 sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
                 B[j][6] = __uint_as_float(sw[0]); B[j][7] = __uint_as_float(sw[1]);
             }
-#endif
         }
         // --- motion MLP 32-64-64-64-(3|6) ---
         mlp_layer<8, 4, NT>(lw + BL::M0, lane, B, D);
@@ -313,12 +290,6 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
             if constexpr (TEMPORAL) temporal_keyframe(tq[j], k_lo[j], t_frac[j]);
         }
         const uint32_t *const ltab = reinterpret_cast<const uint32_t *>(lw + BL::TOTAL);
-#ifdef CED_FIELD_SKELETON   // diagnostic build: MFMA skeleton only (results are meaningless)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) R[j][i] = xn[j][i % 3] + (float)i;
-#else
         // gather slot i of lane group g is level 4i + 2(g&1) + (g>>1): slot i spans levels 4i..4i+3 across the
         // wave, and when those are all dense or all hashed (wave-uniform, decided on the host) only that index
         // form is computed.  The level's constants come from LDS here rather than living in registers.
@@ -344,7 +315,6 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
                     hash_level<F16, TEMPORAL, 0>(L, A.table, xn[j], k_lo[j], t_frac[j], R[j][2 * i], R[j][2 * i + 1]);
             }
         }
-#endif
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             // Slot i holds (f0, f1) of level 4i + h on the even lane group 2h (k-step 2i) and of level
@@ -353,14 +323,9 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
             // of the f1 register leaves k-step 2i in the first and k-step 2i+1 in the second.
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-#ifndef CED_FIELD_SKELETON
                 auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(R[j][2 * i]), __float_as_uint(R[j][2 * i + 1]), false, false);
                 B[j][2 * i] = __uint_as_float(sw[0]);
                 B[j][2 * i + 1] = __uint_as_float(sw[1]);
-#else
-                B[j][2 * i] = R[j][2 * i];
-                B[j][2 * i + 1] = R[j][2 * i + 1];
-#endif
             }
             if (TE) {
 #pragma unroll

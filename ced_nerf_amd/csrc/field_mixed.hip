@@ -11,8 +11,6 @@
 //
 // Same template as the exact kernel (field_kernel.hpp, HEAD16); the packed blob keeps its size: the three head layers
 // sit in their region as fp16 fragments (a plane of high parts, a plane of remainders).
-#include <atomic>
-#include <cstdlib>
 #include <cstring>
 
 #include "ced_common.hpp"
@@ -22,38 +20,19 @@
 
 namespace ced {
 
-// launch geometry (ced_set_option("mixed_variant")): 0 = 768 threads, 512 for the temporal-table kernels (which spill at
-// three waves per SIMD); 1 = 512; 2 = 768
-static std::atomic<int> g_mixed_variant{ [] { const char *e = getenv("CED_MIXED_VARIANT"); return e ? atoi(e) : 0; }() };
-void set_mixed_variant(int v) { g_mixed_variant = v; }
-
 int launch_field_mixed(FieldArgs &A, int time_mode, void *stream)
 {
-    auto launch = [&](auto kernel, int nt, int threads) {
-        const int64_t n_tiles = (A.n + 16 * nt - 1) / (16 * nt);
-        const int waves = threads / 64;
-        int64_t blocks = A.spread_tiles ? (n_tiles + 3) / 4 : (n_tiles + waves - 1) / waves;
-        const int cap = A.max_blocks > 0 ? A.max_blocks : kFieldBlocksDefault;
-        if (blocks > cap) blocks = cap;                                   // one resident workgroup per CU, persistent over tiles
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, A);
-    };
-    const int sel = (time_mode ? 1 : 0) | (A.table_dtype ? 2 : 0) | (A.temporal ? 4 : 0);
-    // 768 threads (three waves per SIMD); the temporal-table kernels run 512 (see field.hip)
-    const int mv = g_mixed_variant.load(std::memory_order_relaxed);
-    const bool small = mv == 1 || (mv == 0 && A.temporal);
-#define CED_MIXED_CASE(TH_)                                                                                    \
-    switch (sel) {                                                                                              \
-    case 0: launch(field_kernel<false, false, false, 2, TH_, true>, 2, TH_); break;                             \
-    case 1: launch(field_kernel<true, false, false, 2, TH_, true>, 2, TH_); break;                              \
-    case 2: launch(field_kernel<false, true, false, 2, TH_, true>, 2, TH_); break;                              \
-    case 3: launch(field_kernel<true, true, false, 2, TH_, true>, 2, TH_); break;                               \
-    case 4: launch(field_kernel<false, false, true, 2, TH_, true>, 2, TH_); break;                              \
-    case 5: launch(field_kernel<true, false, true, 2, TH_, true>, 2, TH_); break;                               \
-    case 6: launch(field_kernel<false, true, true, 2, TH_, true>, 2, TH_); break;                               \
-    default: launch(field_kernel<true, true, true, 2, TH_, true>, 2, TH_); break;                               \
+    // 768 threads (three waves per SIMD); the temporal-table kernels run 512 (they spill at three waves per SIMD)
+    switch ((time_mode ? 1 : 0) | (A.table_dtype ? 2 : 0) | (A.temporal ? 4 : 0)) {
+    case 0: launch_field_grid<2, 768>(field_kernel<false, false, false, 2, 768, true>, A, stream); break;
+    case 1: launch_field_grid<2, 768>(field_kernel<true, false, false, 2, 768, true>, A, stream); break;
+    case 2: launch_field_grid<2, 768>(field_kernel<false, true, false, 2, 768, true>, A, stream); break;
+    case 3: launch_field_grid<2, 768>(field_kernel<true, true, false, 2, 768, true>, A, stream); break;
+    case 4: launch_field_grid<2, 512>(field_kernel<false, false, true, 2, 512, true>, A, stream); break;
+    case 5: launch_field_grid<2, 512>(field_kernel<true, false, true, 2, 512, true>, A, stream); break;
+    case 6: launch_field_grid<2, 512>(field_kernel<false, true, true, 2, 512, true>, A, stream); break;
+    default: launch_field_grid<2, 512>(field_kernel<true, true, true, 2, 512, true>, A, stream); break;
     }
-    if (small) { CED_MIXED_CASE(512) } else { CED_MIXED_CASE(768) }
-#undef CED_MIXED_CASE
     return check_launch("field_forward (fp32 sigma chain, split-fp16 colour head)");
 }
 

@@ -14,13 +14,12 @@
 //                   N_samples, slot and sample bases per frame -- and publishes (alive, done) to pinned host memory;
 //   * THE HOST NEVER WAITS FOR AN ITERATION (the reference syncs at utils.py:231 every time): every kernel reads its
 //     sizes from the plan in device memory, grids are sized by the last PUBLISHED alive count (an upper bound: the
-//     count only falls) and the host enqueues up to `run_ahead` iterations beyond the last one it has seen
+//     count only falls) and the host enqueues up to kRunAhead (1) iteration beyond the last one it has seen
 //     published; iterations enqueued after the frame has finished are empty launches.
 // Pixels, per-iteration schedule and sample counts are bit-identical to the reference loop.
 #include <atomic>
 #include <cfloat>
 #include <chrono>
-#include <cstdlib>
 #include <vector>
 
 #include "ced_common.hpp"
@@ -89,14 +88,9 @@ AccelSpec accel_view(const void *accel, int n_grids, int res, bool with_cells);
 constexpr int kMaxGrids = 8;
 constexpr int kMaxFrames = 64;      // frames rendered by one call (ced_render_frames_test); one lane of the scheduling wave each
 constexpr int kSlotAlign = 256;     // a frame's ray slots start at a multiple of this: no workgroup straddles two frames
-#ifndef CED_MARCH_THREADS
-#define CED_MARCH_THREADS 128
-#endif
-constexpr int kMarchThreads = CED_MARCH_THREADS;
+constexpr int kRunAhead = 1;       // iterations the host enqueues beyond the last plan it has seen published
+constexpr int kMarchThreads = 128;
 constexpr int kCompositeThreads = 256;
-#ifndef CED_COMPOSITE_KU
-#define CED_COMPOSITE_KU 4
-#endif
 constexpr int kHostLatticeWord = 8;    // host_stats: words 0..2 publish {alive, done, seq}; the lattice table from word 8 on
 constexpr int kHostIterWord = 8 + 128; // sharded calls: {alive here, done, seq} of plan k at word kHostIterWord + 3k
 
@@ -413,10 +407,7 @@ __global__ __launch_bounds__(kCullThreads) void march_cull_kernel(MarchArgs A, I
 // march_accel.hpp).  CAND: the rays are those of the culling pass's list, any frame's in any order, kCandLanes of them
 // per wave (64; measured with 32 and 16 -- more, emptier waves in case a wave alone on its SIMD were bound by the latency
 // of its own instruction stream: 118 and 164 us against 91, the kernel is bound by instruction issue, not by that).
-#ifndef CED_CAND_LANES
-#define CED_CAND_LANES 64
-#endif
-constexpr int kCandLanes = CED_CAND_LANES;
+constexpr int kCandLanes = 64;
 template <bool SINGLE, bool CAND, bool FIRST>
 __global__ __launch_bounds__(kMarchThreads, (SINGLE && !CAND) ? 4 : 3) void march_frame_kernel(MarchArgs A, IterPlan *__restrict__ plan)
 {
@@ -596,7 +587,7 @@ __global__ __launch_bounds__(kCompositeThreads) void frame_composite_kernel(
                 float acc = 0.0f;
                 // Samples are consumed strictly in order (the per-ray sums are sequential by contract), but
                 // their loads are issued kU at a time so one memory round trip feeds kU samples.
-                constexpr int kU = CED_COMPOSITE_KU;
+                constexpr int kU = 4;
                 int64_t i = sb;
                 const int64_t end = sb + cnt;
                 for (; i + kU <= end; i += kU) {
@@ -1221,15 +1212,13 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
     if (frame_times)
         hipLaunchKernelGGL(frame_times_kernel, grd, blk, 0, stream, n_rays, (int)rays_per_frame, frame_times, W.ts_ray);
     const int nb = (res + kBrick - 1) / kBrick;
-    AccelSpec acc{ nullptr, nb, nullptr };
-    if (g_march_early_out) {
-        if (accel) {
-            acc = accel_view(accel, n_grids, res, true);             // the caller's: brick and cell fields
-        } else {                                                     // none brought: the cheap brick field, per call
-            int rc = build_brick_accel(binaries, n_grids, res, W.accel, W.accel + (size_t)n_grids * nb * nb * nb, stream);
-            if (rc) return rc;
-            acc = AccelSpec{ W.accel, nb, nullptr };
-        }
+    AccelSpec acc;
+    if (accel) {
+        acc = accel_view(accel, n_grids, res, true);                 // the caller's: brick and cell fields
+    } else {                                                         // none brought: the cheap brick field, per call
+        int rc = build_brick_accel(binaries, n_grids, res, W.accel, W.accel + (size_t)n_grids * nb * nb * nb, stream);
+        if (rc) return rc;
+        acc = AccelSpec{ W.accel, nb, nullptr };
     }
     volatile long long *pub = (volatile long long *)host_stats;
     std::vector<long long> seq_of((size_t)max_iters + 1);
@@ -1247,19 +1236,13 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
     if (rc) return rc;
 
     const float opc_thres = (float)(1.0 - (double)early_stop_eps);
-    static const int run_ahead_env = [] {
-        const char *e = getenv("CED_FRAME_RUN_AHEAD");
-        const int v = e ? atoi(e) : 1;
-        return v < 0 ? 0 : (v > 64 ? 64 : v);
-    }();
-    const int run_ahead = run_ahead_env;
     const long long seq_plan0 = seq;              // publication of plan[0]
     long long alive_bound = n_rays;               // rays alive in the iteration being enqueued: never more than this
     int it = 0;
     for (; it < max_iters; ++it) {
-        // run-ahead control: the plan of iteration it - run_ahead must have been published (it is published by the
-        // schedule launch of iteration it - run_ahead - 1, or by the initial one)
-        const int need = it - run_ahead;
+        // run-ahead control: the plan of iteration it - kRunAhead must have been published (it is published by the
+        // schedule launch of iteration it - kRunAhead - 1, or by the initial one)
+        const int need = it - kRunAhead;
         if (xch) {
             // Sharded frames: every process must enqueue the same number of iterations (each holds a collective), so
             // the loop ends on the plan of iteration `need` -- identical on all processes -- and on nothing later that
@@ -1487,24 +1470,17 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
     // smallest chunk of an iteration (any chunking gives the same result; fewer, larger iterations against samples
     // evaluated behind a ray's end): measured on the 800x800 frame / the 262 k-ray batch, 4 for the full pass (4.26 ->
     // 4.03 ms against chunks from 1) and 8 for the density-only sampling pass
-    static const int min_chunk_env = [] { const char *e = getenv("CED_IMAGE_MIN_CHUNK"); return e ? atoi(e) : 0; }();
-    const int min_chunk = min_chunk_env > 0 ? (min_chunk_env > 64 ? 64 : min_chunk_env) : (full ? 4 : 8);
+    const int min_chunk = full ? 4 : 8;
     hipLaunchKernelGGL(frame_init_kernel, dim3(1), dim3(64), 0, stream,
                        ScheduleArgs{ W.plans, -1, 1, (int)n_rays, min_chunk, big, (long long *)host_stats, seq }, (float *)nullptr,
                        (unsigned long long *)nullptr, 0);
     int rc = check_launch("render_image (prep)");
     if (rc) return rc;
-    static const int run_ahead_env = [] {
-        const char *e = getenv("CED_FRAME_RUN_AHEAD");
-        const int v = e ? atoi(e) : 1;
-        return v < 0 ? 0 : (v > 64 ? 64 : v);
-    }();
-    const int run_ahead = run_ahead_env;
     const long long seq_plan0 = seq;
     long long alive_bound = n_rays;
     int it = 0;
     for (; it < kImageMaxIters; ++it) {
-        const int need = it - run_ahead;
+        const int need = it - kRunAhead;
         if (need >= 0) {
             rc = wait_published(pub + 2, need == 0 ? seq_plan0 : seq_of[need - 1], stream, who);
             if (rc) return rc;

@@ -35,18 +35,9 @@ __device__ void ced_diag_tick(int phase);
 namespace ced {
 
 constexpr int kBrickShift = 3;                 // kBrick == 8
-#ifndef CED_FRAME_LOOK
-#define CED_FRAME_LOOK 4
-#endif
-constexpr int kFrameLook = CED_FRAME_LOOK;     // look-ahead of the frame renderer's exact walk (cells per batch)
-#ifndef CED_MIN_JUMP_CELLS
-#define CED_MIN_JUMP_CELLS 3.0f
-#endif
-#ifndef CED_COARSE_RADIUS
-#define CED_COARSE_RADIUS 6
-#endif
-constexpr float kMinJumpCells = CED_MIN_JUMP_CELLS;   // the closed-form re-entry costs about as much as walking this many cells
-constexpr int kCoarseRadius = CED_COARSE_RADIUS;      // the exact walk hands over to the sphere trace at this empty radius
+constexpr int kFrameLook = 4;                  // look-ahead of the frame renderer's exact walk (cells per batch)
+constexpr float kMinJumpCells = 3.0f;          // the closed-form re-entry costs about as much as walking this many cells
+constexpr int kCoarseRadius = 6;               // the exact walk hands over to the sphere trace at this empty radius
 static_assert((1 << kBrickShift) == kBrick, "brick size");
 
 // Emulates   k = 0; while (k < kcap && x < tau) { prev = x; x = x + d; ++k; }   (binary32, round to nearest even)

@@ -113,10 +113,7 @@ struct GridSpec {
 
 constexpr int kBrick = 8;      // cells per brick side
 
-#ifndef CED_KLOOK
-#define CED_KLOOK 8
-#endif
-constexpr int kLook = CED_KLOOK;   // DDA look-ahead (cells whose occupancy bytes are fetched together)
+constexpr int kLook = 8;           // DDA look-ahead (cells whose occupancy bytes are fetched together)
 
 #if defined(__HIPCC__)
 // Traverses one ray; calls emit(i, t_start, t_end) for sample i = 0.. in order.  Returns the

@@ -10,7 +10,6 @@
 // geometry closes on itself: lane (g, c) ends a layer holding outputs 16 nb + 4 g + r of sample c, and as B operand of
 // the next layer it must supply inputs 16 q + 4 g + s -- the same elements (nb = q, r = s).  Same MFMA order per
 // output as ced_linear => the same bits.  Widths <= 64, <= 6 layers; all layers' fragments live in LDS (<= 96 KB).
-#include <cstdlib>
 
 #include "ced_common.hpp"
 
@@ -525,9 +524,7 @@ extern "C" int ced_mlp_chain(int64_t n, int32_t n_layers, int32_t backward, cons
     int per_cu = (int)((160 * 1024) / (lds > 0 ? lds : 1));
     if (per_cu > 4) per_cu = 4;
     if (per_cu < 1) per_cu = 1;
-    static const int blocks_env = [] { const char *e = getenv("CED_MLP_MAX_BLOCKS"); return e ? atoi(e) : 0; }();
-    const int64_t cap = blocks_env > 0 ? blocks_env : 256 * per_cu;
-    if (blocks > cap) blocks = cap;
+    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
     hipLaunchKernelGGL(ced::mlp_chain_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, A);
     return ced::check_launch("mlp_chain");
 }

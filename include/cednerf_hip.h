@@ -75,20 +75,16 @@ typedef struct ced_field_desc {
 int ced_version(void);
 const char *ced_last_error_string(void);
 
-/* Diagnostic knobs (process-wide; results are identical for every setting -- launch properties that callers vary
- * per call, such as the workgroup count of a field launch, are descriptor fields instead).  "field_variant": launch geometry of the fused field kernel,
- * 0 = 4 column tiles x 512 threads, 1 = 2 x 512, 2 = 2 x 768, 3 = 2 x 1024 (default; the temporal-table kernels, which need
- * more registers, take 2 x 512), 4 = 1 x 1024;
- * "half_variant": the same for the half-precision kernels, 0 = automatic (default: f16x2 2 x 1024, f16 and the
- * time-embedding kernels 2 x 768, temporal tables 2 x 512), 1 = 2 x 512, 2 = 2 x 1024, 3 = 2 x 768;
+/* Process-wide options; results are identical for every setting (launch properties that callers vary per call, such
+ * as the workgroup count of a field launch, are descriptor fields instead).  Three keys; any other key returns -1:
  * "field_spread_tiles": 1 deals the sample tiles of a launch across all CUs in groups of four before any CU takes
  * more (shorter last round, lower frame latency); 2 (default) does the same inside each XCD, the eight XCDs taking eight
  * contiguous parts of the sample stream (one L2 per table line instead of up to eight); 0 = contiguous tiles per workgroup;
- * "field_stagger": start-up phase offset between the waves of a SIMD (0 = none, default);
- * "march_early_out": 1 (default) lets the frame renderer's marching cross empty space through the brick distance
- * field, 0 walks every cell;
  * "march_two_pass": the frame renderer's first iteration as a culling pass (the sphere trace alone, every ray) and a
- * marching pass over the rays it could not rule out: 1 / 0, -1 (default) = when there are several grid levels.
+ * marching pass over the rays it could not rule out: 1 / 0, -1 (default) = when there are several grid levels;
+ * "hash_grad_blocks": cap on the workgroups per level of the hash-table gradient (ced_hash_encode_backward[_temporal]),
+ * 0 (default) = no cap, one per 64 samples; a small cap lets the atomics run beside compute-bound kernels of another
+ * stream.
  * (Round 3's "march_sm" -- that pass on persistent waves with lane-level ray fetch -- was bit-exact and 3x slower; removed
  * in round 4, HISTORY 4.2 keeps the measurements.) */
 int ced_set_option(const char *key, int value);
@@ -478,7 +474,7 @@ int64_t ced_render_image_test_workspace_bytes(int64_t n_rays, int32_t n_grids, i
  * iteration's N_samples = clamp(N_rays // N_alive, min, 64) ON THE DEVICE, and the background / depth
  * normalisation at the end.  Same schedule and per-ray sample sets as the reference loop; unlike it
  * (utils.py:231: one device->host sync per iteration) the host never waits for an iteration: it enqueues up to
- * CED_FRAME_RUN_AHEAD (default 1) iterations beyond the last one whose plan it has seen published in `host_stats`.
+ * one iteration beyond the last one whose plan it has seen published in `host_stats`.
  * `alpha_thre` is not a parameter because the reference ignores it in this function.
  *   rays_o, rays_d [n_rays,3]; binaries [n_grids,res,res,res] bytes; aabbs [n_grids,6];
  *   accel: device, from ced_build_occupancy_accel for these binaries, or NULL (built inside the call);
@@ -534,7 +530,7 @@ int ced_render_frames_test(const ced_field_desc *field, int32_t n_frames, int64_
  * ENQUEUE on `stream` an in-place sum over the processes of counts[0 .. n_counts) (device memory, int64; e.g.
  * ncclAllReduce / torch.distributed.all_reduce on that stream) and return 0, or non-zero to abort the call.  It must
  * not block on the device.  Every process makes the same number of calls in the same order: the host loop ends on the
- * plan of a fixed earlier iteration (CED_FRAME_RUN_AHEAD behind), which is identical on all processes, never on
+ * plan of a fixed earlier iteration (one iteration behind), which is identical on all processes, never on
  * timing.  No kernel of this library waits for another process.
  *   global_rays_per_frame: N_rays of the whole image; local_rays: DEVICE int32 [n_frames] or NULL -- how many of the
  *   frame's `rays_per_frame` local slots hold real rays (shards are padded to a common size; padding is never alive);

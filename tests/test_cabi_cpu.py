@@ -100,6 +100,11 @@ def test_argument_errors_are_reported_not_thrown():
     assert L.ced_occupancy_accel_bytes(1, 4096) < 0
     assert L.ced_build_occupancy_accel(None, 1, 128, None, 0, None) == -1
     assert L.ced_set_option(b"field_max_blocks", 128) == -1          # a per-call descriptor field now, not process state
+    # retired A/B knobs: the library has one launch geometry per kernel and no variant to select
+    for key in (b"field_variant", b"half_variant", b"mixed_variant", b"field_stagger", b"hash_grad_form", b"march_early_out"):
+        assert L.ced_set_option(key, 0) == -1 and key in L.ced_last_error_string(), key
+    for key, default in ((b"field_spread_tiles", 2), (b"march_two_pass", -1), (b"hash_grad_blocks", 0)):
+        assert L.ced_set_option(key, default) == 0, key
 
 
 def test_closed_form_skip_matches_sequential_recurrence(oracle):

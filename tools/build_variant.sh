@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds a variant of the library with extra -D flags applied to the marching / frame sources only:
-#   tools/build_variant.sh NAME -DCED_FRAME_LOOK=8 ...   ->  build/variants/libcednerf_hip.NAME.so
+#   SRCS=frame tools/build_variant.sh diag -DCED_MARCH_DIAG   ->  build/variants/libcednerf_hip.diag.so
 # SRCS="field field_half" chooses which sources get the flags (default: frame accel march).
 # Select it at run time with CED_NERF_LIB=<path>.  (Experiments only; the shipped library is _lib.build().)
 set -e
