@@ -84,6 +84,7 @@ PROTOTYPES = {
     "ced_pack_field_weights": (C.c_int, [C.c_int, C.c_int] + [_vp] * 10),
     "ced_packed_weight_words": (_i64, [C.c_int, C.c_int, C.c_int]),
     "ced_pack_field_weights_half": (C.c_int, [C.c_int, C.c_int, C.c_int] + [_vp] * 10),
+    "ced_pack_field_weights_half_for": (C.c_int, [C.c_int] * 5 + [_vp] * 10),
     "ced_pack_field_weights_mixed": (C.c_int, [C.c_int, C.c_int] + [_vp] * 10),
     "ced_ray_aabb_intersect": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "ced_sort_intersections": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -182,10 +183,6 @@ def build(force: bool = False, verbose: bool = False, extra_flags: Optional[List
     srcs = [os.path.join(_PKG, "csrc", s) for s in SOURCES]
     hipcc = os.environ.get("HIPCC", "hipcc")
     flags = [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags or [])
-    if os.environ.get("CED_HALF_MFMA_K32", "0") == "1":
-        # opt-in: the half-precision MLP blocks on v_mfma_f32_16x16x32_f16 (+11 % in f16x2).  Only for processes in
-        # which no foreign kernel (torch, RCCL) can be co-resident with a field kernel: field_half_device.hpp, mfma_k32
-        flags.append("-DCED_HALF_MFMA_K32")
     obj_dir = os.path.join(_ROOT, "build", "obj")
     os.makedirs(obj_dir, exist_ok=True)
     stamp = os.path.join(obj_dir, "flags.txt")
@@ -212,6 +209,13 @@ def build(force: bool = False, verbose: bool = False, extra_flags: Optional[List
         with ThreadPoolExecutor(max_workers=workers) as pool:
             list(pool.map(run, jobs))
     run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs)
+    # residency gate: every kernel that issues v_mfma_f32_16x16x32_f16 must hold its SIMDs alone (_k32_gate.py)
+    from . import _k32_gate
+    _, bad = _k32_gate.check(LIB_PATH)
+    if bad:
+        os.remove(LIB_PATH)
+        raise RuntimeError("K = 32 residency gate failed (ced_nerf_amd/_k32_gate.py): "
+                           + "; ".join(f"{k}: {v}" for k, v in sorted(bad.items())))
     with open(stamp, "w") as f:
         f.write(flag_text)
     return LIB_PATH

@@ -44,6 +44,37 @@ __device__ __forceinline__ bool field_tile_range(int mode, int64_t n_tiles, int 
     return true;
 }
 
+// The same tiles as ONE sequence per workgroup, for kernels whose waves take their tiles from a workgroup counter
+// (field_half.hip, the K = 32 kernels): element i = t * waves + w is the t-th tile field_tile_range gives wave w,
+// tile (base + (i >> shift) * gstride) << shift | (i & ((1 << shift) - 1)), increasing in i; the sequence ends at the
+// first element >= end.  waves must be a power of two (mode 0).
+struct TileSeq { int64_t base, gstride, end; int shift; };
+__device__ __forceinline__ int64_t field_tile_at(const TileSeq &q, int i)
+{
+    return ((q.base + (int64_t)(i >> q.shift) * q.gstride) << q.shift) + (i & ((1 << q.shift) - 1));
+}
+__device__ __forceinline__ bool field_tile_seq(int mode, int64_t n_tiles, int waves, TileSeq &q)
+{
+    const int64_t grid = gridDim.x, b = blockIdx.x;
+    if (mode == 2 && (grid & 7) == 0) {
+        const int64_t n_groups = (n_tiles + 3) >> 2, per_xcd = grid >> 3, region = (n_groups + 7) >> 3;
+        const int64_t start = (b & 7) * region;
+        const int64_t g_end = start + region < n_groups ? start + region : n_groups;
+        if (start + (b >> 3) >= g_end) return false;
+        q.base = start + (b >> 3);
+        q.gstride = per_xcd;
+        q.end = 4 * g_end < n_tiles ? 4 * g_end : n_tiles;
+        q.shift = 2;
+        return true;
+    }
+    if ((mode ? b * 4 : b * waves) >= n_tiles) return false;
+    q.base = b;
+    q.gstride = grid;
+    q.end = n_tiles;
+    q.shift = mode ? 2 : __builtin_ctz((unsigned)waves);
+    return true;
+}
+
 // Per-level constants, pre-multiplied by the table's bytes per entry (a power of two), so the
 // corner arithmetic below produces byte offsets directly: the xor-hash commutes with the shift
 // ((a^b) << s == (a<<s) ^ (b<<s)) and the dense index is linear.

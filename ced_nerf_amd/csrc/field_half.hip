@@ -47,15 +47,31 @@ template <bool TE> struct HalfBlob {
     static constexpr int FRAGS = H2 + 1 * 2;       // 42 / 46
 };
 
+// Which kernels run their hidden layers on the single 16x16x32 instruction (field_half_device.hpp: mfma_k32): f16x2
+// without a time encoding on a plain (not temporal) table, the 1024-thread kernels of launch_field_half, whose four
+// waves per SIMD hold all of its registers (residency gate: ced_nerf_amd/_k32_gate.py).  The host side of the same
+// choice is half_layout_k32: those kernels need the weights packed with the K = 32 placements.
+constexpr bool half_kernel_k32(bool te, bool temporal, bool split, int threads)
+{
+    return split && !te && !temporal && threads == 1024;
+}
+static bool half_layout_k32(int time_mode, int precision, int temporal)
+{
+    return half_kernel_k32(time_mode != 0, temporal != 0, precision == CED_MLP_F16X2, 1024);
+}
+
 template <bool TE, bool F16, bool TEMPORAL, bool SPLIT, int NT, int THREADS>
 __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
 {
     constexpr int WAVES = THREADS / kWave;
+    constexpr bool K32 = half_kernel_k32(TE, TEMPORAL, SPLIT, THREADS);
+    static_assert(!K32 || (WAVES & (WAVES - 1)) == 0, "field_tile_seq needs a power-of-two wave count");
     constexpr int TILE = 16 * NT;
     using BL = HalfBlob<TE>;
     constexpr int PLANE = BL::FRAGS * kFragHalves;
     constexpr int WHALVES = PLANE * (SPLIT ? 2 : 1);
     __shared__ __attribute__((aligned(16))) _Float16 lds[WHALVES + 16 * CED_MAX_LEVELS];
+    __shared__ int next_elem;                 // K32: the workgroup's next unclaimed element of its tile sequence
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     // the wave's number as a SCALAR: everything derived from it (the wave's tiles, their sample ranges, the bases of the
@@ -73,9 +89,20 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
     // the by-value argument block would make the compiler keep the whole block in scratch.)
     const int64_t sbase = A.base_dev ? *A.base_dev : 0;
     const int64_t n_tiles = (n_eff + TILE - 1) / TILE;
-    // a workgroup without a tile leaves before staging anything (field_device.hpp: field_tile_range)
+    // a workgroup without a tile leaves before staging anything (field_device.hpp: field_tile_range); workgroup-uniform,
+    // before any MFMA.  K32: the waves' first tiles are the static ones, every further tile is claimed from next_elem --
+    // the waves then run out of tiles within one tile of each other and the barrier before the exit costs little.
     TileRange tiles;
-    if (!field_tile_range(A.spread_tiles, n_tiles, WAVES, wave, tiles)) return;
+    TileSeq seq;
+    if constexpr (K32) {
+        if (!field_tile_seq(A.spread_tiles, n_tiles, WAVES, seq)) return;
+        tiles.first = field_tile_at(seq, wave);
+        tiles.end = seq.end;
+        tiles.stride = 0;
+        if (tid == 0) next_elem = WAVES;
+    } else {
+        if (!field_tile_range(A.spread_tiles, n_tiles, WAVES, wave, tiles)) return;
+    }
     if (A.stamp && tid == 0) atomicMin(A.stamp, (unsigned long long)wall_clock64());
 
     {
@@ -93,7 +120,16 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
 
     const float extent[3] = { A.aabb[3] - A.aabb[0], A.aabb[4] - A.aabb[1], A.aabb[5] - A.aabb[2] };
 
-    for (int64_t tile = tiles.first; tile < tiles.end; tile += tiles.stride) {
+    auto next_tile = [&](int64_t tile) -> int64_t {
+        if constexpr (K32) {
+            int i = 0;
+            if (lane == 0) i = atomicAdd(&next_elem, 1);
+            return field_tile_at(seq, __builtin_amdgcn_readfirstlane(i));
+        } else {
+            return tile + tiles.stride;
+        }
+    };
+    for (int64_t tile = tiles.first; tile < tiles.end; tile = next_tile(tile)) {
         // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field.hip)
         int lds_off = 0;
         asm volatile("" : "+v"(lds_off));
@@ -150,11 +186,11 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
         // --- motion MLP 32-64-64-64-(3|6) ---
         mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bh, Bl, D);
         to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        mlp_layer_h<2, 4, NT, SPLIT>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bh, Bl, D);
+        mlp_layer_h<2, 4, NT, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bh, Bl, D);
         to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        mlp_layer_h<2, 4, NT, SPLIT>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bh, Bl, D);
+        mlp_layer_h<2, 4, NT, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bh, Bl, D);
         to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        mlp_layer_h<2, 1, NT, SPLIT>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
+        mlp_layer_h<2, 1, NT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
 
         // --- query_move / normalise / selector (model.py:354-383); motion rows are natural ---
         float xn[NT][3], mnorm[NT];
@@ -236,7 +272,7 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
         // --- mlp_base (32|41)-64-16 ---
         mlp_layer_h<BL::KS_B0, 4, NT, SPLIT>(whi + BL::B0 * kFragHalves, wlo + BL::B0 * kFragHalves, lane, Bh, Bl, D);
         to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        mlp_layer_h<2, 1, NT, SPLIT>(whi + BL::B1 * kFragHalves, wlo + BL::B1 * kFragHalves, lane, Bh, Bl, D);
+        mlp_layer_h<2, 1, NT, SPLIT, K32>(whi + BL::B1 * kFragHalves, wlo + BL::B1 * kFragHalves, lane, Bh, Bl, D);
 
         // accumulator row 4g + r: geometry feature 4g + r; row 15 (g = 3, r = 3): raw density
 #pragma unroll
@@ -278,9 +314,9 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
             }
             mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::H0 * kFragHalves, wlo + BL::H0 * kFragHalves, lane, Bh, Bl, D);
             to_operand_h<NT, SPLIT>(D, Bh, Bl);
-            mlp_layer_h<2, 4, NT, SPLIT>(whi + BL::H1 * kFragHalves, wlo + BL::H1 * kFragHalves, lane, Bh, Bl, D);
+            mlp_layer_h<2, 4, NT, SPLIT, K32>(whi + BL::H1 * kFragHalves, wlo + BL::H1 * kFragHalves, lane, Bh, Bl, D);
             to_operand_h<NT, SPLIT>(D, Bh, Bl);
-            mlp_layer_h<2, 1, NT, SPLIT>(whi + BL::H2 * kFragHalves, wlo + BL::H2 * kFragHalves, lane, Bh, Bl, D);
+            mlp_layer_h<2, 1, NT, SPLIT, K32>(whi + BL::H2 * kFragHalves, wlo + BL::H2 * kFragHalves, lane, Bh, Bl, D);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int64_t s = tile_base + (16 * j + c);
@@ -290,8 +326,16 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
             }
         }
     }
-    // tracing only: every wave stamps its own end (waves of a workgroup finish up to a tile apart; a barrier here
-    // would hold the early ones' registers and cost 3 % of throughput)
+    // K32: no wave frees its registers while a sibling can still issue a 16x16x32 MFMA (field_half_device.hpp: mfma_k32).
+    // Other kernels: no barrier -- under the static mapping waves finish up to a tile apart, and holding the early ones'
+    // registers cost 3 % of throughput.
+    if constexpr (K32) {
+        __syncthreads();
+        // the allocation's floor: 128 registers per wave, all of them (the residency argument at mfma_k32 needs it exact;
+        // here, after the last MFMA, the clobber costs the allocator nothing)
+        asm volatile("" ::: "v127");
+    }
+    // tracing only: every wave stamps its own end
     if (A.stamp && lane == 0) atomicMax(A.stamp + 1, (unsigned long long)wall_clock64());
 }
 
@@ -304,6 +348,7 @@ void pack_half_layer(const float *w, int n_out, int n_in, int nb, int ks, int fr
     for (int p = 0; p < nb * 16; ++p) {
         int neuron = p;
         if (row_map == HALF_ROW_HIDDEN) neuron = half_hidden_neuron(p);
+        else if (row_map == HALF_ROW_HIDDEN_K32) neuron = half_hidden_neuron_k32(p);
         else if (row_map == HALF_ROW_BASE_OUT) neuron = half_base_out_neuron(p);
         else if (row_map == HALF_ROW_RGB) neuron = (p % 4 == 0) ? p / 4 : n_out;
         if (neuron >= n_out) continue;
@@ -313,6 +358,8 @@ void pack_half_layer(const float *w, int n_out, int n_in, int nb, int ks, int fr
             if (col_map == HALF_COL_HASH) {
                 if (k < 32) in = 2 * (4 * (e >> 1) + g) + (e & 1);          // level 4i + g, feature f at e = 2i + f
                 else in = (e < 3 && 4 * e + g <= 8) ? 32 + 4 * e + g : -1;   // time feature 4e + g
+            } else if (col_map == HALF_COL_K32) {
+                in = half_hidden_neuron_k32(16 * (2 * (k / 32) + (e >> 2)) + 4 * g + (e & 3));
             } else if (col_map == HALF_COL_HEAD) {
                 if (e == 0) in = g;                                          // SH component g
                 else if (e <= 4 && 4 * g + e - 1 < 15) in = 4 + 4 * g + e - 1;   // geometry feature 4g + e - 1
@@ -372,11 +419,13 @@ extern "C" int64_t ced_packed_weight_words(int use_div_offsets, int time_mode, i
 
 // Host-side reorder into 16x16x32 A-fragment order: element (accumulator row p, operand position k) of a
 // layer goes to fragment [nb = p/16][ks = k/32], lane 16*((k%32)/8) + p%16, half k%8.  Which neuron row p
-// computes and which input sits at position k are the layer's placements (header comment of this file).
-extern "C" int ced_pack_field_weights_half(int use_div_offsets, int time_mode, int mlp_precision, const float *m_w0,
-                                           const float *m_w1, const float *m_w2, const float *m_w3, const float *b_w0,
-                                           const float *b_w1, const float *h_w0, const float *h_w1, const float *h_w2,
-                                           void *out)
+// computes and which input sits at position k are the layer's placements (header comment of this file).  k32: the
+// placements of the K = 32 kernels (half_kernel_k32): the hidden layers feeding a 16x16x32 layer are packed with
+// half_hidden_neuron_k32 and those layers read their inputs from there; the output rows other code reads (motion
+// offsets, mlp_base outputs, colour) and the three input layers' columns stay as they are.  Same size either way.
+static int pack_half(int use_div_offsets, int time_mode, int mlp_precision, bool k32, const float *m_w0, const float *m_w1,
+                     const float *m_w2, const float *m_w3, const float *b_w0, const float *b_w1, const float *h_w0,
+                     const float *h_w1, const float *h_w2, void *out)
 {
     CED_REQUIRE(m_w0 && m_w1 && m_w2 && m_w3 && b_w0 && b_w1 && h_w0 && h_w1 && h_w2 && out,
                 "pack_field_weights_half: null pointer");
@@ -401,13 +450,37 @@ extern "C" int ced_pack_field_weights_half(int use_div_offsets, int time_mode, i
         const int o[9] = { B::M0, B::M1, B::M2, B::M3, B::B0, B::B1, B::H0, B::H1, B::H2 };
         for (int i = 0; i < 9; ++i) fr[i] = o[i];
     }
+    const int HR = k32 ? HALF_ROW_HIDDEN_K32 : HALF_ROW_HIDDEN, HC = k32 ? HALF_COL_K32 : HALF_COL_NATURAL;
     const L layers[9] = {
-        { m_w0, 64, 32, 4, 1, fr[0], HALF_ROW_HIDDEN, HALF_COL_NATURAL },   { m_w1, 64, 64, 4, 2, fr[1], HALF_ROW_HIDDEN, HALF_COL_NATURAL },
-        { m_w2, 64, 64, 4, 2, fr[2], HALF_ROW_HIDDEN, HALF_COL_NATURAL },   { m_w3, n_mo, 64, 1, 2, fr[3], HALF_ROW_NATURAL, HALF_COL_NATURAL },
-        { b_w0, 64, base_in, 4, ksb0, fr[4], HALF_ROW_HIDDEN, HALF_COL_HASH }, { b_w1, 16, 64, 1, 2, fr[5], HALF_ROW_BASE_OUT, HALF_COL_NATURAL },
-        { h_w0, 64, 19, 4, 1, fr[6], HALF_ROW_HIDDEN, HALF_COL_HEAD },      { h_w1, 64, 64, 4, 2, fr[7], HALF_ROW_HIDDEN, HALF_COL_NATURAL },
-        { h_w2, 3, 64, 1, 2, fr[8], HALF_ROW_RGB, HALF_COL_NATURAL },
+        { m_w0, 64, 32, 4, 1, fr[0], HR, HALF_COL_NATURAL },         { m_w1, 64, 64, 4, 2, fr[1], HR, HC },
+        { m_w2, 64, 64, 4, 2, fr[2], HR, HC },                       { m_w3, n_mo, 64, 1, 2, fr[3], HALF_ROW_NATURAL, HC },
+        { b_w0, 64, base_in, 4, ksb0, fr[4], HR, HALF_COL_HASH },    { b_w1, 16, 64, 1, 2, fr[5], HALF_ROW_BASE_OUT, HC },
+        { h_w0, 64, 19, 4, 1, fr[6], HR, HALF_COL_HEAD },            { h_w1, 64, 64, 4, 2, fr[7], HR, HC },
+        { h_w2, 3, 64, 1, 2, fr[8], HALF_ROW_RGB, HC },
     };
     for (const L &l : layers) pack_half_layer(l.w, l.n_out, l.n_in, l.nb, l.ks, l.frag, l.row, l.col, hi, split ? lo : nullptr);
     return CED_OK;
+}
+
+// The pair-form placements, whatever kernel the blob is for (the layout of rounds 1-4; the tests pin it).
+extern "C" int ced_pack_field_weights_half(int use_div_offsets, int time_mode, int mlp_precision, const float *m_w0,
+                                           const float *m_w1, const float *m_w2, const float *m_w3, const float *b_w0,
+                                           const float *b_w1, const float *h_w0, const float *h_w1, const float *h_w2,
+                                           void *out)
+{
+    return pack_half(use_div_offsets, time_mode, mlp_precision, false, m_w0, m_w1, m_w2, m_w3, b_w0, b_w1, h_w0, h_w1,
+                     h_w2, out);
+}
+
+// The placements the kernel launched for this configuration needs (half_layout_k32): what a field descriptor with
+// these time_mode / mlp_precision / hash table must carry.
+extern "C" int ced_pack_field_weights_half_for(int use_div_offsets, int time_mode, int mlp_precision, int table_dtype,
+                                               int temporal, const float *m_w0, const float *m_w1, const float *m_w2,
+                                               const float *m_w3, const float *b_w0, const float *b_w1, const float *h_w0,
+                                               const float *h_w1, const float *h_w2, void *out)
+{
+    CED_REQUIRE(table_dtype == 0 || table_dtype == 1, "pack_field_weights_half_for: table_dtype=%d (0 = fp32, 1 = fp16)",
+                table_dtype);
+    return pack_half(use_div_offsets, time_mode, mlp_precision, ced::half_layout_k32(time_mode, mlp_precision, temporal),
+                     m_w0, m_w1, m_w2, m_w3, b_w0, b_w1, h_w0, h_w1, h_w2, out);
 }

@@ -181,7 +181,9 @@ class DNGPradianceField(torch.nn.Module):
                                       [w.detach().cpu().numpy() for w in self.xyz_wrap],
                                       [w.detach().cpu().numpy() for w in self.mlp_base],
                                       [w.detach().cpu().numpy() for w in self.mlp_head],
-                                      _lib.MLP_PRECISIONS[self.mlp_precision])
+                                      _lib.MLP_PRECISIONS[self.mlp_precision],
+                                      table_dtype=0 if self.hash_table.dtype == torch.float32 else 1,
+                                      temporal=self.hash_cfg["temporal"])
         self._packed = torch.from_numpy(blob).to(dev)
         hd, _ = ops.make_hash_desc(self.hash_table.data, **self.hash_cfg)
         d = _lib.FieldDesc()

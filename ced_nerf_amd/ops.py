@@ -82,9 +82,11 @@ def make_hash_desc(table: torch.Tensor, base_res: int, max_res: int, n_levels: i
 
 
 def pack_field_weights(use_div_offsets: bool, time_mode: int, xyz_wrap, mlp_base, mlp_head,
-                       mlp_precision: int = _lib.MLP_F32) -> np.ndarray:
+                       mlp_precision: int = _lib.MLP_F32, table_dtype: int = 0, temporal: bool = False) -> np.ndarray:
     """Host: natural W[out][in] float32 arrays -> MFMA-fragment-order blob (ced_pack_field_weights for the
-    fp32 kernel, ced_pack_field_weights_half for the f16x2 / f16 kernels; the latter returns uint32 words)."""
+    fp32 kernel, ced_pack_field_weights_half_for for the f16x2 / f16 kernels; the latter returns uint32 words).
+    table_dtype (0 = float32, 1 = float16 entries) and temporal describe the hash table the blob is used with: the
+    half-precision kernels differ in their weight placements by table as well as by mode."""
     L = _lib.lib()
     mats = [np.ascontiguousarray(np.asarray(w, np.float32)) for w in list(xyz_wrap) + list(mlp_base) + list(mlp_head)]
     base_in = 41 if time_mode else 32
@@ -105,9 +107,10 @@ def pack_field_weights(use_div_offsets: bool, time_mode: int, xyz_wrap, mlp_base
         if n <= 0:
             raise ValueError(f"mlp_precision={mlp_precision}")
         out = np.zeros((n,), np.uint32)
-        rc = L.ced_pack_field_weights_half(int(use_div_offsets), int(time_mode), int(mlp_precision),
-                                           *[m.ctypes.data_as(C.c_void_p) for m in mats], out.ctypes.data_as(C.c_void_p))
-        _lib.check(rc, "pack_field_weights_half")
+        rc = L.ced_pack_field_weights_half_for(int(use_div_offsets), int(time_mode), int(mlp_precision), int(table_dtype),
+                                               int(bool(temporal)), *[m.ctypes.data_as(C.c_void_p) for m in mats],
+                                               out.ctypes.data_as(C.c_void_p))
+        _lib.check(rc, "pack_field_weights_half_for")
         return out
     n = int(L.ced_packed_weight_floats(int(use_div_offsets), int(time_mode)))
     out = np.zeros((n,), np.float32)

@@ -128,6 +128,14 @@ int ced_pack_field_weights_half(int use_div_offsets, int time_mode, int mlp_prec
                                 const float *b_w0, const float *b_w1,
                                 const float *h_w0, const float *h_w1, const float *h_w2,
                                 void *out);
+/* The blob the field kernel for this configuration reads (table_dtype / temporal as in ced_hash_desc): the f16x2 kernels
+ * without a time encoding on a plain table run their hidden layers on v_mfma_f32_16x16x32_f16 and need other row / column
+ * placements than ced_pack_field_weights_half's; every other configuration gets the same blob as there.  Same size. */
+int ced_pack_field_weights_half_for(int use_div_offsets, int time_mode, int mlp_precision, int table_dtype, int temporal,
+                                    const float *m_w0, const float *m_w1, const float *m_w2, const float *m_w3,
+                                    const float *b_w0, const float *b_w1,
+                                    const float *h_w0, const float *h_w1, const float *h_w2,
+                                    void *out);
 /* HOST packer for CED_MLP_F32_HEAD16X2: `out` holds ced_packed_weight_floats() floats (the head's region carries fp16
  * fragments). */
 int ced_pack_field_weights_mixed(int use_div_offsets, int time_mode,

@@ -3,10 +3,12 @@
 of src1 for the low result lane (v_pk_mul_f32 / v_pk_add_f32 ... op_sel:[x,1], v_pk_fma_f32 ... op_sel:[x,1,x]).
 
 On gfx950 that form reads the swizzled operand as zero while another wave of the same SIMD executes
-v_mfma_f32_16x16x32_f16 (tools/probes/pk_opsel_mfma.hip) -- and the half-precision field kernels run that
-MFMA three waves to a SIMD, beside the other kernels of frames in flight.  hipcc's SLP vectoriser is what emits the form,
-hence -fno-slp-vectorize in ced_nerf_amd/_lib.py; this lint is the check that an edit or a flag change has not brought
-it back.  Usage: tools/isa_lint.py [library.so]   (exit status 1 and a list of kernels when the form is present)
+v_mfma_f32_16x16x32_f16 (tools/probes/pk_opsel_mfma.hip) -- and the f16x2 field kernels without a time
+encoding run that MFMA.  hipcc's SLP vectoriser is what emits the form, hence -fno-slp-vectorize in ced_nerf_amd/_lib.py;
+this lint is the check that an edit or a flag change has not brought it back.  Second check: a K-doubled fp16 MFMA
+(16x16x32 / 32x32x16) appears only in kernels that pass the residency gate of ced_nerf_amd/_k32_gate.py (their waves
+hold all registers of their SIMDs, so no foreign wave can run beside them).
+Usage: tools/isa_lint.py [library.so]   (exit status 1 and a list of kernels when either check fails)
 """
 import os
 import re
@@ -53,6 +55,15 @@ def scan(path):
     return n_kernels, bad
 
 
+def k32_scan(path):
+    """-> ({kernel: K-doubled fp16 MFMAs}, {kernel: why it fails the residency gate})"""
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    from ced_nerf_amd import _k32_gate
+    return _k32_gate.check(path)
+
+
 def main():
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(here, "ced_nerf_amd", "libcednerf_hip.so")
@@ -60,7 +71,11 @@ def main():
     print(f"{path}: {n} kernels scanned, {len(bad)} with a src1-high op_sel packed-fp32 instruction or a fused fp16-result fma")
     for k, lines in bad.items():
         print(f"  {k}: {len(lines)}   e.g. {lines[0]}")
-    return 1 if bad else 0
+    k32, ungated = k32_scan(path)
+    print(f"{len(k32)} kernels with v_mfma_f32_16x16x32_f16 / 32x32x16_f16, {len(ungated)} of them without exclusive residency")
+    for k, n_k32 in sorted(k32.items()):
+        print(f"  {k}: {n_k32}" + (f"   FAILS: {ungated[k]}" if k in ungated else ""))
+    return 1 if bad or ungated else 0
 
 
 if __name__ == "__main__":
