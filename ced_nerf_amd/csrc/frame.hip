@@ -132,6 +132,72 @@ __device__ __forceinline__ int frame_of_slot(const IterPlan &P, int n_frames, in
     return (P.count[lo] > 0 && s0 >= P.slot_base[lo] && s0 < (int64_t)P.slot_base[lo] + P.count[lo]) ? lo : -1;
 }
 
+// Workgroup range reservation: every lane asks for n slots (wave-inclusive prefix sums, an exclusive scan of the wave
+// totals in LDS); thread 0 hands the workgroup's total, when there is one, to reserve(total), which makes the site's
+// single atomic and returns the range's first slot.  Returns the lane's first slot.  Two barriers: a persistent loop
+// that calls this again puts a third one behind its last use of the result.
+template <int kWaves, class Reserve>
+__device__ __forceinline__ int64_t workgroup_reserve(int n, Reserve reserve)
+{
+    __shared__ int wave_tot[kWaves];
+    __shared__ long long block_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int v = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += v;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int w = 0; w < kWaves; ++w) { const int t = wave_tot[w]; wave_tot[w] = run; run += t; }
+        block_base = run > 0 ? reserve(run) : 0;
+    }
+    __syncthreads();
+    return (int64_t)block_base + wave_tot[wave] + (incl - n);
+}
+
+// Ballot append: every lane that takes one slot gets its own, in lane order (ballot and popcount per wave, an exclusive
+// scan of the wave counts in LDS).  kSums per-lane values sums[k] are summed over the workgroup on the way; thread 0
+// calls reserve(count, totals) with the workgroup's slot count and those totals, which makes the site's atomics and
+// returns the first slot.  Returns the lane's slot (meaningful where take).  Barriers as workgroup_reserve.
+template <int kWaves, int kSums, class Reserve>
+__device__ __forceinline__ int workgroup_append(bool take, const int *sums, Reserve reserve)
+{
+    __shared__ int wave_cnt[kWaves], wave_sum[kSums > 0 ? kSums : 1][kWaves];
+    __shared__ int block_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long ballot = __ballot(take);
+    int tot[kSums > 0 ? kSums : 1];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) tot[k] = sums[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) tot[k] += __shfl_xor(tot[k], off, 64);
+    if (lane == 0) {
+        wave_cnt[wave] = __builtin_popcountll(ballot);
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) wave_sum[k][wave] = tot[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) tot[k] = 0;
+        for (int w = 0; w < kWaves; ++w) {
+            const int t = wave_cnt[w]; wave_cnt[w] = run; run += t;
+#pragma unroll
+            for (int k = 0; k < kSums; ++k) tot[k] += wave_sum[k][w];
+        }
+        block_base = reserve(run, tot);
+    }
+    __syncthreads();
+    return block_base + wave_cnt[wave] + __builtin_popcountll(ballot & ((1ull << lane) - 1ull));
+}
+
 __global__ __launch_bounds__(256) void frame_times_kernel(int64_t n_rays, int rays_per_frame,
                                                           const float *__restrict__ frame_times, float *__restrict__ ts_ray)
 {
@@ -321,6 +387,46 @@ struct MarchArgs {
 
 constexpr int kMaxRuns = 4;        // runs of consecutive samples a ray's walk is remembered by (more: the ray walks twice)
 
+// A ray's walk remembered as (first t, length) of up to kMaxRuns runs of consecutive samples, in registers: within a
+// run t_start[j+1] == t_end[j] and t_end[j] = t_start[j] + dt(t_start[j]), so replay() regenerates the same floats.
+struct SampleRuns {
+    float t[kMaxRuns] = {};
+    int n[kMaxRuns] = {};
+    int count = 0;
+    float prev_end = 0.0f;
+
+    __device__ __forceinline__ void record(int i, float t0, float t1)
+    {
+        const bool fresh = i == 0 || t0 != prev_end;
+        if (fresh) ++count;
+        prev_end = t1;
+        // run slots as a chain of selects (t / n stay in registers)
+#pragma unroll
+        for (int k = 0; k < kMaxRuns; ++k) {
+            const bool here = count == k + 1;
+            t[k] = (here && fresh) ? t0 : t[k];
+            n[k] += here ? 1 : 0;
+        }
+    }
+    // false: more runs than fit (alternating single occupied cells) or a walk without a step size -- walk again instead
+    __device__ __forceinline__ bool replayable(const GridSpec &grid) const { return count <= kMaxRuns && grid.step_size > 0.0f; }
+    // store(i, t0, t1) for every sample, in the walk's order
+    template <class Store>
+    __device__ __forceinline__ void replay(const GridSpec &grid, Store store) const
+    {
+        int pos = 0;
+#pragma unroll
+        for (int k = 0; k < kMaxRuns; ++k) {
+            float ts = t[k];
+            for (int j = 0; j < n[k]; ++j) {
+                const float te = ts + calc_dt(ts, grid.cone_angle, grid.step_size, 1e10f);
+                store(pos++, ts, te);
+                ts = te;
+            }
+        }
+    }
+};
+
 // One lane per alive ray.  The walk does not store its samples: within a run of consecutive samples t_start[j+1] ==
 // t_end[j] and t_end[j] = t_start[j] + dt(t_start[j]), so a ray remembers (first t, length) of up to kMaxRuns runs in
 // registers.  Then the workgroup reserves ONE contiguous range of the iteration's sample array (wave prefix sums +
@@ -338,12 +444,8 @@ static_assert(kSlotAlign % kCullThreads == 0, "a culling workgroup's slots belon
 template <bool SINGLE>
 __global__ __launch_bounds__(kCullThreads) void march_cull_kernel(MarchArgs A, IterPlan *__restrict__ plan)
 {
-    constexpr int kWaves = kCullThreads / 64;
-    __shared__ int wave_cnt[kWaves];
-    __shared__ int block_base;
     const IterPlan &P = *plan;
     const int64_t total = P.total_slots;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = SINGLE ? 1 : A.grid.n_grids, res = A.grid.res;
     for (int64_t s0 = (int64_t)blockIdx.x * kCullThreads; s0 < total; s0 += (int64_t)gridDim.x * kCullThreads) {
         // kSlotAlign == kCullThreads: a workgroup's slots belong to one frame
@@ -389,16 +491,9 @@ __global__ __launch_bounds__(kCullThreads) void march_cull_kernel(MarchArgs A, I
             }
             if (!cand) { A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0; }
         }
-        const unsigned long long ballot = __ballot(cand);
-        if (lane == 0) wave_cnt[wave] = __builtin_popcountll(ballot);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0;
-            for (int w = 0; w < kWaves; ++w) { const int t = wave_cnt[w]; wave_cnt[w] = run; run += t; }
-            block_base = run > 0 ? atomicAdd(&plan->n_cand, run) : 0;
-        }
-        __syncthreads();
-        if (cand) A.cand[block_base + wave_cnt[wave] + __builtin_popcountll(ballot & ((1ull << lane) - 1ull))] = (int32_t)r;
+        const int slot = workgroup_append<kCullThreads / 64, 0>(
+            cand, nullptr, [&](int run, const int *) { return run > 0 ? atomicAdd(&plan->n_cand, run) : 0; });
+        if (cand) A.cand[slot] = (int32_t)r;
         __syncthreads();
     }
 }
@@ -414,8 +509,6 @@ __global__ __launch_bounds__(kMarchThreads, (SINGLE && !CAND) ? 4 : 3) void marc
     static_assert(!CAND || FIRST, "the candidate list belongs to the first iteration");
     constexpr int kWaves = kMarchThreads / 64;
     constexpr int kPerGroup = CAND ? kWaves * kCandLanes : kMarchThreads;        // rays of one workgroup pass
-    __shared__ int wave_tot[kWaves];
-    __shared__ long long block_base;
     const IterPlan &P = *plan;
     const int64_t total = CAND ? (int64_t)P.n_cand : (int64_t)P.total_slots;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -441,78 +534,37 @@ __global__ __launch_bounds__(kMarchThreads, (SINGLE && !CAND) ? 4 : 3) void marc
         const int m = grid.n_grids;
         float o[3] = { 0.0f, 0.0f, 0.0f }, d[3] = { 0.0f, 0.0f, 1.0f };
         float near = 0.0f, t_term = 0.0f;
-        float run_t[kMaxRuns];
-        int run_n[kMaxRuns];
-#pragma unroll
-        for (int k = 0; k < kMaxRuns; ++k) { run_t[k] = 0.0f; run_n[k] = 0; }
-        int n = 0, n_runs = 0;
+        const auto walk = [&](auto &&emit, float &t_out) {
+            return traverse_ray_frame<kFrameLook, SINGLE, FIRST>(
+                grid, A.accel, FIRST, o, d, near, A.far_plane,
+                SINGLE ? nullptr : A.t_sorted + r * 2 * m, SINGLE ? (const uint8_t *)nullptr : A.t_indices + r * 2 * m,
+                SINGLE ? nullptr : A.hits + r * m, emit, t_out);
+        };
+        SampleRuns runs;
+        int n = 0;
         CED_DIAG_TICK(0);
         if (active) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) { o[a] = A.rays_o[3 * r + a]; d[a] = A.rays_d[3 * r + a]; }
             near = A.near_planes[r];
-            float prev_end = 0.0f;
-            n = traverse_ray_frame<kFrameLook, SINGLE, FIRST>(
-                grid, A.accel, FIRST, o, d, near, A.far_plane,
-                SINGLE ? nullptr : A.t_sorted + r * 2 * m, SINGLE ? (const uint8_t *)nullptr : A.t_indices + r * 2 * m,
-                SINGLE ? nullptr : A.hits + r * m,
-                [&](int i, float t0, float t1) {
-                    const bool fresh = i == 0 || t0 != prev_end;
-                    if (fresh) ++n_runs;
-                    prev_end = t1;
-                    // run slots as a chain of selects (run_t / run_n stay in registers)
-#pragma unroll
-                    for (int k = 0; k < kMaxRuns; ++k) {
-                        const bool here = n_runs == k + 1;
-                        run_t[k] = (here && fresh) ? t0 : run_t[k];
-                        run_n[k] += here ? 1 : 0;
-                    }
-                },
-                t_term);
+            n = walk([&](int i, float t0, float t1) { runs.record(i, t0, t1); }, t_term);
             A.near_planes[r] = t_term;
         }
-        // wave-inclusive prefix sum of the counts, one reservation per workgroup
         CED_DIAG_TICK(6);
-        int incl = n;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0;
-            for (int w = 0; w < kWaves; ++w) { const int t = wave_tot[w]; wave_tot[w] = run; run += t; }
-            block_base = run > 0 ? (long long)atomicAdd(reinterpret_cast<unsigned long long *>(&plan->total_samples),
-                                                        (unsigned long long)run) : 0;
-        }
-        __syncthreads();
-        const int64_t start = (int64_t)block_base + wave_tot[wave] + (incl - n);
+        const int64_t start = workgroup_reserve<kWaves>(n, [&](int run) {
+            return (long long)atomicAdd(reinterpret_cast<unsigned long long *>(&plan->total_samples), (unsigned long long)run);
+        });
         if (active) {
             A.packed[2 * r] = (int32_t)start;
             A.packed[2 * r + 1] = n;
             float *const p0 = A.t_starts + start, *const p1 = A.t_ends + start;
             int32_t *const pr = A.ray_idx + start;
-            if (n > 0 && (n_runs > kMaxRuns || !(grid.step_size > 0.0f))) {
+            const auto store = [&](int i, float t0, float t1) { p0[i] = t0; p1[i] = t1; pr[i] = (int32_t)r; };
+            if (n > 0 && !runs.replayable(grid)) {
                 float unused;                               // the walk again, storing at the final position
-                (void)traverse_ray_frame<kFrameLook, SINGLE, FIRST>(
-                    grid, A.accel, FIRST, o, d, near, A.far_plane,
-                    SINGLE ? nullptr : A.t_sorted + r * 2 * m, SINGLE ? (const uint8_t *)nullptr : A.t_indices + r * 2 * m,
-                    SINGLE ? nullptr : A.hits + r * m,
-                    [&](int i, float t0, float t1) { p0[i] = t0; p1[i] = t1; pr[i] = (int32_t)r; }, unused);
+                (void)walk(store, unused);
             } else {
-                int pos = 0;
-#pragma unroll
-                for (int k = 0; k < kMaxRuns; ++k) {
-                    float t = run_t[k];
-                    for (int j = 0; j < run_n[k]; ++j) {
-                        const float t1 = t + calc_dt(t, grid.cone_angle, grid.step_size, 1e10f);
-                        p0[pos] = t; p1[pos] = t1; pr[pos] = (int32_t)r;
-                        ++pos;
-                        t = t1;
-                    }
-                }
+                runs.replay(grid, store);
             }
         }
         CED_DIAG_TICK(7);
@@ -562,9 +614,6 @@ __global__ __launch_bounds__(kCompositeThreads) void frame_composite_kernel(
     const float *__restrict__ t1, const float *__restrict__ sig, const float *__restrict__ rgbs, float *__restrict__ rgb,
     float *__restrict__ opacity, float *__restrict__ depth, float opc_thres)
 {
-    constexpr int kWaves = kCompositeThreads / 64;
-    __shared__ int wave_alive[kWaves], wave_samples[kWaves];
-    __shared__ long long block_base;
     const IterPlan &P = *plan;
     const int64_t total = P.total_slots;
     for (int64_t s0 = (int64_t)blockIdx.x * kCompositeThreads; s0 < total; s0 += (int64_t)gridDim.x * kCompositeThreads) {
@@ -630,25 +679,12 @@ __global__ __launch_bounds__(kCompositeThreads) void frame_composite_kernel(
             }
             alive = !P.last[f] && (op <= opc_thres) && (cnt == limit);
         }
-        const unsigned long long ballot = __ballot(alive);
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        int wsum = cnt;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) wsum += __shfl_xor(wsum, off, 64);
-        if (lane == 0) { wave_alive[wave] = __builtin_popcountll(ballot); wave_samples[wave] = wsum; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0, samples = 0;
-            for (int w = 0; w < kWaves; ++w) { int t = wave_alive[w]; wave_alive[w] = run; run += t; samples += wave_samples[w]; }
-            const unsigned long long add = (unsigned long long)run + ((unsigned long long)samples << 32);
-            block_base = add != 0 ? (long long)(atomicAdd(&plan->next[f], add) & 0xffffffffull) : 0;
-        }
-        __syncthreads();
-        if (alive) {
-            const int rank = __builtin_popcountll(ballot & ((1ull << lane) - 1ull));
-            next_list[first + block_base + wave_alive[wave] + rank] = (int32_t)r;
-        }
-        __syncthreads();                                     // wave_alive / block_base are reused by the next chunk
+        const int slot = workgroup_append<kCompositeThreads / 64, 1>(alive, &cnt, [&](int run, const int *samples) {
+            const unsigned long long add = (unsigned long long)run + ((unsigned long long)samples[0] << 32);
+            return add != 0 ? (int)(atomicAdd(&plan->next[f], add) & 0xffffffffull) : 0;
+        });
+        if (alive) next_list[first + slot] = (int32_t)r;
+        __syncthreads();                                     // the append's LDS is reused by the next chunk
     }
 }
 
@@ -734,14 +770,10 @@ __global__ __launch_bounds__(kMarchThreads) void image_chunk_kernel(
     const float *__restrict__ t0_all, const float *__restrict__ t1_all, const int32_t *__restrict__ cursor,
     float *__restrict__ t0s, float *__restrict__ t1s, int32_t *__restrict__ ridx, int32_t *__restrict__ packed)
 {
-    constexpr int kWaves = kMarchThreads / 64;
-    __shared__ int wave_tot[kWaves];
-    __shared__ long long block_base;
     const IterPlan &P = *plan;
     const int64_t total = P.count[0];
     const int limit = P.limit[0];
     const int64_t base = P.sample_base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t s0 = (int64_t)blockIdx.x * kMarchThreads; s0 < total; s0 += (int64_t)gridDim.x * kMarchThreads) {
         const int64_t idx = s0 + threadIdx.x;
         const bool active = idx < total;
@@ -754,23 +786,11 @@ __global__ __launch_bounds__(kMarchThreads) void image_chunk_kernel(
             n = (int)(left < limit ? left : limit);
             src = packed_all[2 * r] + cur;
         }
-        int incl = n;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0;
-            for (int w = 0; w < kWaves; ++w) { const int t = wave_tot[w]; wave_tot[w] = run; run += t; }
-            block_base = run > 0 ? (long long)atomicAdd(reinterpret_cast<unsigned long long *>(&plan->total_samples),
-                                                        (unsigned long long)run) : 0;
-        }
-        __syncthreads();
+        const int64_t slot = workgroup_reserve<kMarchThreads / 64>(n, [&](int run) {
+            return (long long)atomicAdd(reinterpret_cast<unsigned long long *>(&plan->total_samples), (unsigned long long)run);
+        });
         if (active) {
-            const int64_t start = base + (int64_t)block_base + wave_tot[wave] + (incl - n);
+            const int64_t start = base + slot;
             packed[2 * r] = (int32_t)start;
             packed[2 * r + 1] = n;
             for (int i = 0; i < n; ++i) {
@@ -795,9 +815,6 @@ __global__ __launch_bounds__(kCompositeThreads) void image_composite_kernel(
     float *__restrict__ rgb, float *__restrict__ opacity, float *__restrict__ depth, float eps, float alpha_thre,
     int64_t n_all)
 {
-    constexpr int kWaves = kCompositeThreads / 64;
-    __shared__ int wave_alive[kWaves], wave_samples[kWaves], wave_kept[kWaves];
-    __shared__ long long block_base;
     const IterPlan &P = *plan;
     const int64_t total = P.count[0];
     for (int64_t s0 = (int64_t)blockIdx.x * kCompositeThreads; s0 < total; s0 += (int64_t)gridDim.x * kCompositeThreads) {
@@ -866,27 +883,14 @@ __global__ __launch_bounds__(kCompositeThreads) void image_composite_kernel(
                 alive = open && (int64_t)cur < ray_count(packed_all, r, n_all) && (det_expf(-acc) >= eps);
             }
         }
-        const unsigned long long ballot = __ballot(alive);
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        int wsum = cnt, ksum = kept_new;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { wsum += __shfl_xor(wsum, off, 64); ksum += __shfl_xor(ksum, off, 64); }
-        if (lane == 0) { wave_alive[wave] = __builtin_popcountll(ballot); wave_samples[wave] = wsum; wave_kept[wave] = ksum; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0, samples = 0, keptw = 0;
-            for (int w = 0; w < kWaves; ++w) {
-                int t = wave_alive[w]; wave_alive[w] = run; run += t; samples += wave_samples[w]; keptw += wave_kept[w];
-            }
-            const unsigned long long add = (unsigned long long)run + ((unsigned long long)samples << 32);
-            block_base = add != 0 ? (long long)(atomicAdd(&plan->next[0], add) & 0xffffffffull) : 0;
-            if (keptw) atomicAdd(&plan->next[1], (unsigned long long)keptw);       // kept samples of the iteration
-        }
-        __syncthreads();
-        if (alive) {
-            const int rank = __builtin_popcountll(ballot & ((1ull << lane) - 1ull));
-            next_list[block_base + wave_alive[wave] + rank] = (int32_t)r;
-        }
+        const int sums[2] = { cnt, kept_new };
+        const int slot = workgroup_append<kCompositeThreads / 64, 2>(alive, sums, [&](int run, const int *tot) {
+            const unsigned long long add = (unsigned long long)run + ((unsigned long long)tot[0] << 32);
+            const int base = add != 0 ? (int)(atomicAdd(&plan->next[0], add) & 0xffffffffull) : 0;
+            if (tot[1]) atomicAdd(&plan->next[1], (unsigned long long)tot[1]);        // kept samples of the iteration
+            return base;
+        });
+        if (alive) next_list[slot] = (int32_t)r;
         __syncthreads();
     }
 }
@@ -984,83 +988,55 @@ template <bool SINGLE>
 __global__ __launch_bounds__(kMarchThreads, SINGLE ? 4 : 3) void march_all_onepass_kernel(MarchAllArgs A, int64_t capacity,
                                                                                          unsigned long long *total)
 {
-    constexpr int kWaves = kMarchThreads / 64;
-    __shared__ int wave_tot[kWaves];
-    __shared__ long long block_base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r = (int64_t)blockIdx.x * kMarchThreads + threadIdx.x;
     const bool active = r < A.n_rays;
     const int m = A.grid.n_grids;
     float o[3] = { 0.0f, 0.0f, 0.0f }, d[3] = { 0.0f, 0.0f, 1.0f };
     float near = 0.0f, t_term = 0.0f;
-    float run_t[kMaxRuns];
-    int run_n[kMaxRuns];
-#pragma unroll
-    for (int k = 0; k < kMaxRuns; ++k) { run_t[k] = 0.0f; run_n[k] = 0; }
-    int n = 0, n_runs = 0;
     const float *const ts_row = (SINGLE || !active) ? nullptr : A.t_sorted + r * 2 * m;
     const int64_t *const ti_row = (SINGLE || !active) ? nullptr : A.t_indices + r * 2 * m;
     const uint8_t *const hit_row = (SINGLE || !active) ? nullptr : A.hits + r * m;
+    const auto walk = [&](auto &&emit, float &t_out) {
+        return traverse_ray_frame<kFrameLook, SINGLE, false>(A.grid, A.accel, true, o, d, near, A.far_plane, ts_row, ti_row,
+                                                             hit_row, emit, t_out);
+    };
+    SampleRuns runs;
+    int n = 0;
     if (active) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { o[a] = A.rays_o[3 * r + a]; d[a] = A.rays_d[3 * r + a]; }
         near = A.near_planes[r];
-        float prev_end = 0.0f;
-        n = traverse_ray_frame<kFrameLook, SINGLE, false>(
-            A.grid, A.accel, true, o, d, near, A.far_plane, ts_row, ti_row, hit_row,
-            [&](int i, float t0, float t1) {
-                const bool fresh = i == 0 || t0 != prev_end;
-                if (fresh) ++n_runs;
-                prev_end = t1;
-#pragma unroll
-                for (int k = 0; k < kMaxRuns; ++k) {
-                    const bool here = n_runs == k + 1;
-                    run_t[k] = (here && fresh) ? t0 : run_t[k];
-                    run_n[k] += here ? 1 : 0;
-                }
-            },
-            t_term);
+        n = walk([&](int i, float t0, float t1) { runs.record(i, t0, t1); }, t_term);
     }
-    int incl = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int w = 0; w < kWaves; ++w) { const int t = wave_tot[w]; wave_tot[w] = run; run += t; }
-        block_base = run > 0 ? (long long)atomicAdd(total, (unsigned long long)run) : 0;
-    }
-    __syncthreads();
+    const int64_t start = workgroup_reserve<kMarchThreads / 64>(n, [&](int run) {
+        return (long long)atomicAdd(total, (unsigned long long)run);
+    });
     if (!active) return;
-    const int64_t start = (int64_t)block_base + wave_tot[wave] + (incl - n);
     A.packed[2 * r] = start;
     A.packed[2 * r + 1] = n;
     if (n == 0 || start + n > capacity) return;
     float *const p0 = A.t_starts + start, *const p1 = A.t_ends + start;
-    if (n_runs > kMaxRuns || !(A.grid.step_size > 0.0f)) {
+    const auto store = [&](int i, float t0, float t1) { p0[i] = t0; p1[i] = t1; };
+    if (!runs.replayable(A.grid)) {
         float unused;
-        (void)traverse_ray_frame<kFrameLook, SINGLE, false>(A.grid, A.accel, true, o, d, near, A.far_plane, ts_row, ti_row, hit_row,
-                                                     [&](int i, float t0, float t1) { p0[i] = t0; p1[i] = t1; }, unused);
+        (void)walk(store, unused);
     } else {
-        int pos = 0;
-#pragma unroll
-        for (int k = 0; k < kMaxRuns; ++k) {
-            float t = run_t[k];
-            for (int j = 0; j < run_n[k]; ++j) {
-                const float t1 = t + calc_dt(t, A.grid.cone_angle, A.grid.step_size, 1e10f);
-                p0[pos] = t; p1[pos] = t1;
-                ++pos;
-                t = t1;
-            }
-        }
+        runs.replay(A.grid, store);
     }
 }
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+// A bump allocator over a call's workspace: every array starts 256-byte aligned; `off` ends as the bytes taken (base may
+// be NULL to size a workspace).
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t count)
+    {
+        T *p = (T *)(base + off);
+        off = (off + count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
 
 struct FrameWorkspace {
     float *t_sorted; uint8_t *t_indices; uint8_t *hits; float *near; int32_t *packed;
@@ -1094,26 +1070,25 @@ static inline int64_t sample_capacity(int n_frames, int64_t rays_per_frame, int 
 static FrameWorkspace carve(void *base, int64_t n, int m, int64_t cap, int max_iters, int res, bool per_ray_times = false)
 {
     FrameWorkspace w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return (char *)base + o; };
-    w.t_sorted = (float *)take((size_t)n * 2 * m * 4);
-    w.t_indices = (uint8_t *)take((size_t)n * 2 * m);
-    w.hits = (uint8_t *)take((size_t)n * m);
-    w.near = (float *)take((size_t)n * 4);
-    w.packed = (int32_t *)take((size_t)n * 8);
-    w.alive_a = (int32_t *)take((size_t)n * 4);
-    w.alive_b = (int32_t *)take((size_t)n * 4);
-    w.plans = (IterPlan *)take((size_t)(max_iters + 2) * sizeof(IterPlan));
-    w.lattice = (float *)take(256 * 4);
-    w.ts_ray = (float *)take(per_ray_times ? (size_t)n * 4 : 0);
-    w.t0 = (float *)take((size_t)cap * 4);
-    w.t1 = (float *)take((size_t)cap * 4);
-    w.ridx = (int32_t *)take((size_t)cap * 4);
-    w.sigma = (float *)take((size_t)cap * 4);
-    w.rgbs = (float *)take((size_t)cap * 12);
+    Carver c{ (char *)base };
+    w.t_sorted = c.take<float>((size_t)n * 2 * m);
+    w.t_indices = c.take<uint8_t>((size_t)n * 2 * m);
+    w.hits = c.take<uint8_t>((size_t)n * m);
+    w.near = c.take<float>((size_t)n);
+    w.packed = c.take<int32_t>((size_t)n * 2);
+    w.alive_a = c.take<int32_t>((size_t)n);
+    w.alive_b = c.take<int32_t>((size_t)n);
+    w.plans = c.take<IterPlan>((size_t)max_iters + 2);
+    w.lattice = c.take<float>(256);
+    w.ts_ray = c.take<float>(per_ray_times ? (size_t)n : 0);
+    w.t0 = c.take<float>((size_t)cap);
+    w.t1 = c.take<float>((size_t)cap);
+    w.ridx = c.take<int32_t>((size_t)cap);
+    w.sigma = c.take<float>((size_t)cap);
+    w.rgbs = c.take<float>((size_t)cap * 3);
     const int64_t nbk = (res + kBrick - 1) / kBrick;
-    w.accel = (uint8_t *)take((size_t)(2 * m * nbk * nbk * nbk));       // brick field + scratch (no accel from the caller)
-    w.bytes = off;
+    w.accel = c.take<uint8_t>((size_t)(2 * m * nbk * nbk * nbk));       // brick field + scratch (no accel from the caller)
+    w.bytes = c.off;
     return w;
 }
 
@@ -1144,6 +1119,52 @@ static int wait_published(volatile long long *flag, long long seq, hipStream_t s
         } else {
             CED_CPU_PAUSE();
         }
+    }
+    return CED_OK;
+}
+
+// Run-ahead control, before iteration `it` is enqueued: the plan of iteration it - kRunAhead must have been published
+// (by the schedule launch of the iteration before it, or by the initial one; plan_seq[k]: the publication of plan k).
+// Then `stop` when the loop is over, else alive_bound tightened to the published alive count.  pub: the words
+// {alive, done, seq} the latest plan is published to.  host_iter (sharded frames, else NULL): those of every plan --
+// every process must enqueue the same number of iterations (each holds a collective), so the loop ends on the plan of
+// iteration it - kRunAhead, identical on all processes, and on nothing later that happens to have been published already.
+static int run_ahead(volatile long long *pub, volatile long long *host_iter, const std::vector<long long> &plan_seq, int it,
+                     hipStream_t stream, const char *who, bool &stop, long long &alive_bound)
+{
+    const int need = it - kRunAhead;
+    if (need < 0 && host_iter) return CED_OK;
+    volatile long long *const rec = host_iter ? host_iter + 3 * need : pub;
+    if (need >= 0) {
+        const int rc = wait_published(rec + 2, plan_seq[need], stream, who);
+        if (rc) return rc;
+    }
+    if (host_iter || __atomic_load_n(pub + 2, __ATOMIC_ACQUIRE) >= plan_seq[0]) {   // something of THIS call is published
+        if (rec[1]) {                                                               // nothing left: stop enqueueing
+            stop = true;
+            return CED_OK;
+        }
+        const long long a = rec[0];
+        if (a >= 0 && a < alive_bound) alive_bound = a;
+    }
+    return CED_OK;
+}
+
+// The per-iteration record of a call: the plans of its `enqueued` iterations and the one after come back in one copy
+// (the call blocks here, once).  n_iters: the iterations that ran, up to the first plan with nothing left; a loop that
+// was not stopped by such a plan left rays alive.
+static int read_back_plans(const IterPlan *dev_plans, int enqueued, hipStream_t stream, const char *what, const char *who,
+                           std::vector<IterPlan> &plans, int &n_iters)
+{
+    plans.resize((size_t)enqueued + 1);
+    if (hipMemcpyAsync(plans.data(), dev_plans, plans.size() * sizeof(IterPlan), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+        return check_launch(what);
+    n_iters = 0;
+    while (n_iters < enqueued && !plans[n_iters].done && plans[n_iters].total_slots != 0) ++n_iters;
+    if (n_iters == enqueued && !plans[enqueued].done) {
+        set_error("%s: the loop stopped after %d iterations with rays still alive", who, enqueued);
+        return CED_E_LAUNCH;
     }
     return CED_OK;
 }
@@ -1221,13 +1242,13 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
         acc = AccelSpec{ W.accel, nb, nullptr };
     }
     volatile long long *pub = (volatile long long *)host_stats;
-    std::vector<long long> seq_of((size_t)max_iters + 1);
-    long long seq = ++g_publish_seq;
+    std::vector<long long> plan_seq((size_t)max_iters + 1);       // publication of plan k
+    plan_seq[0] = ++g_publish_seq;
     const bool use_lattice = cone_angle == 0.0f && step_size > 0.0f && near_plane >= 0.0f;
     if (use_lattice) build_lattice(near_plane, step_size, reinterpret_cast<float *>(host_stats + kHostLatticeWord));
     hipLaunchKernelGGL(frame_init_kernel, dim3(1), dim3(64), 0, stream,
                        ScheduleArgs{ W.plans, -1, n_frames, (int)rays_per_frame, min_samples, (int)max_samples,
-                                     (long long *)host_stats, seq, xch ? xch->local_rays : nullptr, nullptr,
+                                     (long long *)host_stats, plan_seq[0], xch ? xch->local_rays : nullptr, nullptr,
                                      xch ? xch->global_rays_per_frame : 0, host_iter },
                        use_lattice ? W.lattice : (float *)nullptr,
                        (unsigned long long *)(trace ? trace->field_stamps : nullptr),
@@ -1236,36 +1257,13 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
     if (rc) return rc;
 
     const float opc_thres = (float)(1.0 - (double)early_stop_eps);
-    const long long seq_plan0 = seq;              // publication of plan[0]
     long long alive_bound = n_rays;               // rays alive in the iteration being enqueued: never more than this
     int it = 0;
     for (; it < max_iters; ++it) {
-        // run-ahead control: the plan of iteration it - kRunAhead must have been published (it is published by the
-        // schedule launch of iteration it - kRunAhead - 1, or by the initial one)
-        const int need = it - kRunAhead;
-        if (xch) {
-            // Sharded frames: every process must enqueue the same number of iterations (each holds a collective), so
-            // the loop ends on the plan of iteration `need` -- identical on all processes -- and on nothing later that
-            // happens to have been published already.
-            if (need >= 0) {
-                volatile long long *rec = host_iter + 3 * need;
-                rc = wait_published(rec + 2, need == 0 ? seq_plan0 : seq_of[need - 1], stream, who);
-                if (rc) return rc;
-                if (rec[1]) break;
-                const long long a = rec[0];
-                if (a >= 0 && a < alive_bound) alive_bound = a;
-            }
-        } else {
-            if (need >= 0) {
-                rc = wait_published(pub + 2, need == 0 ? seq_plan0 : seq_of[need - 1], stream, who);
-                if (rc) return rc;
-            }
-            if (__atomic_load_n(pub + 2, __ATOMIC_ACQUIRE) >= seq_plan0) {       // something of THIS call has been published
-                if (pub[1]) break;                                              // nothing left: stop enqueueing
-                const long long a = pub[0];
-                if (a >= 0 && a < alive_bound) alive_bound = a;
-            }
-        }
+        bool stop = false;
+        rc = run_ahead(pub, host_iter, plan_seq, it, stream, who, stop, alive_bound);
+        if (rc) return rc;
+        if (stop) break;
         IterPlan *plan = W.plans + it;
         const int32_t *cur_list = it == 0 ? nullptr : ((it & 1) ? W.alive_a : W.alive_b);
         int32_t *next_list = (it & 1) ? W.alive_b : W.alive_a;
@@ -1332,8 +1330,7 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
 
         int64_t cgrid = (slot_bound + kCompositeThreads - 1) / kCompositeThreads;
         if (cgrid > 4096) cgrid = 4096;
-        seq = ++g_publish_seq;
-        seq_of[it] = seq;
+        plan_seq[it + 1] = ++g_publish_seq;
         hipLaunchKernelGGL(frame_composite_kernel, dim3((unsigned)cgrid), dim3(kCompositeThreads), 0, stream,
                            plan, n_frames, (int)rays_per_frame, cur_list, next_list, W.packed, W.t0, W.t1, W.sigma, W.rgbs,
                            rgb, opacity, depth, opc_thres);
@@ -1353,7 +1350,7 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
         }
         hipLaunchKernelGGL(frame_schedule_kernel, dim3(1), dim3(64), 0, stream,
                            ScheduleArgs{ W.plans, it, n_frames, (int)rays_per_frame, min_samples, (int)max_samples,
-                                         (long long *)host_stats, seq, xch ? xch->local_rays : nullptr,
+                                         (long long *)host_stats, plan_seq[it + 1], xch ? xch->local_rays : nullptr,
                                          xch ? xch->counts : nullptr, xch ? xch->global_rays_per_frame : 0, host_iter });
         rc = check_launch("render_image_test (composite / schedule)");
         if (rc) return rc;
@@ -1362,16 +1359,13 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
     hipLaunchKernelGGL(frame_finalize_kernel, grd, blk, 0, stream, n_rays, bkgd, rgb, opacity, depth);
     rc = check_launch("render_image_test (finalize)");
     if (rc) return rc;
-    // the per-iteration record (plans) comes back in one copy; the call blocks here, once, for the sample totals
-    std::vector<IterPlan> plans((size_t)enqueued + 1);
-    if (hipMemcpyAsync(plans.data(), W.plans, plans.size() * sizeof(IterPlan), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
-        return check_launch("render_image_test (read-back)");
-    int64_t total[kMaxFrames] = { 0 };
+    std::vector<IterPlan> plans;
     int n_iters = 0;
-    for (int k = 0; k < enqueued; ++k) {
+    rc = read_back_plans(W.plans, enqueued, stream, "render_image_test (read-back)", who, plans, n_iters);
+    if (rc) return rc;
+    int64_t total[kMaxFrames] = { 0 };
+    for (int k = 0; k < n_iters; ++k) {
         const IterPlan &P = plans[k];
-        if (P.done || P.total_slots == 0) break;
         int64_t alive_total = 0, samples_it = 0;
         int max_limit = 0;
         for (int f = 0; f < n_frames; ++f) {
@@ -1385,11 +1379,6 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
             if (trace->iter_n_samples) trace->iter_n_samples[k] = max_limit;
             if (trace->iter_samples) trace->iter_samples[k] = samples_it;
         }
-        ++n_iters;
-    }
-    if (n_iters == enqueued && enqueued < max_iters && !plans[enqueued].done) {
-        set_error("%s: the frame loop stopped after %d iterations with rays still alive", who, enqueued);
-        return CED_E_LAUNCH;
     }
     if (trace) trace->n_iters = n_iters;
     if (total_samples_out)
@@ -1410,25 +1399,24 @@ constexpr int kImageMaxIters = 1024;
 static ImageWorkspace carve_image(void *base, int64_t n, int64_t cap)
 {
     ImageWorkspace w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return (char *)base + o; };
-    w.st.cursor = (int32_t *)take((size_t)n * 4);
-    w.st.acc_all = (float *)take((size_t)n * 4);
-    w.st.acc_kept = (float *)take((size_t)n * 4);
-    w.packed = (int32_t *)take((size_t)n * 8);
-    w.alive_a = (int32_t *)take((size_t)n * 4);
-    w.alive_b = (int32_t *)take((size_t)n * 4);
-    w.plans = (IterPlan *)take((size_t)(kImageMaxIters + 2) * sizeof(IterPlan));
-    w.t0 = (float *)take((size_t)cap * 4);
-    w.t1 = (float *)take((size_t)cap * 4);
-    w.ridx = (int32_t *)take((size_t)cap * 4);
-    w.sigma = (float *)take((size_t)cap * 4);
-    w.rgbs = (float *)take((size_t)cap * 12);
-    w.w = (float *)take((size_t)cap * 4);
-    w.tr = (float *)take((size_t)cap * 4);
-    w.al = (float *)take((size_t)cap * 4);
-    w.rank = (int32_t *)take((size_t)cap * 4);
-    w.bytes = off;
+    Carver c{ (char *)base };
+    w.st.cursor = c.take<int32_t>((size_t)n);
+    w.st.acc_all = c.take<float>((size_t)n);
+    w.st.acc_kept = c.take<float>((size_t)n);
+    w.packed = c.take<int32_t>((size_t)n * 2);
+    w.alive_a = c.take<int32_t>((size_t)n);
+    w.alive_b = c.take<int32_t>((size_t)n);
+    w.plans = c.take<IterPlan>((size_t)kImageMaxIters + 2);
+    w.t0 = c.take<float>((size_t)cap);
+    w.t1 = c.take<float>((size_t)cap);
+    w.ridx = c.take<int32_t>((size_t)cap);
+    w.sigma = c.take<float>((size_t)cap);
+    w.rgbs = c.take<float>((size_t)cap * 3);
+    w.w = c.take<float>((size_t)cap);
+    w.tr = c.take<float>((size_t)cap);
+    w.al = c.take<float>((size_t)cap);
+    w.rank = c.take<int32_t>((size_t)cap);
+    w.bytes = c.off;
     return w;
 }
 
@@ -1464,32 +1452,25 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
     const dim3 blk(256), grd((unsigned)((n_rays + 255) / 256));
     hipLaunchKernelGGL(image_prep_kernel, grd, blk, 0, stream, n_rays, W.st, rgb, opacity, depth);
     volatile long long *pub = (volatile long long *)host_stats;
-    std::vector<long long> seq_of((size_t)kImageMaxIters + 1);
-    long long seq = ++g_publish_seq;
+    std::vector<long long> plan_seq((size_t)kImageMaxIters + 1);  // publication of plan k
+    plan_seq[0] = ++g_publish_seq;
     const int big = 1 << 30;                               // no sample budget: the loop ends when no ray is alive
     // smallest chunk of an iteration (any chunking gives the same result; fewer, larger iterations against samples
     // evaluated behind a ray's end): measured on the 800x800 frame / the 262 k-ray batch, 4 for the full pass (4.26 ->
     // 4.03 ms against chunks from 1) and 8 for the density-only sampling pass
     const int min_chunk = full ? 4 : 8;
     hipLaunchKernelGGL(frame_init_kernel, dim3(1), dim3(64), 0, stream,
-                       ScheduleArgs{ W.plans, -1, 1, (int)n_rays, min_chunk, big, (long long *)host_stats, seq }, (float *)nullptr,
+                       ScheduleArgs{ W.plans, -1, 1, (int)n_rays, min_chunk, big, (long long *)host_stats, plan_seq[0] }, (float *)nullptr,
                        (unsigned long long *)nullptr, 0);
     int rc = check_launch("render_image (prep)");
     if (rc) return rc;
-    const long long seq_plan0 = seq;
     long long alive_bound = n_rays;
     int it = 0;
     for (; it < kImageMaxIters; ++it) {
-        const int need = it - kRunAhead;
-        if (need >= 0) {
-            rc = wait_published(pub + 2, need == 0 ? seq_plan0 : seq_of[need - 1], stream, who);
-            if (rc) return rc;
-        }
-        if (__atomic_load_n(pub + 2, __ATOMIC_ACQUIRE) >= seq_plan0) {
-            if (pub[1]) break;
-            const long long a = pub[0];
-            if (a >= 0 && a < alive_bound) alive_bound = a;
-        }
+        bool stop = false;
+        rc = run_ahead(pub, nullptr, plan_seq, it, stream, who, stop, alive_bound);
+        if (rc) return rc;
+        if (stop) break;
         IterPlan *plan = W.plans + it;
         const int32_t *cur_list = it == 0 ? nullptr : ((it & 1) ? W.alive_a : W.alive_b);
         int32_t *next_list = (it & 1) ? W.alive_b : W.alive_a;
@@ -1512,8 +1493,7 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
         int64_t cgrid = (alive_bound + kCompositeThreads - 1) / kCompositeThreads;
         if (cgrid > 4096) cgrid = 4096;
         if (cgrid < 1) cgrid = 1;
-        seq = ++g_publish_seq;
-        seq_of[it] = seq;
+        plan_seq[it + 1] = ++g_publish_seq;
         if (full)
             hipLaunchKernelGGL(image_composite_kernel<true>, dim3((unsigned)cgrid), dim3(kCompositeThreads), 0, stream, plan,
                                cur_list, next_list, W.packed, packed_all, W.t0, W.t1, W.sigma, W.rgbs, W.st, W.w, W.tr, W.al,
@@ -1524,7 +1504,7 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
                                (float *)nullptr, (float *)nullptr, (float *)nullptr, W.rank, (float *)nullptr,
                                (float *)nullptr, (float *)nullptr, early_stop_eps, alpha_thre, n_all);
         hipLaunchKernelGGL(frame_schedule_kernel, dim3(1), dim3(64), 0, stream,
-                           ScheduleArgs{ W.plans, it, 1, (int)n_rays, min_chunk, big, (long long *)host_stats, seq });
+                           ScheduleArgs{ W.plans, it, 1, (int)n_rays, min_chunk, big, (long long *)host_stats, plan_seq[it + 1] });
         rc = check_launch("render_image (iteration)");
         if (rc) return rc;
     }
@@ -1532,22 +1512,14 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
     if (full) hipLaunchKernelGGL(frame_finalize_kernel, grd, blk, 0, stream, n_rays, bkgd, rgb, opacity, depth);
     rc = check_launch("render_image (finalize)");
     if (rc) return rc;
-    std::vector<IterPlan> plans((size_t)enqueued + 1);
-    if (hipMemcpyAsync(plans.data(), W.plans, plans.size() * sizeof(IterPlan), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
-        return check_launch("render_image (read-back)");
-    int64_t processed = 0, kept_total = 0;
+    std::vector<IterPlan> plans;
     int n_iters = 0;
-    for (int k = 0; k < enqueued; ++k) {
-        const IterPlan &P = plans[k];
-        if (P.done || P.count[0] == 0) break;
-        processed = P.sample_base + P.total_samples;
-        kept_total += (int64_t)P.next[1];
-        ++n_iters;
-    }
-    if (n_iters == enqueued && enqueued == kImageMaxIters && !plans[enqueued].done) {
-        set_error("%s: rays still alive after %d iterations", who, enqueued);
-        return CED_E_LAUNCH;
+    rc = read_back_plans(W.plans, enqueued, stream, "render_image (read-back)", who, plans, n_iters);
+    if (rc) return rc;
+    int64_t processed = 0, kept_total = 0;
+    for (int k = 0; k < n_iters; ++k) {
+        processed = plans[k].sample_base + plans[k].total_samples;
+        kept_total += (int64_t)plans[k].next[1];
     }
     CED_REQUIRE(processed <= cap, "%s: internal: %lld samples processed, capacity %lld", who, (long long)processed, (long long)cap);
     if (stats_out) { stats_out[0] = processed; stats_out[1] = n_iters; stats_out[2] = kept_total; }

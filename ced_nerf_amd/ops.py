@@ -761,8 +761,26 @@ class FrameTracer:
         return [self.events[i][0].elapsed_time(self.events[i][1]) for i in range(n)]
 
 
-_frame_ws = {}
-_frame_ws_lock = __import__("threading").Lock()
+# One workspace + pinned hand-shake buffer per (device, stream) and call family: frames in flight on different streams
+# (PipelinedRenderer) never share them.  Two caches: ced_render_image_gather reads the image workspace after
+# ced_render_image has returned, so the frame calls must not reuse it.
+_frame_ws: Dict[tuple, tuple] = {}
+_image_ws: Dict[tuple, tuple] = {}
+_ws_lock = __import__("threading").Lock()
+
+
+def _cached_workspace(cache: dict, device, stream: int, need_bytes: int, host_words: int = 512):
+    """(device uint8 buffer of at least need_bytes, pinned int64 buffer of at least host_words) of (device, stream)."""
+    key = (device.index, stream)
+    with _ws_lock:
+        ws = cache.get(key)
+        if ws is None or ws[0].numel() < need_bytes or ws[1].numel() < host_words:
+            ws = (ws[0] if ws is not None and ws[0].numel() >= need_bytes
+                  else torch.empty((max(need_bytes, 1),), device=device, dtype=torch.uint8),
+                  ws[1] if ws is not None and ws[1].numel() >= host_words
+                  else torch.zeros((host_words,), dtype=torch.int64).pin_memory())
+            cache[key] = ws
+    return ws
 
 
 def render_image_test_native(desc: _lib.FieldDesc, rays_o, rays_d, binaries, aabbs, near_plane, far_plane,
@@ -788,15 +806,7 @@ def render_image_test_native(desc: _lib.FieldDesc, rays_o, rays_d, binaries, aab
     need = int(L.ced_render_image_test_workspace_bytes(n, m, res, float(cone_angle), int(max_samples)))
     if need < 0:
         raise ValueError("render_image_test: unsupported sizes")
-    # one workspace + pinned hand-shake buffer per (device, stream): frames in flight on different
-    # streams (PipelinedRenderer) never share them
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    with _frame_ws_lock:
-        ws = _frame_ws.get(key)
-        if ws is None or ws[0].numel() < need:
-            ws = (torch.empty((max(need, 1),), device=dev, dtype=torch.uint8),
-                  ws[1] if ws is not None else torch.zeros((512,), dtype=torch.int64).pin_memory())
-            _frame_ws[key] = ws
+    ws = _cached_workspace(_frame_ws, dev, torch.cuda.current_stream().cuda_stream, need)
     rgb = torch.empty((n, 3), device=dev, dtype=torch.float32)
     opacity = torch.empty((n, 1), device=dev, dtype=torch.float32)
     depth = torch.empty((n, 1), device=dev, dtype=torch.float32)
@@ -811,10 +821,9 @@ def render_image_test_native(desc: _lib.FieldDesc, rays_o, rays_d, binaries, aab
     return rgb, opacity, depth, int(total.value)
 
 
-def march_all(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_plane: float, step_size: float, cone_angle: float,
-              want_ray_indices: bool = True, t_sorted=None, t_indices=None, hits=None):
-    """ced_march_all: every ray marched to the far plane on the accelerated walk.  Several grid levels need the sorted
-    ray / box events (t_sorted, t_indices, hits).  Returns (t_starts, t_ends, ray_indices or None, packed_info [n,2])."""
+def _march_all_args(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_plane, step_size, cone_angle, t_sorted,
+                    t_indices, hits) -> tuple:
+    """The checked inputs of ced_march_all as its arguments up to `hits`."""
     _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
     _chk(aabbs, torch.float32, "aabbs"); _chk(near_planes, torch.float32, "near_planes")
     assert binaries.is_cuda and binaries.is_contiguous() and binaries.ndim == 4
@@ -824,12 +833,21 @@ def march_all(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_plane: fl
     if m > 1:
         _chk(t_sorted, torch.float32, "t_sorted"); _chk(t_indices, torch.int64, "t_indices")
         assert t_sorted.shape == (n, 2 * m) and t_indices.shape == (n, 2 * m) and hits.shape == (n, m) and hits.is_contiguous()
+    return (n, _p(rays_o), _p(rays_d), _p(_as_u8(binaries)), m, res, _p(aabbs), _p(accel), _p(near_planes), float(far_plane),
+            float(step_size), float(cone_angle), _p(t_sorted) if m > 1 else None, _p(t_indices) if m > 1 else None,
+            _p(_as_u8(hits)) if m > 1 else None)
+
+
+def march_all(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_plane: float, step_size: float, cone_angle: float,
+              want_ray_indices: bool = True, t_sorted=None, t_indices=None, hits=None):
+    """ced_march_all: every ray marched to the far plane on the accelerated walk.  Several grid levels need the sorted
+    ray / box events (t_sorted, t_indices, hits).  Returns (t_starts, t_ends, ray_indices or None, packed_info [n,2])."""
+    args = _march_all_args(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_plane, step_size, cone_angle, t_sorted,
+                           t_indices, hits)
+    n = args[0]
     dev = rays_o.device
     L = _lib.lib()
     packed = torch.zeros((n, 2), device=dev, dtype=torch.int64)
-    args = (n, _p(rays_o), _p(rays_d), _p(_as_u8(binaries)), m, res, _p(aabbs), _p(accel), _p(near_planes), float(far_plane),
-            float(step_size), float(cone_angle), _p(t_sorted) if m > 1 else None, _p(t_indices) if m > 1 else None,
-            _p(_as_u8(hits)) if m > 1 else None)
     _lib.check(L.ced_march_all(*args, 0, _p(packed), None, None, None, 0, None, _stream()), "march_all (count)")
     counts = packed[:, 1]
     incl = torch.cumsum(counts, 0)
@@ -849,43 +867,27 @@ def march_all_onepass(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_p
     """ced_march_all, one pass (fill = 2) into arrays of `capacity` samples.  Returns (t_starts, t_ends, packed_info,
     total) with `total` a DEVICE int64 scalar: the samples marched; > capacity means some rays stored nothing.  Rays'
     ranges are in workgroup arrival order (not sorted by ray)."""
-    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
-    _chk(aabbs, torch.float32, "aabbs"); _chk(near_planes, torch.float32, "near_planes")
-    assert binaries.is_cuda and binaries.is_contiguous() and binaries.ndim == 4 and accel is not None and accel.is_cuda
-    n = rays_o.shape[0]
-    m, res = binaries.shape[0], binaries.shape[1]
-    if m > 1:
-        _chk(t_sorted, torch.float32, "t_sorted"); _chk(t_indices, torch.int64, "t_indices")
-        assert t_sorted.shape == (n, 2 * m) and t_indices.shape == (n, 2 * m) and hits.shape == (n, m) and hits.is_contiguous()
+    args = _march_all_args(rays_o, rays_d, binaries, aabbs, accel, near_planes, far_plane, step_size, cone_angle, t_sorted,
+                           t_indices, hits)
     dev = rays_o.device
-    packed = torch.empty((n, 2), device=dev, dtype=torch.int64)
+    packed = torch.empty((args[0], 2), device=dev, dtype=torch.int64)
     total = torch.zeros((1,), device=dev, dtype=torch.int64)
     t_starts = torch.empty((capacity,), device=dev, dtype=torch.float32)
     t_ends = torch.empty((capacity,), device=dev, dtype=torch.float32)
-    rc = _lib.lib().ced_march_all(n, _p(rays_o), _p(rays_d), _p(_as_u8(binaries)), m, res, _p(aabbs), _p(accel),
-                                  _p(near_planes), float(far_plane), float(step_size), float(cone_angle),
-                                  _p(t_sorted) if m > 1 else None, _p(t_indices) if m > 1 else None,
-                                  _p(_as_u8(hits)) if m > 1 else None, 2, _p(packed), _p(t_starts), _p(t_ends), None,
-                                  int(capacity), _p(total), _stream())
+    rc = _lib.lib().ced_march_all(*args, 2, _p(packed), _p(t_starts), _p(t_ends), None, int(capacity), _p(total), _stream())
     _lib.check(rc, "march_all (one pass)")
     return t_starts, t_ends, packed, total
 
 
-_image_ws: Dict[tuple, tuple] = {}
 
-
-def render_image_eval_native(desc: _lib.FieldDesc, rays_o, rays_d, packed_info, t_starts, t_ends, early_stop_eps,
-                             alpha_thre, timestamps, t_per_ray, bkgd, chunk_rays: int = 0, max_workgroups: int = 0):
-    """ced_render_image + ced_render_image_gather: `sampling` (visibility filter) and `rendering` of cednerf/utils.py:115-133
-    from one field evaluation per sample.  (packed_info, t_starts, t_ends): the one-shot march of all rays.
-    Returns (rgb [n,3], opacity [n,1], depth [n,1], extras, ray_offsets [n+1] int64, stats) where extras holds the
-    kept samples' ray_indices (relative to chunks of `chunk_rays` rays when > 0), t_starts, t_ends, sigmas, rgbs,
-    weights, trans, alphas in the reference's order, and stats = (samples evaluated, iterations)."""
+def _render_image(desc: _lib.FieldDesc, rays_o, rays_d, packed_info, t_starts, t_ends, early_stop_eps, alpha_thre,
+                  timestamps, t_per_ray, bkgd, full: bool, chunk_rays: int, max_workgroups: int):
+    """ced_render_image + ced_render_image_gather.  full: pixel sums and every per-sample output; otherwise the
+    sampling-only mode (density only) and the kept samples' ray_indices, t_starts, t_ends.  Returns
+    ((rgb, opacity, depth) or None, extras, ray_offsets [n+1] int64, (samples evaluated, iterations))."""
     _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
     _chk(packed_info, torch.int64, "packed_info"); _chk(t_starts, torch.float32, "t_starts")
     _chk(t_ends, torch.float32, "t_ends"); _chk(timestamps, torch.float32, "timestamps")
-    _chk(bkgd, torch.float32, "render_bkgd", allow_none=True)
-    assert rays_o.ndim == 2 and rays_o.shape[1] == 3 and rays_o.shape == rays_d.shape
     n = rays_o.shape[0]
     n_all = t_starts.shape[0]
     assert packed_info.shape == (n, 2) and t_ends.shape == (n_all,)
@@ -896,37 +898,45 @@ def render_image_eval_native(desc: _lib.FieldDesc, rays_o, rays_d, packed_info, 
     need = int(L.ced_render_image_workspace_bytes(n, n_all))
     if need < 0:
         raise ValueError("render_image: unsupported sizes")
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    with _frame_ws_lock:
-        ws = _image_ws.get(key)
-        if ws is None or ws[0].numel() < need:
-            ws = (torch.empty((max(need, 1),), device=dev, dtype=torch.uint8),
-                  ws[1] if ws is not None else torch.zeros((512,), dtype=torch.int64).pin_memory())
-            _image_ws[key] = ws
-    rgb = torch.empty((n, 3), device=dev, dtype=torch.float32)
-    opacity = torch.empty((n, 1), device=dev, dtype=torch.float32)
-    depth = torch.empty((n, 1), device=dev, dtype=torch.float32)
+    ws = _cached_workspace(_image_ws, dev, torch.cuda.current_stream().cuda_stream, need)
+    f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+    pixels = (f(n, 3), f(n, 1), f(n, 1)) if full else None
     kept = torch.empty((n,), device=dev, dtype=torch.int32)
     stats = (C.c_int64 * 3)()
     rc = L.ced_render_image(C.byref(_with_workgroups(desc, max_workgroups)), n, _p(rays_o), _p(rays_d), n_all,
                             _p(packed_info), _p(t_starts), _p(t_ends), float(early_stop_eps), float(alpha_thre),
-                            _p(timestamps), int(bool(t_per_ray)), _p(bkgd), _p(rgb), _p(opacity), _p(depth), _p(kept),
-                            _p(ws[0]), ws[0].numel(), C.c_void_p(ws[1].data_ptr()), stats, None, _stream())
-    _lib.check(rc, "render_image")
+                            _p(timestamps), int(bool(t_per_ray)), _p(bkgd), *(map(_p, pixels) if full else (None,) * 3),
+                            _p(kept), _p(ws[0]), ws[0].numel(), C.c_void_p(ws[1].data_ptr()), stats, None, _stream())
+    mode = "" if full else " (sampling)"
+    _lib.check(rc, "render_image" + mode)
     processed = int(stats[0])
     offsets = torch.zeros((n + 1,), device=dev, dtype=torch.int64)
     torch.cumsum(kept, 0, out=offsets[1:])
     total = int(stats[2])                    # = offsets[-1], without another device round trip
-    f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
-    extras = {"ray_indices": torch.empty((total,), device=dev, dtype=torch.int64), "t_starts": f(total), "t_ends": f(total),
-              "sigmas": f(total), "rgbs": f(total, 3), "weights": f(total), "trans": f(total), "alphas": f(total)}
+    extras = {"ray_indices": torch.empty((total,), device=dev, dtype=torch.int64), "t_starts": f(total), "t_ends": f(total)}
+    if full:
+        extras.update(sigmas=f(total), rgbs=f(total, 3), weights=f(total), trans=f(total), alphas=f(total))
     if total > 0:               # (an alpha threshold can drop every sample of a faint scene)
+        names = ("ray_indices", "t_starts", "t_ends", "sigmas", "rgbs", "weights", "trans", "alphas")
         rc = L.ced_render_image_gather(n, n_all, processed, _p(ws[0]), ws[0].numel(), _p(offsets), int(chunk_rays),
-                                       _p(extras["ray_indices"]), _p(extras["t_starts"]), _p(extras["t_ends"]),
-                                       _p(extras["sigmas"]), _p(extras["rgbs"]), _p(extras["weights"]), _p(extras["trans"]),
-                                       _p(extras["alphas"]), _stream())
-        _lib.check(rc, "render_image_gather")
-    return rgb, opacity, depth, extras, offsets, (processed, int(stats[1]))
+                                       *(_p(extras.get(k)) for k in names), _stream())
+        _lib.check(rc, "render_image_gather" + mode)
+    return pixels, extras, offsets, (processed, int(stats[1]))
+
+
+def render_image_eval_native(desc: _lib.FieldDesc, rays_o, rays_d, packed_info, t_starts, t_ends, early_stop_eps,
+                             alpha_thre, timestamps, t_per_ray, bkgd, chunk_rays: int = 0, max_workgroups: int = 0):
+    """ced_render_image + ced_render_image_gather: `sampling` (visibility filter) and `rendering` of cednerf/utils.py:115-133
+    from one field evaluation per sample.  (packed_info, t_starts, t_ends): the one-shot march of all rays.
+    Returns (rgb [n,3], opacity [n,1], depth [n,1], extras, ray_offsets [n+1] int64, stats) where extras holds the
+    kept samples' ray_indices (relative to chunks of `chunk_rays` rays when > 0), t_starts, t_ends, sigmas, rgbs,
+    weights, trans, alphas in the reference's order, and stats = (samples evaluated, iterations)."""
+    _chk(bkgd, torch.float32, "render_bkgd", allow_none=True)
+    assert rays_o.ndim == 2 and rays_o.shape[1] == 3 and rays_o.shape == rays_d.shape
+    (rgb, opacity, depth), extras, offsets, stats = _render_image(
+        desc, rays_o, rays_d, packed_info, t_starts, t_ends, early_stop_eps, alpha_thre, timestamps, t_per_ray, bkgd,
+        True, chunk_rays, max_workgroups)
+    return rgb, opacity, depth, extras, offsets, stats
 
 
 def sampling_native(desc: _lib.FieldDesc, rays_o, rays_d, packed_info, t_starts, t_ends, early_stop_eps, alpha_thre,
@@ -934,42 +944,9 @@ def sampling_native(desc: _lib.FieldDesc, rays_o, rays_d, packed_info, t_starts,
     """The visibility filter of OccGridEstimator.sampling (sigma_fn = the fused field) on ced_render_image's
     sampling-only mode: density evaluated front to back, rays stopped at the transmittance threshold.
     Returns the surviving (ray_indices, t_starts, t_ends) -- those of the filter over every marched sample."""
-    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
-    _chk(packed_info, torch.int64, "packed_info"); _chk(t_starts, torch.float32, "t_starts")
-    _chk(t_ends, torch.float32, "t_ends"); _chk(timestamps, torch.float32, "timestamps")
-    n = rays_o.shape[0]
-    n_all = t_starts.shape[0]
-    assert packed_info.shape == (n, 2) and t_ends.shape == (n_all,)
-    if t_per_ray:
-        assert timestamps.numel() == n, "per-ray timestamps must have one entry per ray"
-    dev = rays_o.device
-    L = _lib.lib()
-    need = int(L.ced_render_image_workspace_bytes(n, n_all))
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    with _frame_ws_lock:
-        ws = _image_ws.get(key)
-        if ws is None or ws[0].numel() < need:
-            ws = (torch.empty((max(need, 1),), device=dev, dtype=torch.uint8),
-                  ws[1] if ws is not None else torch.zeros((512,), dtype=torch.int64).pin_memory())
-            _image_ws[key] = ws
-    kept = torch.empty((n,), device=dev, dtype=torch.int32)
-    stats = (C.c_int64 * 3)()
-    rc = L.ced_render_image(C.byref(_with_workgroups(desc, max_workgroups)), n, _p(rays_o), _p(rays_d), n_all,
-                            _p(packed_info), _p(t_starts), _p(t_ends), float(early_stop_eps), float(alpha_thre),
-                            _p(timestamps), int(bool(t_per_ray)), None, None, None, None, _p(kept),
-                            _p(ws[0]), ws[0].numel(), C.c_void_p(ws[1].data_ptr()), stats, None, _stream())
-    _lib.check(rc, "render_image (sampling)")
-    offsets = torch.zeros((n + 1,), device=dev, dtype=torch.int64)
-    torch.cumsum(kept, 0, out=offsets[1:])
-    total = int(offsets[-1].item()) if n > 0 else 0
-    ray_indices = torch.empty((total,), device=dev, dtype=torch.int64)
-    t0 = torch.empty((total,), device=dev, dtype=torch.float32)
-    t1 = torch.empty((total,), device=dev, dtype=torch.float32)
-    if total > 0:
-        rc = L.ced_render_image_gather(n, n_all, int(stats[0]), _p(ws[0]), ws[0].numel(), _p(offsets), 0, _p(ray_indices),
-                                       _p(t0), _p(t1), None, None, None, None, None, _stream())
-        _lib.check(rc, "render_image_gather (sampling)")
-    return ray_indices, t0, t1
+    _, extras, _, _ = _render_image(desc, rays_o, rays_d, packed_info, t_starts, t_ends, early_stop_eps, alpha_thre,
+                                    timestamps, t_per_ray, None, False, 0, max_workgroups)
+    return extras["ray_indices"], extras["t_starts"], extras["t_ends"]
 
 
 class ScheduleExchange:
@@ -1058,13 +1035,7 @@ def render_frames_test_native(desc: _lib.FieldDesc, n_frames: int, rays_o, rays_
     if need < 0:
         raise ValueError("render_frames_test: unsupported sizes (1..64 frames)")
     host_words = 512 if exchange is None else max(512, exchange.host_words)
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    with _frame_ws_lock:
-        ws = _frame_ws.get(key)
-        if ws is None or ws[0].numel() < need or ws[1].numel() < host_words:
-            ws = (ws[0] if ws is not None and ws[0].numel() >= need else torch.empty((max(need, 1),), device=dev, dtype=torch.uint8),
-                  ws[1] if ws is not None and ws[1].numel() >= host_words else torch.zeros((host_words,), dtype=torch.int64).pin_memory())
-            _frame_ws[key] = ws
+    ws = _cached_workspace(_frame_ws, dev, torch.cuda.current_stream().cuda_stream, need, host_words)
     rgb = torch.empty((n, 3), device=dev, dtype=torch.float32)
     opacity = torch.empty((n, 1), device=dev, dtype=torch.float32)
     depth = torch.empty((n, 1), device=dev, dtype=torch.float32)
