@@ -164,6 +164,12 @@ class DNGPradianceField(torch.nn.Module):
     def _weights(self):
         return list(self.xyz_wrap) + list(self.mlp_base) + list(self.mlp_head)
 
+    def weights_changed(self) -> None:
+        """Re-pack the MLP weights at the next launch.  The packed blob is keyed on the tensors' version counters; an
+        update that writes them without advancing the counters (torch's fused Adam) must say so here."""
+        with self._desc_lock:
+            self._packed_key = None
+
     def _descriptor(self) -> _lib.FieldDesc:
         with self._desc_lock:
             return self._descriptor_locked()

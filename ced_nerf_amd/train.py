@@ -480,7 +480,7 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
                render_bkgd: Optional[torch.Tensor] = None, grad_scaler=None, native_sampling: bool = True,
                overlap_table_grad: bool = True, rgb_loss: str = "smooth_l1", distortion_loss: bool = False,
                acc_entropy_loss: bool = False, opacity_loss: bool = False, weight_rgbper: bool = False,
-               loss_weights: Optional[Dict[str, float]] = None) -> Dict:
+               loss_weights: Optional[Dict[str, float]] = None, skip_empty: bool = False) -> Dict:
     """One optimisation step on a batch of rays (train_real.py:339-420): stratified occupancy-grid sampling with the
     current density (no gradient), differentiable field + compositing, colour loss, the enabled regularisers, optimiser
     step.
@@ -491,6 +491,8 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
       acc_entropy_loss (-ae)  "acc_entropy"    losses.acc_entropy_loss of the opacities
       opacity_loss     (-o)   "opacity"        losses.opacity_loss of the opacities
       weight_rgbper    (-wr)  "weight_rgbper"  losses.weighted_rgb_loss with the (detached) rendering weights
+    skip_empty: a batch whose rays keep no sample returns {"loss": nan, "n_samples": 0, "loss_terms": {}, "skipped": True}
+    before any gradient, optimiser or scaler work (train_real.py:351-352); the default runs every step through.
     Returns {"loss", "n_samples", "loss_terms"}: loss_terms holds the unscaled value of every enabled term."""
     if rgb_loss not in _COLOUR_LOSSES:
         raise ValueError(f"rgb_loss={rgb_loss!r}: one of {sorted(_COLOUR_LOSSES)}")
@@ -518,6 +520,8 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
                                                        far_plane=far_plane, render_step_size=render_step_size,
                                                        stratified=True, cone_angle=cone_angle, alpha_thre=alpha_thre,
                                                        sigma_field=(fused, ts, True) if native_sampling else None)
+    if skip_empty and t_starts.shape[0] == 0:
+        return {"loss": float("nan"), "n_samples": 0, "loss_terms": {}, "skipped": True}
 
     with_heads = field.use_feat_predict or field.use_weight_predict
 
@@ -563,6 +567,7 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
     else:
         optimizer.step()
     field.sync_half_table()
+    fused.weights_changed()          # a fused optimiser writes the parameters without advancing their versions
     if not terms:
         return {"loss": float(loss.detach()), "n_samples": int(t_starts.shape[0]), "loss_terms": {}}
     values = torch.stack([loss.detach()] + [v.detach().float() for v in terms.values()]).tolist()     # one read-back

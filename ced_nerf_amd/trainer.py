@@ -1,0 +1,227 @@
+"""The training loop of train_real.py:185-520 on this package's pieces.
+
+`fit` draws each step's batch with the one-launch sampler (`trainset.TrainViews.batch`), refreshes the occupancy grid,
+runs `train.train_step` (HIP sampling, field, compositing, losses) under the reference's optimiser, grad scaler,
+learning-rate schedule and dynamic ray batch, and evaluates held-out views with `metrics.evaluate_views`.
+
+    python -m ced_nerf_amd.trainer --data_root DATA --scene lego [-df -f -w -te -ta -o -d -wr -ae] [--max_steps N]
+
+trains a D-NeRF synthetic folder with the flags of opt.py and prints the reference's progress and evaluation lines.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import time
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import synthetic
+from .metrics import evaluate_views
+from .nerfacc_api import OccGridEstimator
+from .train import TrainableField, next_num_rays, refresh_occupancy, train_step
+from .trainset import BKGD_MODES, VIEW_MODES, TrainViews
+
+
+def _preset(name: str, max_steps: int, init_batch_size: int, target_sample_batch_size: int, lr: float, milestones,
+            train_bkgd: str, test_bkgd: str, view_mode: str) -> Dict:
+    c = synthetic.CONFIGS[name]          # the scene constants this package already keeps (train_real.py:86-175)
+    return dict(max_steps=max_steps, init_batch_size=init_batch_size, target_sample_batch_size=target_sample_batch_size,
+                lr=lr, weight_decay=0.0, aabb=list(c["aabb"]), near_plane=c["near_plane"], far_plane=c["far_plane"],
+                moving_step=c["moving_step"], hash_dst_resolution=c["hash_max_res"],
+                grid_resolution=c["grid_resolution"], grid_levels=c["grid_levels"],
+                render_step_size=c["render_step_size"], alpha_thre=c["alpha_thre"], cone_angle=c["cone_angle"],
+                milestones=tuple(milestones), train_bkgd=train_bkgd, test_bkgd=test_bkgd, view_mode=view_mode,
+                log2_hashmap_size=21)
+
+
+# train_real.py:85-182.  milestones are (numerator, denominator) pairs: milestone = max_steps * num // den, the
+# reference's integer arithmetic.  Backgrounds: D-NeRF passes no color_bkgd_aug (train_real.py:101), whose default is
+# white; HyperNeRF black; DyNeRF random for training and black for evaluation.  View mode: D-NeRF batches over images
+# (a view per ray), HyperNeRF draws one view per step.
+PRESETS: Dict[str, Dict] = {
+    "dnerf": _preset("dnerf", 20000, 1024, 1 << 18, 1e-2, ((1, 2), (3, 4), (9, 10)), "white", "white", "per_ray"),
+    "hypernerf": _preset("hypernerf", 20000, 1024, 1 << 18, 1e-2, ((1, 2), (3, 4), (9, 10)), "black", "black",
+                         "one_per_step"),
+    # DyNeRF samples rays uniformly here: the reference's ISG / IST importance sampling (dnerf_3d_video_IS.py) is not
+    # restated.
+    "dynerf": _preset("dynerf", 40000, 1024, 1 << 20, 1e-2, ((1, 2), (3, 4), (5, 6), (9, 10)), "random", "black",
+                      "one_per_step"),
+}
+
+def milestone_steps(milestones, max_steps: int):
+    return [max_steps * num // den for num, den in milestones]
+
+
+def make_scheduler(optimizer, max_steps: int, milestones):
+    """train_real.py:278-290: LinearLR(0.01 -> 1 over 100 steps) chained with MultiStepLR(milestones, 0.33)."""
+    return torch.optim.lr_scheduler.ChainedScheduler([
+        torch.optim.lr_scheduler.LinearLR(optimizer, start_factor=0.01, total_iters=100),
+        torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=milestone_steps(milestones, max_steps), gamma=0.33),
+    ])
+
+
+def resolve_config(preset: str = "dnerf", max_steps: Optional[int] = None, **overrides) -> Dict:
+    """The preset's constants with `overrides` applied; ValueError on an unknown preset, key or mode."""
+    if preset not in PRESETS:
+        raise ValueError(f"preset={preset!r}: one of {sorted(PRESETS)}")
+    cfg = dict(PRESETS[preset])
+    unknown = set(overrides) - set(cfg)
+    if unknown:
+        raise ValueError(f"unknown settings {sorted(unknown)} (known: {sorted(cfg)})")
+    cfg.update(overrides)
+    if max_steps is not None:
+        cfg["max_steps"] = int(max_steps)
+    if cfg["max_steps"] < 1:
+        raise ValueError(f"max_steps must be >= 1, got {cfg['max_steps']}")
+    for key in ("train_bkgd",):
+        if cfg[key] not in BKGD_MODES:
+            raise ValueError(f"{key}={cfg[key]!r}: one of {sorted(BKGD_MODES)}")
+    if cfg["test_bkgd"] not in ("white", "black"):
+        raise ValueError(f"test_bkgd={cfg['test_bkgd']!r}: 'white' or 'black'")
+    if cfg["view_mode"] not in VIEW_MODES:
+        raise ValueError(f"view_mode={cfg['view_mode']!r}: one of {sorted(VIEW_MODES)}")
+    if int(cfg["init_batch_size"]) < 1:
+        raise ValueError(f"init_batch_size must be >= 1, got {cfg['init_batch_size']}")
+    return cfg
+
+
+def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset: str = "dnerf",
+        max_steps: Optional[int] = None, seed: int = 42, *, use_div_offsets: bool = False,
+        use_time_embedding: bool = False, use_time_attenuation: bool = False, use_feat_predict: bool = False,
+        use_weight_predict: bool = False, table_dtype=np.float16, distortion_loss: bool = False,
+        acc_entropy_loss: bool = False, opacity_loss: bool = False, weight_rgbper: bool = False,
+        eval_every: int = 0, log_every: int = 10000, save_path: Optional[str] = None, verbose: bool = True,
+        **overrides) -> Dict:
+    """Trains a field on `train_views` as train_real.py:185-520 does and evaluates it on `test_views`.
+
+    Setup: OccGridEstimator(aabb, grid_resolution, grid_levels); a TrainableField with the reference's initialisation
+    (synthetic.init_field_params(regime="init") on estimator.aabbs[-1]) and the flags of train_real.py:253-265
+    (table_dtype float16 is the reference's table; float32 also trains); Adam(lr, eps=1e-15, fused) -- apex FusedAdam's
+    counterpart; GradScaler(2**10); LinearLR + MultiStepLR.  Per step, in the reference's order: batch, occupancy
+    refresh (every 16 steps), train_step (MSE colour loss, the enabled regularisers -d -ae -o -wr, the grad scaler),
+    dynamic num_rays, scheduler.  A step with no samples is skipped (train_real.py:351-352): no optimiser, scaler or
+    scheduler step, num_rays unchanged.  Steps 0 .. max_steps, as the reference's range(max_steps + 1).
+
+    `overrides` replace preset constants (max_steps, target_sample_batch_size, lr, log2_hashmap_size, ...).
+    Returns {"field", "inference", "estimator", "train_seconds", "history", "eval", "evals", "config"}: history holds a
+    dict per step (step, lr, num_rays, n_samples, loss, scale, skipped, occ_refreshed, seconds: the loop's wall time
+    when the step's loss had been read back, evaluations excluded); eval is evaluate_views' result
+    on test_views after the last step (None without test views); evals the (step, result) pairs of every eval_every.
+    save_path: torch.save({"radiance_field": inference.state_dict(), "occupancy_grid": estimator.state_dict()})."""
+    cfg = resolve_config(preset, max_steps, **overrides)
+    dev = train_views.device
+    if dev.type != "cuda":
+        raise NotImplementedError("fit trains on the GPU: the views must be on a cuda device")
+    torch.manual_seed(seed)                    # the occupancy refresh's draws (train_real.py:82, set_random_seed(42))
+    np.random.seed(seed)
+    steps = int(cfg["max_steps"])
+    flags = dict(use_div_offsets=use_div_offsets, use_time_embedding=use_time_embedding,
+                 use_time_attenuation=use_time_attenuation)
+    estimator = OccGridEstimator(cfg["aabb"], cfg["grid_resolution"], cfg["grid_levels"]).to(dev)
+    params = synthetic.init_field_params(estimator.aabbs[-1].cpu().numpy(), cfg["moving_step"], cfg["hash_dst_resolution"],
+                                         int(cfg["log2_hashmap_size"]), regime="init", seed=seed, table_dtype=table_dtype,
+                                         **flags)
+    field = TrainableField(params, dev, use_feat_predict=use_feat_predict, use_weight_predict=use_weight_predict, seed=seed)
+    inference = field.shared_inference()
+    optimizer = torch.optim.Adam(field.parameters(), lr=cfg["lr"], eps=1e-15, weight_decay=cfg["weight_decay"], fused=True)
+    scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 10)
+    scheduler = make_scheduler(optimizer, steps, cfg["milestones"])
+    losses = dict(distortion_loss=distortion_loss, acc_entropy_loss=acc_entropy_loss, opacity_loss=opacity_loss,
+                  weight_rgbper=weight_rgbper)
+    render = dict(near_plane=cfg["near_plane"], far_plane=cfg["far_plane"], render_step_size=cfg["render_step_size"],
+                  cone_angle=cfg["cone_angle"], alpha_thre=cfg["alpha_thre"])
+
+    def evaluate():
+        if test_views is None:
+            return None
+        return evaluate_views(inference, estimator, test_views.test_views(bkgd=cfg["test_bkgd"]), **render)
+
+    num_rays = int(cfg["init_batch_size"])
+    target = int(cfg["target_sample_batch_size"])
+    history, evals = [], []
+    eval_seconds = 0.0
+    torch.cuda.synchronize(dev)
+    tic = time.time()
+    for step in range(steps + 1):
+        field.train()
+        estimator.train()
+        data = train_views.batch(num_rays, step, bkgd=cfg["train_bkgd"], view_mode=cfg["view_mode"], seed=seed)
+        rays, pixels, ts = data["rays"], data["pixels"], data["timestamps"]
+        version = estimator.binaries._version
+        refresh_occupancy(field, estimator, step, ts, cfg["render_step_size"])
+        refreshed = estimator.binaries._version != version
+        lr = optimizer.param_groups[0]["lr"]
+        out = train_step(field, estimator, optimizer, rays.origins, rays.viewdirs, ts, pixels, cfg["render_step_size"],
+                         near_plane=cfg["near_plane"], far_plane=cfg["far_plane"], cone_angle=cfg["cone_angle"],
+                         alpha_thre=cfg["alpha_thre"], render_bkgd=data["color_bkgd"], grad_scaler=scaler,
+                         rgb_loss="mse", skip_empty=True, **losses)
+        skipped = bool(out.get("skipped", False))
+        rec = dict(step=step, lr=lr, num_rays=num_rays, n_samples=out["n_samples"], loss=out["loss"],
+                   scale=float(scaler.get_scale()), skipped=skipped, occ_refreshed=refreshed,
+                   seconds=time.time() - tic - eval_seconds)
+        history.append(rec)
+        if not skipped:
+            num_rays = next_num_rays(num_rays, out["n_samples"], target) if target > 0 else num_rays
+            scheduler.step()
+        if verbose and (step % log_every == 0 or step == steps):
+            psnr = -10.0 * math.log10(out["loss"]) if out["loss"] > 0 else float("inf")
+            print(f"elapsed_time={time.time() - tic - eval_seconds:.2f}s | step={step} | loss={out['loss']:.5f} | "
+                  f"psnr={psnr:.2f} | n_rendering_samples={out['n_samples']:d} | num_rays={rec['num_rays']:d} | ",
+                  flush=True)
+        if eval_every and step > 0 and step % eval_every == 0 and step != steps:
+            t0 = time.time()
+            evals.append((step, evaluate()))
+            eval_seconds += time.time() - t0
+    torch.cuda.synchronize(dev)
+    train_seconds = time.time() - tic - eval_seconds
+    field.sync_half_table()
+    if save_path:
+        torch.save({"radiance_field": inference.state_dict(), "occupancy_grid": estimator.state_dict()}, save_path)
+    result = evaluate()
+    if result is not None:
+        evals.append((steps, result))
+        if verbose:
+            print(f"evaluation: psnr_avg={result['psnr_avg']}, ssim_avg={result['ssim_avg']}", flush=True)
+    return dict(field=field, inference=inference, estimator=estimator, train_seconds=train_seconds, history=history,
+                eval=result, evals=evals, config=cfg)
+
+
+def main(argv=None) -> int:
+    """CLI over a D-NeRF synthetic folder, with the flag names of opt.py."""
+    p = argparse.ArgumentParser(description="Train a D-NeRF synthetic scene (train_real.py's loop)")
+    p.add_argument("--data_root", required=True)
+    p.add_argument("--scene", required=True)
+    p.add_argument("--train_split", default="train", choices=["train", "trainval"])
+    p.add_argument("--test_split", default="test")
+    p.add_argument("--max_steps", type=int, default=None)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--log2_hashmap_size", type=int, default=21)
+    p.add_argument("--save_path", default=None)
+    p.add_argument("-df", "--use_div_offsets", action="store_true")
+    p.add_argument("-f", "--use_feat_predict", action="store_true")
+    p.add_argument("-w", "--use_weight_predict", action="store_true")
+    p.add_argument("-te", "--use_time_embedding", action="store_true")
+    p.add_argument("-ta", "--use_time_attenuation", action="store_true")
+    p.add_argument("-ms", "--moving_step", type=float, default=None)
+    p.add_argument("-o", "--use_opacity_loss", action="store_true")
+    p.add_argument("-d", "--distortion_loss", action="store_true")
+    p.add_argument("-wr", "--weight_rgbper", action="store_true")
+    p.add_argument("-ae", "--acc_entorpy_loss", action="store_true")
+    a = p.parse_args(argv)
+    train = TrainViews.from_dnerf_folder(a.data_root, a.scene, a.train_split)
+    test = TrainViews.from_dnerf_folder(a.data_root, a.scene, a.test_split)
+    extra = {} if a.moving_step is None else dict(moving_step=a.moving_step)
+    log_every = 10000 if a.max_steps is None else max(1, min(10000, a.max_steps))
+    fit(train, test, preset="dnerf", max_steps=a.max_steps, seed=a.seed, use_div_offsets=a.use_div_offsets,
+        use_time_embedding=a.use_time_embedding, use_time_attenuation=a.use_time_attenuation,
+        use_feat_predict=a.use_feat_predict, use_weight_predict=a.use_weight_predict, distortion_loss=a.distortion_loss,
+        acc_entropy_loss=a.acc_entorpy_loss, opacity_loss=a.use_opacity_loss, weight_rgbper=a.weight_rgbper,
+        log_every=log_every, save_path=a.save_path, log2_hashmap_size=a.log2_hashmap_size, **extra)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -448,6 +448,35 @@ int ced_generate_rays_hypercam(int32_t width, int32_t height, const float *orien
                                float skew, float pixel_aspect_ratio, const float *radial3_host,
                                const float *tangential2_host, float *origins, float *viewdirs, void *stream);
 
+/* Training batch in one launch: replaces the per-step fetch_data + preprocess of datasets/dnerf_synthetic.py:142-242
+ * (D-NeRF, a view per ray, RGBA composited on the batch's background) and datasets/hypernerf.py:443-541 (HyperNeRF,
+ * one view per batch, RGB, rays at the pixel centre).  Views are device-resident:
+ *   images          uint8 [n_views, height, width, channels], channels 4 (RGBA) or 3 (RGB);
+ *   cameras         float [n_views, CED_PINHOLE_FLOATS] or [n_views, CED_HYPERCAM_FLOATS] (layouts below);
+ *   view_timestamps float [n_views].
+ * Every ray r draws (view, x, y) uniformly (view_mode CED_VIEW_PER_RAY), or the batch draws one view
+ * (CED_VIEW_PER_STEP); its ray is the full-frame kernels' ray of that pixel, bit for bit (pinhole: pixel (x, y) as in
+ * ced_generate_rays_pinhole; hypercam: centre (x + .5, y + .5) as in ced_generate_rays_hypercam).  Pixels: RGBA
+ * rgb / 255 * (a / 255) + bkgd * (1 - a / 255), RGB u8 / 255.  Background: white, black or one random colour per batch.
+ * The random numbers are a pure function of (seed, step, ray, draw) (train_batch.hip, DESIGN.md "Training batches").
+ * Writes origins [n,3], viewdirs [n,3], pixels [n,3], timestamps [n] (the view's), color_bkgd [3] and, if `indices` is
+ * not NULL, the drawn (view, x, y) as int32 [n,3].  One launch, no host synchronisation. */
+#define CED_CAMERA_PINHOLE 0
+#define CED_CAMERA_HYPERCAM 1
+#define CED_PINHOLE_FLOATS 17    /* fx, fy, cx, cy, c2w[3][4] row-major, sign (-1 OpenGL, +1 OpenCV) */
+#define CED_HYPERCAM_FLOATS 22   /* orientation[3][3] row-major, position[3], focal, principal x, principal y, skew,
+                                    pixel aspect ratio, k1, k2, k3, p1, p2 */
+#define CED_VIEW_PER_RAY 0
+#define CED_VIEW_PER_STEP 1
+#define CED_BKGD_WHITE 0
+#define CED_BKGD_BLACK 1
+#define CED_BKGD_RANDOM 2
+int ced_sample_training_batch(int32_t camera_model, int32_t n_views, int32_t width, int32_t height, int32_t channels,
+                              const uint8_t *images, const float *cameras, const float *view_timestamps,
+                              int64_t num_rays, uint64_t seed, int64_t step, int32_t view_mode, int32_t bkgd_mode,
+                              float *origins, float *viewdirs, float *pixels, float *timestamps, float *color_bkgd,
+                              int32_t *indices, void *stream);
+
 /* Optional per-iteration trace of ced_render_image_test (host struct, host arrays of `capacity`
  * entries, each may be NULL).  field_begin/field_end are caller-created hipEvent_t handles that the
  * renderer records on `stream` around the field-kernel launch of iteration i, so a benchmark can
