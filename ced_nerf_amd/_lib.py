@@ -15,7 +15,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("CED_NERF_LIB", os.path.join(_PKG, "libcednerf_hip.so"))
 SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "field_half.hip", "field_mixed.hip", "frame.hip", "occgrid.hip",
            "raygen.hip", "wgrad.hip", "pixels.hip", "accel.hip", "linear.hip", "mlp.hip", "train_glue.hip", "losses.hip",
-           "metrics.hip", "train_batch.hip"]
+           "metrics.hip", "train_batch.hip", "importance.hip"]
 MLP_F32, MLP_F16X2, MLP_F16, MLP_F32_HEAD16X2 = 0, 1, 2, 3          # ced_field_desc.mlp_precision
 # "f32+h16x2": sigma chain exact fp32 (counts / opacity / depth bit-identical to "f32"), colour head on split-fp16 MFMAs
 MLP_PRECISIONS = {"f32": MLP_F32, "f16x2": MLP_F16X2, "f16": MLP_F16, "f32+h16x2": MLP_F32_HEAD16X2}
@@ -131,6 +131,12 @@ PROTOTYPES = {
     "ced_generate_rays_hypercam": (C.c_int, [_i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _f, _f, _f,
                                              C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
     "ced_sample_training_batch": (C.c_int, [_i32] * 5 + [_vp] * 3 + [_i64, C.c_uint64, _i64, _i32, _i32] + [_vp] * 7),
+    "ced_importance_batch_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "ced_sample_importance_batch": (C.c_int, [_i32] * 5 + [_vp] * 4 + [_i32, _i64, _i64, C.c_uint64, _i64, _i32] + [_vp] * 8
+                                    + [_i64, _vp]),
+    "ced_temporal_median_u8": (C.c_int, [_i32] * 4 + [_vp] * 3),
+    "ced_isg_weights": (C.c_int, [_i32] * 4 + [_vp, _vp, _f, _vp, _vp]),
+    "ced_ist_weights": (C.c_int, [_i32] * 4 + [_vp, _f, _i32, _vp, _vp]),
     "ced_render_image_test_workspace_bytes": (_i64, [_i64, _i32, _i32, _f, _i32]),
     "ced_render_image_test": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _f, _f, _f, _f, _f,
                                         _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i64),

@@ -58,6 +58,39 @@ __device__ __forceinline__ float det_expf(float x)
     return (x != x) ? x : v;
 }
 
+// log(x) for a positive normal x (the importance sampler's Exp(1) variates, train_batch.hip): x = 2^k * m with m in
+// (sqrt(1/2), sqrt(2)], f = m - 1 (exact), the Cephes logf polynomial in Horner form and its two-part k * ln 2.  Every
+// operation is one float32 rounding (no fused multiply-add, no libm, no hardware log), so numpy float32 gives the same
+// bits (trainset.det_logf_np).
+__device__ __forceinline__ float det_logf(float x)
+{
+    const uint32_t b = __builtin_bit_cast(uint32_t, x);
+    int k = (int)(b >> 23) - 127;
+    float m = __builtin_bit_cast(float, (b & 0x007fffffu) | 0x3f800000u);
+    if (m > 1.41421353816986083984375f) {
+        m = m * 0.5f;
+        k += 1;
+    }
+    const float f = m - 1.0f;
+    const float z = f * f;
+    float p = 7.0376836292e-2f;
+    p = p * f + -1.1514610310e-1f;
+    p = p * f + 1.1676998740e-1f;
+    p = p * f + -1.2420140846e-1f;
+    p = p * f + 1.4249322787e-1f;
+    p = p * f + -1.6668057665e-1f;
+    p = p * f + 2.0000714765e-1f;
+    p = p * f + -2.4999993993e-1f;
+    p = p * f + 3.3333331174e-1f;
+    const float kf = (float)k;
+    float y = (p * f) * z;
+    y = y + kf * -2.12194440e-4f;
+    y = y + z * -0.5f;
+    float r = f + y;
+    r = r + kf * 0.693359375f;
+    return r;
+}
+
 __device__ __forceinline__ float sin_kernel(float x)
 {
     float x2 = x * x;

@@ -1,6 +1,7 @@
 """The training loop of train_real.py:185-520 on this package's pieces.
 
-`fit` draws each step's batch with the one-launch sampler (`trainset.TrainViews.batch`), refreshes the occupancy grid,
+`fit` draws each step's batch with the one-launch sampler (`trainset.TrainViews.batch`, or DyNeRF's importance sampler
+`TrainViews.batch_importance` when given sampling weights), refreshes the occupancy grid,
 runs `train.train_step` (HIP sampling, field, compositing, losses) under the reference's optimiser, grad scaler,
 learning-rate schedule and dynamic ray batch, and evaluates held-out views with `metrics.evaluate_views`.
 
@@ -45,8 +46,8 @@ PRESETS: Dict[str, Dict] = {
     "dnerf": _preset("dnerf", 20000, 1024, 1 << 18, 1e-2, ((1, 2), (3, 4), (9, 10)), "white", "white", "per_ray"),
     "hypernerf": _preset("hypernerf", 20000, 1024, 1 << 18, 1e-2, ((1, 2), (3, 4), (9, 10)), "black", "black",
                          "one_per_step"),
-    # DyNeRF samples rays uniformly here: the reference's ISG / IST importance sampling (dnerf_3d_video_IS.py) is not
-    # restated.
+    # DyNeRF's ISG / IST importance sampling (dnerf_3d_video_IS.py:401-440) is fit's `sampling_weights` argument, with the
+    # maps of ced_nerf_amd.importance; without it the rays are uniform.
     "dynerf": _preset("dynerf", 40000, 1024, 1 << 20, 1e-2, ((1, 2), (3, 4), (5, 6), (9, 10)), "random", "black",
                       "one_per_step"),
 }
@@ -94,7 +95,8 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
         use_weight_predict: bool = False, table_dtype=np.float16, distortion_loss: bool = False,
         acc_entropy_loss: bool = False, opacity_loss: bool = False, weight_rgbper: bool = False,
         eval_every: int = 0, log_every: int = 10000, save_path: Optional[str] = None, verbose: bool = True,
-        **overrides) -> Dict:
+        sampling_weights: Optional[torch.Tensor] = None, weights_subsampled: int = 1,
+        ist_weights: Optional[torch.Tensor] = None, ist_from_step: Optional[int] = None, **overrides) -> Dict:
     """Trains a field on `train_views` as train_real.py:185-520 does and evaluates it on `test_views`.
 
     Setup: OccGridEstimator(aabb, grid_resolution, grid_levels); a TrainableField with the reference's initialisation
@@ -105,6 +107,13 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
     dynamic num_rays, scheduler.  A step with no samples is skipped (train_real.py:351-352): no optimiser, scaler or
     scheduler step, num_rays unchanged.  Steps 0 .. max_steps, as the reference's range(max_steps + 1).
 
+    `sampling_weights` (DyNeRF, dnerf_3d_video_IS.py:401-440): a float32 device tensor of V * (H // s) * (W // s) cell
+    weights, s = `weights_subsampled` (importance.isg_weights(...).reshape(-1), or the reference's isg_weights.pt); the
+    batch is then `TrainViews.batch_importance`, num_rays // s^2 cells without replacement, and the dynamic ray count
+    follows the number of rays returned.  From step `ist_from_step` on the map is `ist_weights` (the reference's
+    switch_to_ist, which train_real.py:301-309 has commented out: by default ISG throughout).  The history records then
+    carry "sampling": "isg" or "ist".  Without `sampling_weights` the batches are the uniform ones.
+
     `overrides` replace preset constants (max_steps, target_sample_batch_size, lr, log2_hashmap_size, ...).
     Returns {"field", "inference", "estimator", "train_seconds", "history", "eval", "evals", "config"}: history holds a
     dict per step (step, lr, num_rays, n_samples, loss, scale, skipped, occ_refreshed, seconds: the loop's wall time
@@ -112,6 +121,10 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
     on test_views after the last step (None without test views); evals the (step, result) pairs of every eval_every.
     save_path: torch.save({"radiance_field": inference.state_dict(), "occupancy_grid": estimator.state_dict()})."""
     cfg = resolve_config(preset, max_steps, **overrides)
+    if sampling_weights is None and (ist_weights is not None or ist_from_step is not None):
+        raise ValueError("ist_weights / ist_from_step switch an importance-sampled run: sampling_weights is missing")
+    if (ist_weights is None) != (ist_from_step is None):
+        raise ValueError("ist_weights and ist_from_step go together")
     dev = train_views.device
     if dev.type != "cuda":
         raise NotImplementedError("fit trains on the GPU: the views must be on a cuda device")
@@ -148,7 +161,12 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
     for step in range(steps + 1):
         field.train()
         estimator.train()
-        data = train_views.batch(num_rays, step, bkgd=cfg["train_bkgd"], view_mode=cfg["view_mode"], seed=seed)
+        if sampling_weights is None:
+            data = train_views.batch(num_rays, step, bkgd=cfg["train_bkgd"], view_mode=cfg["view_mode"], seed=seed)
+        else:
+            use_ist = ist_from_step is not None and step >= ist_from_step
+            data = train_views.batch_importance(num_rays, step, ist_weights if use_ist else sampling_weights,
+                                                weights_subsampled, bkgd=cfg["train_bkgd"], seed=seed)
         rays, pixels, ts = data["rays"], data["pixels"], data["timestamps"]
         version = estimator.binaries._version
         refresh_occupancy(field, estimator, step, ts, cfg["render_step_size"])
@@ -162,9 +180,12 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
         rec = dict(step=step, lr=lr, num_rays=num_rays, n_samples=out["n_samples"], loss=out["loss"],
                    scale=float(scaler.get_scale()), skipped=skipped, occ_refreshed=refreshed,
                    seconds=time.time() - tic - eval_seconds)
+        if sampling_weights is not None:
+            rec["sampling"] = "ist" if use_ist else "isg"
+            rec["n_rays"] = int(data["pixels"].shape[0])      # num_rays // s^2 cells of s^2 rays
         history.append(rec)
         if not skipped:
-            num_rays = next_num_rays(num_rays, out["n_samples"], target) if target > 0 else num_rays
+            num_rays = next_num_rays(int(data["pixels"].shape[0]), out["n_samples"], target) if target > 0 else num_rays
             scheduler.step()
         if verbose and (step % log_every == 0 or step == steps):
             psnr = -10.0 * math.log10(out["loss"]) if out["loss"] > 0 else float("inf")

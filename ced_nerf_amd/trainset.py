@@ -7,7 +7,8 @@ HyperNeRF draws one view per step and undistorts every ray of the batch on the h
 blocks and timestamps kept on the device, with no host work and no upload per step.
 
 The sampler's random numbers are a pure function of (seed, step, ray, draw); `draws` below restates them in numpy,
-bit for bit (DESIGN.md, "Training batches").
+bit for bit ("Training batches").  `TrainViews.batch_importance` is DyNeRF's importance-sampled batch
+(datasets/dnerf_3d_video_IS.py:401-440) on the same draws, restated by `importance_draws`.
 """
 from __future__ import annotations
 
@@ -96,6 +97,102 @@ def draws(seed: int, step: int, num_rays: int, n_views: int, width: int, height:
     else:
         colour = np.full(3, 1.0 if bkgd == "white" else 0.0, np.float32)
     return view, x, y, colour
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The importance sampler of train_batch.hip (ced_sample_importance_batch), restated in numpy
+# ---------------------------------------------------------------------------------------------------------------------
+def det_logf_np(x) -> np.ndarray:
+    """ced_common.hpp's det_logf on positive normal float32 values, operation for operation in float32."""
+    f32 = np.float32
+    x = np.ascontiguousarray(x, f32)
+    b = x.view(np.uint32)
+    k = (b >> np.uint32(23)).astype(np.int32) - np.int32(127)
+    m = ((b & np.uint32(0x007FFFFF)) | np.uint32(0x3F800000)).view(f32)
+    big = m > f32(1.41421353816986083984375)
+    m = np.where(big, m * f32(0.5), m).astype(f32)
+    k = np.where(big, k + np.int32(1), k).astype(np.int32)
+    f = m - f32(1.0)
+    z = f * f
+    p = np.full_like(f, f32(7.0376836292e-2))
+    for c in (-1.1514610310e-1, 1.1676998740e-1, -1.2420140846e-1, 1.4249322787e-1, -1.6668057665e-1, 2.0000714765e-1,
+              -2.4999993993e-1, 3.3333331174e-1):
+        p = p * f + f32(c)
+    kf = k.astype(f32)
+    y = (p * f) * z
+    y = y + kf * f32(-2.12194440e-4)
+    y = y + z * f32(-0.5)
+    r = f + y
+    r = r + kf * f32(0.693359375)
+    assert r.dtype == f32
+    return r
+
+
+def draw_exponential(u) -> np.ndarray:
+    """The Exp(1) variate of a 32-bit draw: unit = ((u >> 9) * 2 + 1) * 2^-24 in (0, 1), e = -det_logf(unit)."""
+    odd = (np.asarray(u, np.uint32) >> np.uint32(9)) * np.uint32(2) + np.uint32(1)
+    unit = odd.astype(np.float32) * np.float32(2.0 ** -24)
+    return -det_logf_np(unit)
+
+
+def importance_candidates(seed: int, step: int, weights, pool_size: int = 2_000_000):
+    """The sampler's candidates for a step: (cell [M] int64, key [M] uint32 bit patterns of weight / Exp(1) variate)."""
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    n = w.shape[0]
+    if n < 1 or n >= 1 << 31:
+        raise ValueError(f"the weight map must have 1 .. 2^31 - 1 cells, got {n}")
+    if pool_size < 1 or pool_size >= 1 << 31:
+        raise ValueError(f"pool_size must be in 1 .. 2^31 - 1, got {pool_size}")
+    key = batch_key(seed, step)
+    if n <= pool_size:
+        j = np.arange(n, dtype=np.uint64)
+        cell = j.astype(np.int64)
+    else:
+        j = np.arange(pool_size, dtype=np.uint64)
+        cell = draw_below(batch_draw(key, j, 3), n).astype(np.int64)
+    e = draw_exponential(batch_draw(key, j, 4))
+    wc = w[cell]
+    with np.errstate(over="ignore", under="ignore", invalid="ignore", divide="ignore"):
+        q = (wc / e).astype(np.float32)
+    bits = np.where((wc > 0) & np.isfinite(wc), q.view(np.uint32), np.uint32(0)).astype(np.uint32)
+    return cell, bits
+
+
+def select_largest(bits, k: int) -> np.ndarray:
+    """The sampler's selection: the candidates j of the k largest key patterns, equal keys to the lower j, in ascending
+    j.  ValueError when fewer than k patterns are positive."""
+    bits = np.asarray(bits, np.uint32)
+    order = np.argsort(-bits.astype(np.int64), kind="stable")[:k]
+    if order.shape[0] < k or bits[order[-1]] == 0:
+        raise ValueError(f"fewer than {k} candidates with a positive weight")
+    return np.sort(order)
+
+
+def importance_draws(seed: int, step: int, num_rays: int, weights, s: int, pool_size: int, width: int, height: int):
+    """What `TrainViews.batch_importance` draws: (view, x, y) as int32 [k * s * s] each, k = num_rays // s^2.  `weights`
+    is the flat map of V * (height // s) * (width // s) cells."""
+    s = int(s)
+    if s < 1 or s > min(width, height):
+        raise ValueError(f"weights_subsampled must be in 1 .. {min(width, height)}, got {s}")
+    k = int(num_rays) // (s * s)
+    if k < 1:
+        raise ValueError(f"num_rays={num_rays} gives no cell at weights_subsampled={s}")
+    hsub, wsub = height // s, width // s
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.shape[0] % (hsub * wsub):
+        raise ValueError(f"{w.shape[0]} weights are not whole views of {hsub} x {wsub} cells")
+    cell, bits = importance_candidates(seed, step, w, pool_size)
+    chosen = cell[select_largest(bits, k)]
+    view = chosen // (hsub * wsub)
+    ysub = (chosen % (hsub * wsub)) // wsub
+    xsub = (chosen % (hsub * wsub)) % wsub
+    xs, ys = [], []
+    for ah in range(s):
+        for aw in range(s):
+            xs.append(xsub * s + aw)
+            ys.append(ysub * s + ah)
+    return (np.tile(view, s * s).astype(np.int32), np.concatenate(xs).astype(np.int32),
+            np.concatenate(ys).astype(np.int32))
 
 
 def _u8_unit(t: torch.Tensor) -> torch.Tensor:
@@ -241,6 +338,71 @@ class TrainViews:
                 P(self.timestamps), num_rays, int(seed) % (1 << 64), int(step), VIEW_MODES[mode], BKGD_MODES[bkgd],
                 P(o), P(d), P(px), P(ts), P(bk), P(idx), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, "sample_training_batch")
+        out = {"rays": Rays(origins=o, viewdirs=d), "pixels": px, "timestamps": ts, "color_bkgd": bk}
+        if return_indices:
+            out["indices"] = idx
+        return out
+
+    def batch_importance(self, num_rays: int, step: int, weights: torch.Tensor, weights_subsampled: int = 1,
+                         bkgd: str = "random", seed: int = 0, pool_size: int = 2_000_000,
+                         return_indices: bool = False) -> Dict:
+        """The reference's importance-sampled item (dnerf_3d_video_IS.py:401-440): k = num_rays // s^2 cells of the
+        weight map drawn without replacement as torch.multinomial draws them, each expanded to its s x s pixels
+        (s = weights_subsampled); the dict of `batch` with k * s^2 rays.  `weights`: float32 device tensor of
+        V * (H // s) * (W // s) non-negative entries, cell (view * (H // s) + ysub) * (W // s) + xsub.  More cells than
+        `pool_size`: the draw is made among pool_size cells drawn uniformly with replacement first.  A pure function
+        of (seed, step), restated by `importance_draws`.  Reads one word back from the device to raise ValueError
+        when fewer than k candidates have a positive weight."""
+        num_rays, s, pool_size = int(num_rays), int(weights_subsampled), int(pool_size)
+        if bkgd not in BKGD_MODES:
+            raise ValueError(f"bkgd={bkgd!r}: one of {sorted(BKGD_MODES)}")
+        if self.channels != 3:
+            raise ValueError("batch_importance samples RGB views; these are RGBA")
+        if s < 1 or s > min(self.width, self.height):
+            raise ValueError(f"weights_subsampled must be in 1 .. {min(self.width, self.height)}, got {s}")
+        k = num_rays // (s * s)
+        if k < 1:
+            raise ValueError(f"num_rays={num_rays} gives no cell at weights_subsampled={s}")
+        n_cells = self.n_views * (self.height // s) * (self.width // s)
+        if n_cells >= 1 << 31:
+            raise ValueError(f"{n_cells} cells: the sampler indexes below 2^31")
+        if not 1 <= pool_size < 1 << 31:
+            raise ValueError(f"pool_size must be in 1 .. 2^31 - 1, got {pool_size}")
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.numel() != n_cells:
+            raise ValueError(f"weights must be a float32 tensor of {n_cells} cells "
+                             f"({self.n_views} x {self.height // s} x {self.width // s})")
+        if k > min(n_cells, pool_size):
+            raise ValueError(f"cannot draw {k} cells without replacement from {min(n_cells, pool_size)} candidates")
+        dev = self.device
+        if dev.type != "cuda":
+            raise NotImplementedError("TrainViews.batch_importance samples on the GPU: the views must be on a cuda device")
+        if weights.device != dev:
+            raise ValueError(f"weights are on {weights.device}, the views on {dev}")
+        weights = weights.contiguous()
+        n = k * s * s
+        f = dict(device=dev, dtype=torch.float32)
+        o = torch.empty((n, 3), **f)
+        d = torch.empty((n, 3), **f)
+        px = torch.empty((n, 3), **f)
+        ts = torch.empty((n, 1), **f)
+        bk = torch.empty((3,), **f)
+        idx = torch.empty((n, 3), device=dev, dtype=torch.int32) if return_indices else None
+        L = _lib.lib()
+        ws_bytes = int(L.ced_importance_batch_workspace_bytes(n_cells, pool_size, k))
+        if ws_bytes < 0:
+            raise ValueError(L.ced_last_error_string().decode())
+        ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.int32)
+        min_key = torch.empty((1,), device=dev, dtype=torch.int32)
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(dev):
+            rc = L.ced_sample_importance_batch(
+                self.model, self.n_views, self.width, self.height, self.channels, P(self.images), P(self.cameras),
+                P(self.timestamps), P(weights), s, pool_size, k, int(seed) % (1 << 64), int(step), BKGD_MODES[bkgd],
+                P(o), P(d), P(px), P(ts), P(bk), P(idx), P(min_key), P(ws), ws_bytes,
+                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "sample_importance_batch")
+        if int(min_key.item()) == 0:               # the smallest selected key: 0 = not a positive weight
+            raise ValueError(f"fewer than {k} candidates with a positive weight (step {step})")
         out = {"rays": Rays(origins=o, viewdirs=d), "pixels": px, "timestamps": ts, "color_bkgd": bk}
         if return_indices:
             out["indices"] = idx

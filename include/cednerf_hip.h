@@ -477,6 +477,48 @@ int ced_sample_training_batch(int32_t camera_model, int32_t n_views, int32_t wid
                               float *origins, float *viewdirs, float *pixels, float *timestamps, float *color_bkgd,
                               int32_t *indices, void *stream);
 
+/* Importance-sampled training batch (datasets/dnerf_3d_video_IS.py:401-440): num_cells cells of a weight map drawn
+ * without replacement, as torch.multinomial draws them (weight / Exp(1) variate, the num_cells largest), each cell
+ * expanded to its s x s pixels, s = weights_subsampled.
+ *   weights  float [n_views * (height / s) * (width / s)] (device), non-negative, any positive scale; cell index
+ *            (view * (height / s) + ysub) * (width / s) + xsub.  n_cells = that count, below 2^31.
+ *   Candidates: all n_cells cells (candidate j = cell j) when n_cells <= pool_size, else pool_size cells drawn uniformly
+ *            with replacement, c_j = (draw(j, 3) * n_cells) >> 32 (the draws of ced_sample_training_batch).
+ *   Key:     u = draw(j, 4), unit = ((u >> 9) * 2 + 1) * 2^-24, e = -det_logf(unit) (ced_common.hpp: every operation one
+ *            float32 rounding), key_j = weights[c_j] / e; a weight that is not a positive finite number gives key 0.
+ *   Select:  the num_cells largest keys as unsigned bit patterns, equal keys to the lower j; the selected candidates in
+ *            ascending j are i = 0 .. num_cells - 1.
+ *   Rays:    ray (ah * s + aw) * num_cells + i is pixel (xsub * s + aw, ysub * s + ah) of the cell's view; its ray,
+ *            colour (u8 / 255; channels must be 3), timestamp and the batch's background as ced_sample_training_batch.
+ * Writes num_cells * s * s rays to origins, viewdirs, pixels [n,3], timestamps [n], color_bkgd [3] and, if not NULL,
+ * indices int32 [n,3] = (view, x, y), and to min_key (device, one uint32) the bit pattern of the smallest selected key:
+ * 0 means that fewer than num_cells candidates had a positive key and the batch is not a valid draw (the caller's check;
+ * every write stays in bounds).  workspace: ced_importance_batch_workspace_bytes(n_cells, pool_size, num_cells) bytes of
+ * device scratch (-1 for sizes the sampler rejects), 16-byte aligned, contents unspecified.  Ten launches and a memset on
+ * the stream, no host synchronisation, no state kept between calls. */
+int64_t ced_importance_batch_workspace_bytes(int64_t n_cells, int64_t pool_size, int64_t num_cells);
+int ced_sample_importance_batch(int32_t camera_model, int32_t n_views, int32_t width, int32_t height, int32_t channels,
+                                const uint8_t *images, const float *cameras, const float *view_timestamps,
+                                const float *weights, int32_t weights_subsampled, int64_t pool_size, int64_t num_cells,
+                                uint64_t seed, int64_t step, int32_t bkgd_mode, float *origins, float *viewdirs,
+                                float *pixels, float *timestamps, float *color_bkgd, int32_t *indices, uint32_t *min_key,
+                                void *workspace, int64_t workspace_bytes, void *stream);
+
+/* DyNeRF's sampling-weight maps (datasets/dnerf_3d_video_IS.py:13-76, 187) from device-resident uint8 images
+ * [n_cameras, n_frames, height, width, 3], camera-major.  One launch each, no workspace, no host synchronisation.
+ * ced_temporal_median_u8: median uint8 [n_cameras, height, width, 3], per camera, pixel and channel the median over the
+ *   frames with torch.median's rule (the lower middle value for an even count).
+ * ced_isg_weights: weights float [n_cameras, n_frames, height, width] = dynerf_isg_weight in its order of roundings:
+ *   a = u8 / 255, m = median / 255, d = a - m, q = d * d, p = q / (q + gamma * gamma), (p0 + p1 + p2) * (1/3 in float).
+ * ced_ist_weights: dynerf_ist_weight_nice: per channel max over s = 1 .. frame_shift of |f[t + s] - f[t]| and
+ *   |f[t - s] - f[t]| on the 0 .. 255 values, a neighbour outside the clip being zero; (m0 + m1 + m2) / 3; max(., alpha). */
+int ced_temporal_median_u8(int32_t n_cameras, int32_t n_frames, int32_t height, int32_t width, const uint8_t *images,
+                           uint8_t *median, void *stream);
+int ced_isg_weights(int32_t n_cameras, int32_t n_frames, int32_t height, int32_t width, const uint8_t *images,
+                    const uint8_t *median, float gamma, float *weights, void *stream);
+int ced_ist_weights(int32_t n_cameras, int32_t n_frames, int32_t height, int32_t width, const uint8_t *images,
+                    float alpha, int32_t frame_shift, float *weights, void *stream);
+
 /* Optional per-iteration trace of ced_render_image_test (host struct, host arrays of `capacity`
  * entries, each may be NULL).  field_begin/field_end are caller-created hipEvent_t handles that the
  * renderer records on `stream` around the field-kernel launch of iteration i, so a benchmark can
