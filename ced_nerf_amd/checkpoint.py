@@ -177,6 +177,41 @@ def load_reference_checkpoint(path_or_state, radiance_field, estimator=None, *, 
         estimator.load_state_dict(occ, strict=False)
 
 
+def read_checkpoint(path, map_location="cpu") -> Dict:
+    """The dict of a `model.pth`: {"radiance_field": state dict, "occupancy_grid": state dict}.  weights_only: both this
+    package's files and the reference's hold tensors and python scalars only; a pickle's code is never run for them."""
+    ckpt = torch.load(path, map_location=map_location, weights_only=True)
+    if not isinstance(ckpt, dict) or "radiance_field" not in ckpt:
+        raise ValueError(f"{path}: not a model.pth (no 'radiance_field' entry)")
+    return ckpt
+
+
+def is_reference_state(state: Dict) -> bool:
+    """Whether a `radiance_field` state dict is the reference's (tiny-cuda-nn's flat `params`) and not this package's."""
+    return "hash_encoder.params" in state
+
+
+@torch.no_grad()
+def load_checkpoint(path_or_ckpt, radiance_field, estimator=None, *, assume_tcnn_layout: Optional[str] = None,
+                    map_location="cpu") -> None:
+    """train_real.py:524-529 for either kind of `model.pth`, into modules constructed with the run's flags.  A file
+    written by this package (`trainer.fit(save_path=...)`: the modules' own state dicts) loads as it is; the field must
+    have been built with the checkpoint's hash-table dtype.  A file of the reference goes through
+    `load_reference_checkpoint`, and needs `assume_tcnn_layout` for the reason given there."""
+    ckpt = path_or_ckpt if isinstance(path_or_ckpt, dict) else read_checkpoint(path_or_ckpt, map_location)
+    state = ckpt["radiance_field"]
+    if is_reference_state(state):
+        load_reference_checkpoint(ckpt, radiance_field, estimator, assume_tcnn_layout=assume_tcnn_layout)
+        return
+    if state["hash_table"].dtype != radiance_field.hash_table.dtype:
+        raise ValueError(f"the checkpoint's hash table is {state['hash_table'].dtype}, the module's "
+                         f"{radiance_field.hash_table.dtype}")
+    radiance_field.load_state_dict(state)
+    radiance_field.weights_changed()
+    if estimator is not None and "occupancy_grid" in ckpt:
+        estimator.load_state_dict(ckpt["occupancy_grid"])
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # A falsifiability gate for the layout hypothesis (tools/verify_checkpoint.py)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -7,12 +7,16 @@ learning-rate schedule and dynamic ray batch, and evaluates held-out views with 
 
     python -m ced_nerf_amd.trainer --data_root DATA --scene lego [-df -f -w -te -ta -o -d -wr -ae] [--max_steps N]
 
-trains a D-NeRF synthetic folder with the flags of opt.py and prints the reference's progress and evaluation lines.
+trains a scene folder with the flags of opt.py and prints the reference's progress and evaluation lines.  The scene
+name picks the loader and the preset (`scenes.preset_of`): D-NeRF synthetic, HyperNeRF (`vrig_chicken`, ...) or DyNeRF
+(`coffee_martini`, ...; importance-sampled by the folder's weight files or by maps computed on the device).
+`--load_model PATH` skips training; `--render_video DIR` writes the render path's frames as PNGs.
 """
 from __future__ import annotations
 
 import argparse
 import math
+import os
 import time
 from typing import Dict, Optional
 
@@ -210,17 +214,114 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
                 eval=result, evals=evals, config=cfg)
 
 
+def build_modules(cfg: Dict, device, *, use_div_offsets: bool = False, use_time_embedding: bool = False,
+                  use_time_attenuation: bool = False, use_feat_predict: bool = False, use_weight_predict: bool = False,
+                  hash_dtype: torch.dtype = torch.float16):
+    """(DNGPradianceField, OccGridEstimator) as train_real.py:185-187, 253-265 constructs them for a resolved config:
+    the modules a checkpoint of a run with these flags loads into (`checkpoint.load_checkpoint`)."""
+    from .model import DNGPradianceField
+    estimator = OccGridEstimator(cfg["aabb"], cfg["grid_resolution"], cfg["grid_levels"]).to(device)
+    field = DNGPradianceField(aabb=estimator.aabbs[-1].clone(), dst_resolution=cfg["hash_dst_resolution"],
+                              log2_hashmap_size=int(cfg["log2_hashmap_size"]), moving_step=cfg["moving_step"],
+                              use_div_offsets=use_div_offsets, use_time_embedding=use_time_embedding,
+                              use_time_attenuation=use_time_attenuation, use_feat_predict=use_feat_predict,
+                              use_weight_predict=use_weight_predict, hash_dtype=hash_dtype).to(device)
+    return field.eval(), estimator.eval()
+
+
+def load_scene(data_root: str, scene: str, kind: str, split: str, factor: Optional[int] = None, device="cuda",
+               read_image=None) -> TrainViews:
+    """One split of a scene folder through the loader of its dataset kind (`scenes.preset_of`)."""
+    if kind == "dnerf":
+        return TrainViews.from_dnerf_folder(data_root, scene, split, device=device)
+    extra = {} if factor is None else dict(factor=factor)
+    if kind == "hypernerf":
+        return TrainViews.from_hypernerf_folder(data_root, scene, split, device=device, read_image=read_image, **extra)
+    if kind == "dynerf":
+        return TrainViews.from_dynerf_folder(data_root, scene, split, device=device, read_image=read_image, **extra)
+    raise ValueError(f"dataset kind {kind!r}: one of {sorted(PRESETS)}")
+
+
+def dynerf_sampling(train: TrainViews, ist_from_step: Optional[int] = None, verbose: bool = True) -> Dict:
+    """fit's importance-sampling arguments for DyNeRF views: the folder's `isg_weights.pt` / `ist_weights.pt` with the
+    loader's `weights_subsampled` where they were shipped, otherwise `importance.isg_weights(views, n_cameras,
+    gamma=2e-2)` / `importance.ist_weights(views, n_cameras)` computed on the device at the loaded resolution
+    (weights_subsampled = 1).  The IST map is only needed with `ist_from_step`."""
+    from . import importance
+    if hasattr(train, "isg_weights"):
+        out = dict(sampling_weights=train.isg_weights, weights_subsampled=train.weights_subsampled)
+        source = f"isg_weights.pt ({train.isg_weights.numel()} cells, weights_subsampled={train.weights_subsampled})"
+    else:
+        out = dict(sampling_weights=importance.isg_weights(train, train.n_cameras, gamma=2e-2).reshape(-1),
+                   weights_subsampled=1)
+        source = f"computed on the device ({out['sampling_weights'].numel()} cells, gamma=2e-2, weights_subsampled=1)"
+    if verbose:
+        print(f"ISG sampling weights: {source}", flush=True)
+    if ist_from_step is not None:
+        if hasattr(train, "ist_weights") and hasattr(train, "isg_weights"):
+            ist, source = train.ist_weights, "ist_weights.pt"
+        elif hasattr(train, "isg_weights"):
+            raise ValueError("the folder ships isg_weights.pt without ist_weights.pt: --ist_from_step needs both maps "
+                             "at one resolution")
+        else:
+            ist, source = importance.ist_weights(train, train.n_cameras).reshape(-1), "computed on the device"
+        out.update(ist_weights=ist, ist_from_step=int(ist_from_step))
+        if verbose:
+            print(f"IST sampling weights from step {ist_from_step}: {source}", flush=True)
+    return out
+
+
+def write_video_frames(out_dir: str, inference, estimator, cfg: Dict, test: TrainViews, kind: str,
+                       n_frames: Optional[int] = None) -> int:
+    """train_real.py:531-558 up to the encoder: renders DyNeRF's spiral path (`render_poses`) or, for the other two
+    kinds, the test views' cameras at their times with `video.render_video` on black with 1024 samples per ray, and
+    writes `rgb_%04d.png` / `depth_%04d.png` (8-bit normalised depth) into `out_dir`.  Returns the frame count."""
+    from .video import render_video
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("--render_video writes PNGs with PIL (Pillow), which is not installed") from e
+    dev = test.device
+    if kind == "dynerf":
+        total = len(test.render_poses)
+        rays_of = lambda i: test.render_path_rays(i)[0]
+        time_of = lambda i: torch.full((1, 1), float(i) / total, device=dev, dtype=torch.float32)
+    else:
+        total = len(test)
+        rays_of = test.view_rays
+        time_of = lambda i: test.timestamps[i].reshape(1, 1)
+    n = total if n_frames is None else max(0, min(int(n_frames), total))
+    render = dict(near_plane=cfg["near_plane"], far_plane=cfg["far_plane"], render_step_size=cfg["render_step_size"],
+                  cone_angle=cfg["cone_angle"], alpha_thre=cfg["alpha_thre"], render_bkgd=torch.zeros(3, device=dev))
+    frames = render_video(inference, estimator, rays_of, time_of, n, max_samples=1024, render_kwargs=render,
+                          to_host=True)
+    os.makedirs(out_dir, exist_ok=True)
+    for i, frame in enumerate(frames):
+        Image.fromarray(frame["rgb"]).save(os.path.join(out_dir, f"rgb_{i:04d}.png"))
+        Image.fromarray(frame["depth"]).save(os.path.join(out_dir, f"depth_{i:04d}.png"))
+    return len(frames)
+
+
 def main(argv=None) -> int:
-    """CLI over a D-NeRF synthetic folder, with the flag names of opt.py."""
-    p = argparse.ArgumentParser(description="Train a D-NeRF synthetic scene (train_real.py's loop)")
+    """CLI over a D-NeRF synthetic, HyperNeRF or DyNeRF scene folder, with the flag names of opt.py."""
+    from . import checkpoint, scenes
+    p = argparse.ArgumentParser(description="Train a D-NeRF synthetic, HyperNeRF or DyNeRF scene (train_real.py's loop)")
     p.add_argument("--data_root", required=True)
     p.add_argument("--scene", required=True)
+    p.add_argument("--dataset", default="auto", choices=["auto", "dnerf", "hypernerf", "dynerf"],
+                   help="the folder's kind; auto looks the scene name up in the reference's scene tables")
+    p.add_argument("--factor", type=int, default=None, help="image downscale (default 2 for HyperNeRF, 4 for DyNeRF)")
     p.add_argument("--train_split", default="train", choices=["train", "trainval"])
     p.add_argument("--test_split", default="test")
     p.add_argument("--max_steps", type=int, default=None)
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--log2_hashmap_size", type=int, default=21)
     p.add_argument("--save_path", default=None)
+    p.add_argument("--load_model", default=None, metavar="PATH", help="skip training and load this model.pth")
+    p.add_argument("--assume_tcnn_layout", default=None, help="for a --load_model file written by the reference")
+    p.add_argument("--render_video", default=None, metavar="DIR", help="write rgb_%%04d.png / depth_%%04d.png here")
+    p.add_argument("--video_frames", type=int, default=None, help="render only the first N frames of the path")
+    p.add_argument("--ist_from_step", type=int, default=None, help="DyNeRF: sample by the IST map from this step on")
     p.add_argument("-df", "--use_div_offsets", action="store_true")
     p.add_argument("-f", "--use_feat_predict", action="store_true")
     p.add_argument("-w", "--use_weight_predict", action="store_true")
@@ -232,15 +333,44 @@ def main(argv=None) -> int:
     p.add_argument("-wr", "--weight_rgbper", action="store_true")
     p.add_argument("-ae", "--acc_entorpy_loss", action="store_true")
     a = p.parse_args(argv)
-    train = TrainViews.from_dnerf_folder(a.data_root, a.scene, a.train_split)
-    test = TrainViews.from_dnerf_folder(a.data_root, a.scene, a.test_split)
+    if a.dataset != "auto":
+        kind = a.dataset
+    else:
+        try:
+            kind = scenes.preset_of(a.scene)
+        except ValueError:
+            # a D-NeRF-layout folder under a name of its own trains as before
+            if not os.path.exists(os.path.join(a.data_root, a.scene, f"transforms_{a.train_split}.json")):
+                raise
+            kind = "dnerf"
+    if a.ist_from_step is not None and kind != "dynerf":
+        p.error("--ist_from_step belongs to DyNeRF's importance sampling")
+    train_split, test_split = (a.train_split, a.test_split) if kind == "dnerf" else ("train", "test")
     extra = {} if a.moving_step is None else dict(moving_step=a.moving_step)
-    log_every = 10000 if a.max_steps is None else max(1, min(10000, a.max_steps))
-    fit(train, test, preset="dnerf", max_steps=a.max_steps, seed=a.seed, use_div_offsets=a.use_div_offsets,
-        use_time_embedding=a.use_time_embedding, use_time_attenuation=a.use_time_attenuation,
-        use_feat_predict=a.use_feat_predict, use_weight_predict=a.use_weight_predict, distortion_loss=a.distortion_loss,
-        acc_entropy_loss=a.acc_entorpy_loss, opacity_loss=a.use_opacity_loss, weight_rgbper=a.weight_rgbper,
-        log_every=log_every, save_path=a.save_path, log2_hashmap_size=a.log2_hashmap_size, **extra)
+    extra["log2_hashmap_size"] = a.log2_hashmap_size
+    flags = dict(use_div_offsets=a.use_div_offsets, use_time_embedding=a.use_time_embedding,
+                 use_time_attenuation=a.use_time_attenuation, use_feat_predict=a.use_feat_predict,
+                 use_weight_predict=a.use_weight_predict)
+    test = load_scene(a.data_root, a.scene, kind, test_split, a.factor)
+    if a.load_model:                             # train_real.py:189-190, 524-529: no training set, no loop
+        cfg = resolve_config(kind, a.max_steps, **extra)
+        ckpt = checkpoint.read_checkpoint(a.load_model)
+        state = ckpt["radiance_field"]
+        dtype = torch.float16 if checkpoint.is_reference_state(state) else state["hash_table"].dtype
+        inference, estimator = build_modules(cfg, test.device, hash_dtype=dtype, **flags)
+        checkpoint.load_checkpoint(ckpt, inference, estimator, assume_tcnn_layout=a.assume_tcnn_layout)
+        print(f"loaded {a.load_model}", flush=True)
+    else:
+        train = load_scene(a.data_root, a.scene, kind, train_split, a.factor)
+        sampling = dynerf_sampling(train, a.ist_from_step) if kind == "dynerf" else {}
+        log_every = 10000 if a.max_steps is None else max(1, min(10000, a.max_steps))
+        res = fit(train, test, preset=kind, max_steps=a.max_steps, seed=a.seed, distortion_loss=a.distortion_loss,
+                  acc_entropy_loss=a.acc_entorpy_loss, opacity_loss=a.use_opacity_loss, weight_rgbper=a.weight_rgbper,
+                  log_every=log_every, save_path=a.save_path, **flags, **sampling, **extra)
+        inference, estimator, cfg = res["inference"], res["estimator"], res["config"]
+    if a.render_video:
+        n = write_video_frames(a.render_video, inference.eval(), estimator.eval(), cfg, test, kind, a.video_frames)
+        print(f"wrote {n} rgb and depth frames to {a.render_video}", flush=True)
     return 0
 
 

@@ -9,18 +9,21 @@ blocks and timestamps kept on the device, with no host work and no upload per st
 The sampler's random numbers are a pure function of (seed, step, ray, draw); `draws` below restates them in numpy,
 bit for bit ("Training batches").  `TrainViews.batch_importance` is DyNeRF's importance-sampled batch
 (datasets/dnerf_3d_video_IS.py:401-440) on the same draws, restated by `importance_draws`.
+
+Views come from arrays (`TrainViews.pinhole`, `TrainViews.hypercam`) or from the reference's scene folders
+(`from_dnerf_folder`, `from_hypernerf_folder`, `from_dynerf_folder`; the conventions are `scenes.py`'s).
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
 import os
-from typing import Dict, Iterator, Optional, Sequence
+from typing import Callable, Dict, Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, scenes
 from .utils import Rays
 
 CAMERA_PINHOLE, CAMERA_HYPERCAM = 0, 1                  # CED_CAMERA_*
@@ -307,6 +310,161 @@ class TrainViews:
                           device=device)
         out.focal = float(focal)
         return out
+
+    @staticmethod
+    def _image_reader(read_image: Optional[Callable[[str], np.ndarray]], who: str) -> Callable[[str], np.ndarray]:
+        """The `read_image` hook of the folder loaders: path -> uint8 [H,W,3].  None reads with PIL."""
+        if read_image is not None:
+            return read_image
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise ImportError(f"TrainViews.{who} reads PNGs with PIL (Pillow), which is not installed") from e
+
+        def read(path: str) -> np.ndarray:
+            with Image.open(path) as im:
+                return np.asarray(im.convert("RGB"), np.uint8)
+        return read
+
+    @staticmethod
+    def _read_rgb(read: Callable[[str], np.ndarray], path: str) -> np.ndarray:
+        img = np.asarray(read(path))
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[-1] != 3:
+            raise ValueError(f"{path}: expected a uint8 [H,W,3] image, got {img.shape} {img.dtype}")
+        return img
+
+    @classmethod
+    def from_hypernerf_folder(cls, root: str, scene: str, split: str = "train", factor: int = 2, device="cuda",
+                              read_image: Optional[Callable[[str], np.ndarray]] = None) -> "TrainViews":
+        """A HyperNeRF capture (hypernerf.py:84-156, 184-268, 331-352) in `root/scene/<scene without its interp_ /
+        misc_ / vrig_ prefix>`: `scene.json` (near, far, scale, center), `metadata.json` (camera_id, time_id per image
+        id), `dataset.json` (ids, train_ids, val_ids), `camera/{id}.json` and `rgb/{factor}x/{id}.png`.  The split is
+        `scenes.hypernerf_split`, every camera `scenes.scale_hyper_camera(json, 1 / factor, center, scale)`, a view's
+        time its time_id / the largest time_id of all ids; one view per step.  ValueError naming the file when an
+        image's size is not its scaled camera's (the reference's assertion, hypernerf.py:393-394).
+
+        `read_image` (the reference's `read_image` switch as a hook): a callable path -> uint8 [H,W,3] used instead of
+        PIL.  Attributes besides `TrainViews.hypercam`'s: `near`, `far`, `ids` (of the split) and `camera_ids`."""
+        if split not in ("train", "test"):
+            raise ValueError(f"split={split!r}: 'train' or 'test'")
+        read = cls._image_reader(read_image, "from_hypernerf_folder")
+        data_dir = os.path.join(root, scene, scenes.hypernerf_subfolder(scene))
+        loaded = {}
+        for name in ("scene", "metadata", "dataset"):
+            with open(os.path.join(data_dir, name + ".json")) as fp:
+                loaded[name] = json.load(fp)
+        scene_json, meta, dataset = loaded["scene"], loaded["metadata"], loaded["dataset"]
+        ids = list(dataset["ids"])
+        train, test = scenes.hypernerf_split(ids, dataset.get("train_ids"), dataset.get("val_ids"))
+        max_time = max(meta[i]["time_id"] for i in ids)
+        images, cams, times, kept = [], [], [], []
+        for k in (train if split == "train" else test):
+            name = ids[k]
+            with open(os.path.join(data_dir, "camera", f"{name}.json")) as fp:
+                cam = scenes.scale_hyper_camera(json.load(fp), 1.0 / factor, scene_json["center"], scene_json["scale"])
+            path = os.path.join(data_dir, "rgb", f"{int(factor)}x", f"{name}.png")
+            img = cls._read_rgb(read, path)
+            if (img.shape[1], img.shape[0]) != tuple(cam["image_size"]):
+                raise ValueError(f"{path}: the image is {img.shape[1]} x {img.shape[0]}, its camera at 1/{factor} "
+                                 f"{cam['image_size'][0]} x {cam['image_size'][1]}")
+            if images and img.shape != images[0].shape:
+                raise ValueError(f"{path}: the image is {img.shape[1]} x {img.shape[0]}, the views before it "
+                                 f"{images[0].shape[1]} x {images[0].shape[0]}")
+            images.append(img)
+            cams.append(cam)
+            times.append(meta[name]["time_id"] / max_time)
+            kept.append(name)
+        if not images:
+            raise ValueError(f"{data_dir}: the {split} split is empty")
+        out = cls.hypercam(np.stack(images, axis=0), cams, np.asarray(times, np.float32), device=device,
+                           view_mode="one_per_step")
+        out.near, out.far = float(scene_json["near"]), float(scene_json["far"])
+        out.ids = kept
+        out.camera_ids = [meta[name]["camera_id"] for name in kept]
+        return out
+
+    @classmethod
+    def from_dynerf_folder(cls, root: str, scene: str, split: str = "train", factor: int = 4,
+                           load_every: Optional[int] = None, device="cuda",
+                           read_image: Optional[Callable[[str], np.ndarray]] = None) -> "TrainViews":
+        """A DyNeRF (Plenoptic Video) scene folder `root/scene` (dnerf_3d_video_IS.py:78-198, 245-306):
+        `poses_bounds.npy` and `images_x{factor}_list.json`, whose "videos" each list "images" with "path" (below the
+        folder), "idx", "height" and the width under the reference's key "weight".  Poses: `scenes.dynerf_poses` (the
+        h/w/focal column from the json and focal / factor, `correct_poses_bounds`, the 300-frame spiral, axes flipped,
+        x 0.4, + (0, 0, 1.5)).  train = videos [1:] with every frame, test = video [0] with every 10th; `load_every`
+        overrides both strides.  A frame's time is its idx / (frames of its video - 1).  `flame_salmon_k` reads frames
+        [(k - 1) * 300, k * 300) of the folder `flame_salmon_1`, with the idx the json gives them.  OpenCV pinhole
+        cameras K = [[f, 0, W/2], [0, f, H/2], [0, 0, 1]], one view per step, views camera-major (all frames of a
+        camera, then the next camera), which is what `importance.isg_weights(views, n_cameras)` assumes.
+
+        Attributes besides `TrainViews.pinhole`'s: `n_cameras`, `frames_per_camera` (views loaded per camera), `focal`,
+        `render_poses` (float32 [300,3,4], see `render_path_rays`), `weights_subsampled` = int(4 / factor) (the weight
+        files are made at factor 4), and `isg_weights` / `ist_weights` (flat float32 tensors on `device`) when
+        `isg_weights.pt` / `ist_weights.pt` lie in the folder.  The reference loads isg_weights.pt under both names
+        (dnerf_3d_video_IS.py:270-271); here each file is loaded under its own name."""
+        if split not in ("train", "test"):
+            raise ValueError(f"split={split!r}: 'train' or 'test'")
+        stride = int(load_every) if load_every is not None else (1 if split == "train" else 10)
+        if stride < 1:
+            raise ValueError(f"load_every must be >= 1, got {load_every}")
+        read = cls._image_reader(read_image, "from_dynerf_folder")
+        folder, frame_range = scenes.dynerf_folder_and_frames(scene)
+        data_dir = os.path.join(root, folder)
+        poses_bounds = np.load(os.path.join(data_dir, "poses_bounds.npy"))
+        list_path = os.path.join(data_dir, f"images_x{int(factor)}_list.json")
+        with open(list_path) as fp:
+            videos = json.load(fp)["videos"]
+        if len(videos) != poses_bounds.shape[0]:
+            raise ValueError(f"{list_path}: {len(videos)} videos for {poses_bounds.shape[0]} poses")
+        first = videos[0]["images"][0]
+        height, width = int(first["height"]), int(first["weight"])
+        poses, render_poses, focal = scenes.dynerf_poses(poses_bounds, height, width, factor)
+        cameras = list(range(1, len(videos))) if split == "train" else [0]
+        if not cameras:
+            raise ValueError(f"{list_path}: the {split} split has no video")
+        images, c2ws, times, per_camera = None, [], [], None
+        for cam in cameras:
+            frames = videos[cam]["images"]
+            if frame_range is not None:
+                frames = frames[frame_range[0]:frame_range[1]]
+            chosen = frames[::stride]
+            if per_camera is None:
+                per_camera = len(chosen)
+                images = np.empty((len(cameras) * per_camera, height, width, 3), np.uint8)
+            if len(chosen) != per_camera or per_camera == 0:
+                raise ValueError(f"{list_path}: video {cam} gives {len(chosen)} frames, the first one {per_camera}")
+            for frame in chosen:
+                path = os.path.join(data_dir, frame["path"])
+                img = cls._read_rgb(read, path)
+                if img.shape[:2] != (height, width):
+                    raise ValueError(f"{path}: the image is {img.shape[1]} x {img.shape[0]}, the list says "
+                                     f"{width} x {height}")
+                images[len(times)] = img
+                times.append(frame["idx"] / max(len(frames) - 1, 1))
+                c2ws.append(poses[cam])
+        K = np.array([[focal, 0, width / 2.0], [0, focal, height / 2.0], [0, 0, 1]], np.float32)
+        out = cls.pinhole(images, K, np.asarray(c2ws, np.float32), np.asarray(times, np.float32), opengl=False,
+                          device=device, view_mode="one_per_step")
+        out.focal = float(focal)
+        out.n_cameras, out.frames_per_camera = len(cameras), per_camera
+        out.render_poses = render_poses.astype(np.float32)
+        out.weights_subsampled = int(4 / factor)
+        for name in ("isg_weights", "ist_weights"):
+            path = os.path.join(data_dir, name + ".pt")
+            if os.path.exists(path):
+                w = torch.load(path, map_location="cpu", weights_only=True)
+                setattr(out, name, w.to(device=out.device, dtype=torch.float32).reshape(-1).contiguous())
+        return out
+
+    def render_path_rays(self, i: int) -> Tuple[Rays, torch.Tensor]:
+        """Frame i of the render path of a DyNeRF scene (dnerf_3d_video_IS.py:328-371): (Rays [H,W,3] of
+        `render_poses[i]` through `cameras.pinhole_rays`, timestamps [1,1] = i / number of poses)."""
+        from . import cameras
+        poses = getattr(self, "render_poses", None)
+        if poses is None:
+            raise ValueError("these views have no render path (TrainViews.from_dynerf_folder sets render_poses)")
+        rays = cameras.pinhole_rays(self.K[0], poses[i], self.width, self.height, opengl=self.opengl, device=self.device)
+        return rays, torch.full((1, 1), float(i) / len(poses), device=self.device, dtype=torch.float32)
 
     # -- sampling -----------------------------------------------------------------------------------------------------
     def batch(self, num_rays: int, step: int, bkgd: str = "white", view_mode: Optional[str] = None, seed: int = 0,
