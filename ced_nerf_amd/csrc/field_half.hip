@@ -31,35 +31,6 @@
 
 namespace ced {
 
-// packed blob, in fragments: layer l = [nb][ks] fragments; a second plane of the same shape holds the
-// low parts in F16X2 mode
-template <bool TE> struct HalfBlob {
-    static constexpr int KS_B0 = TE ? 2 : 1;
-    static constexpr int M0 = 0;
-    static constexpr int M1 = M0 + 4 * 1;
-    static constexpr int M2 = M1 + 4 * 2;
-    static constexpr int M3 = M2 + 4 * 2;
-    static constexpr int B0 = M3 + 1 * 2;
-    static constexpr int B1 = B0 + 4 * KS_B0;
-    static constexpr int H0 = B1 + 1 * 2;
-    static constexpr int H1 = H0 + 4 * 1;
-    static constexpr int H2 = H1 + 4 * 2;
-    static constexpr int FRAGS = H2 + 1 * 2;       // 42 / 46
-};
-
-// Which kernels run their hidden layers on the single 16x16x32 instruction (field_half_device.hpp: mfma_k32): f16x2
-// without a time encoding on a plain (not temporal) table, the 1024-thread kernels of launch_field_half, whose four
-// waves per SIMD hold all of its registers (residency gate: ced_nerf_amd/_k32_gate.py).  The host side of the same
-// choice is half_layout_k32: those kernels need the weights packed with the K = 32 placements.
-constexpr bool half_kernel_k32(bool te, bool temporal, bool split, int threads)
-{
-    return split && !te && !temporal && threads == 1024;
-}
-static bool half_layout_k32(int time_mode, int precision, int temporal)
-{
-    return half_kernel_k32(time_mode != 0, temporal != 0, precision == CED_MLP_F16X2, 1024);
-}
-
 template <bool TE, bool F16, bool TEMPORAL, bool SPLIT, int NT, int THREADS>
 __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
 {

@@ -1,0 +1,609 @@
+// The deformation field on its own: DNGPradianceField.query_move (cednerf/model.py:354-365) with the normalisation that
+// follows it (:378-383), and DNGPradianceField._query_rgb (:447-466).  Inside the fused field kernels the move vector and
+// the head's input only ever live in registers; these entries hand them out (ced_field_move, ced_field_move_rays) and
+// take the head's input from memory (ced_field_rgb).
+//
+// They are built from the fused kernels' own device code -- mlp_layer / to_operand (field_kernel.hpp), mlp_layer_h /
+// to_operand_h / to_half8 (field_half_device.hpp), the deterministic transcendentals of ced_common.hpp -- on the same
+// packed blob read at the same offsets, in the arithmetic the descriptor's mlp_precision selects for that network:
+//   motion network  f32, f32+h16x2: fp32 MFMA chain      f16: fp16 operands      f16x2: split fp16
+//   colour head     f32: fp32 MFMA chain      f16: fp16 operands      f16x2, f32+h16x2: split fp16
+// so a value computed here is the value the fused kernel computes internally, bit for bit.  Where the fused f16x2 kernel
+// runs its hidden layers on the K-doubled v_mfma_f32_16x16x32_f16 (half_kernel_k32; the blob then carries the K = 32
+// placements) these kernels evaluate that instruction's four blocks of eight products, in its order, on two
+// v_mfma_f32_16x16x16_f16 (mlp_layer_k32_blocks below): the K-doubled instruction stays confined to the two fused kernels
+// that hold their SIMDs alone, and these short kernels need no residency rule.
+//
+// Shape: one network per 32-sample wave tile, workgroups persistent over tiles (wave w of workgroup b takes tiles
+// b * WAVES + w, + gridDim.x * WAVES, ...).  Only that network's layers are staged into LDS (motion: 44 KB fp32 or split
+// fp16, 22 KB fp16; head: 28 KB / 14 KB), not the fused kernel's 86 KB, so two 512-thread workgroups share a CU.
+#include "ced_common.hpp"
+#include "field_device.hpp"
+#include "field_half_device.hpp"
+#include "field_kernel.hpp"
+
+namespace ced {
+
+struct MoveArgs {
+    int64_t n;
+    const int64_t *n_dev;                             // optional device-side sample count (<= n)
+    const float *pos, *t;                             // explicit mode
+    const float *rays_o, *rays_d;                     // rays mode
+    const int64_t *ray_idx;
+    const float *t0, *t1, *timestamps;
+    int rays_mode, t_per_ray;
+    float *x_move, *move, *x_norm;                    // [n,3] each, any may be null
+    uint8_t *selector;                                // [n], may be null
+    float aabb[6];
+    float moving_step;
+    int use_div;
+    const void *weights;                              // the motion network's first layer inside the packed blob
+    int64_t lo_halves;                                // f16x2: halves from the plane of high parts to the plane of remainders
+};
+
+struct RgbArgs {
+    int64_t n;
+    const float *dir, *geo;                           // [n,3], [n,15]
+    int apply_act;
+    float *rgb;                                       // [n,3]
+    const void *weights;                              // the head's first layer inside the packed blob
+    int64_t lo_halves;
+};
+
+static_assert(HalfBlob<true>::B0 == HalfBlob<false>::B0 && Blob<true>::B0 == Blob<false>::B0,
+              "the motion network sits at the start of the blob with or without a time encoding");
+constexpr int kMotionFloats = Blob<false>::B0;                                  // fp32 layers M0..M3
+constexpr int kMotionHalves = HalfBlob<false>::B0 * kFragHalves;                // the same as fp16 fragments, one plane
+constexpr int kHeadFloats = Blob<false>::TOTAL - Blob<false>::H0;               // fp32 layers H0..H2
+constexpr int kHeadHalves = Blob<false>::HEAD_FRAGS * kFragHalves;
+static_assert(HalfBlob<false>::FRAGS - HalfBlob<false>::H0 == Blob<false>::HEAD_FRAGS &&
+              HalfBlob<false>::H1 - HalfBlob<false>::H0 == Blob<false>::HF_H1 &&
+              HalfBlob<false>::H2 - HalfBlob<false>::H0 == Blob<false>::HF_H2,
+              "the head's fragments are laid out alike in the half blobs and in the mixed blob");
+
+// `count` 16-byte words of weights into LDS
+template <int THREADS> __device__ __forceinline__ void stage(void *dst, const void *src, int count, int tid)
+{
+    const f4 *s = reinterpret_cast<const f4 *>(src);
+    f4 *d = reinterpret_cast<f4 *>(dst);
+    for (int i = tid; i < count; i += THREADS) d[i] = s[i];
+}
+
+__device__ __forceinline__ int64_t sample_count(int64_t n, const int64_t *n_dev)
+{
+    if (!n_dev) return n;
+    const int64_t nd = *n_dev;
+    return nd < n ? nd : n;
+}
+
+// Position and time of sample c of each 16-sample column tile: the expressions of field_kernel.hpp / field_half.hip
+// (rays mode: o + (d * (t0 + t1)) / 2 in fp32; a negative ray index is evaluated on ray 0 at distance 0).  A ragged last
+// tile repeats the last sample (never stored).
+template <int NT>
+__device__ __forceinline__ void load_samples(const MoveArgs &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[NT][3],
+                                             float (&tq)[NT])
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        int64_t s = tile_base + 16 * j + c;
+        s = s < n_eff ? s : n_eff - 1;
+        if (A.rays_mode) {
+            const int64_t r_in = A.ray_idx[s];
+            const bool used = r_in >= 0;
+            const int64_t r = used ? r_in : 0;
+            const float tm2 = used ? A.t0[s] + A.t1[s] : 0.0f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) px[j][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
+            tq[j] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
+        } else {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) px[j][a] = A.pos[3 * s + a];
+            tq[j] = A.t[s];
+        }
+    }
+}
+
+// query_move / normalise / selector (model.py:354-383) from the motion network's accumulators (rows natural: row a on
+// lane group 0 register a; rows 3,4,5 on (g0,r3), (g1,r0), (g1,r1)), as the fused kernels state it -- except that x_norm
+// leaves unclamped, as the reference returns it.  Lane group a < 3 stores component a, lane group 3 the selector.
+template <int NT>
+__device__ __forceinline__ void move_store(const MoveArgs &A, const f4 (&D)[NT][4], const float (&px)[NT][3], int64_t tile_base,
+                                           int64_t n_eff, int g, int c)
+{
+    const float extent[3] = { A.aabb[3] - A.aabb[0], A.aabb[4] - A.aabb[1], A.aabb[5] - A.aabb[2] };
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        float mv[3], xm[3], xn[3];
+        bool inside = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float off = __shfl(D[j][0][a], c, 64);
+            float m = off * A.moving_step;
+            if (A.use_div) {
+                constexpr int kFineReg[3] = { 3, 0, 1 };
+                const float fine = __shfl(D[j][0][kFineReg[a]], (a == 0) ? c : 16 + c, 64);
+                const float e = det_expf(2.0f * fine);
+                const float th = 1.0f - 2.0f / (e + 1.0f);
+                m = m + th * A.moving_step;
+            }
+            mv[a] = m;
+            xm[a] = px[j][a] + m;
+            const float x = (xm[a] - A.aabb[a]) / extent[a];
+            inside = inside && (x > 0.0f && x < 1.0f);
+            xn[a] = x;
+        }
+        const int64_t s = tile_base + 16 * j + c;
+        if (s >= n_eff) continue;
+        if (g == 3) {
+            if (A.selector) A.selector[s] = inside ? 1 : 0;
+            continue;
+        }
+        const float o_move = (g == 0) ? mv[0] : (g == 1) ? mv[1] : mv[2];
+        const float o_xm = (g == 0) ? xm[0] : (g == 1) ? xm[1] : xm[2];
+        const float o_xn = (g == 0) ? xn[0] : (g == 1) ? xn[1] : xn[2];
+        if (A.move) A.move[3 * s + g] = o_move;
+        if (A.x_move) A.x_move[3 * s + g] = o_xm;
+        if (A.x_norm) A.x_norm[3 * s + g] = o_xn;
+    }
+}
+
+// ---- a K = 32 layer without the K-doubled instruction --------------------------------------------------------------
+// v_mfma_f32_16x16x32_f16 consumes lane group q's eight operand elements as block q of eight products, q = 0..3, each
+// block rounded once onto the accumulator; v_mfma_f32_16x16x16_f16 consumes lane groups {0,1}, then {2,3}, four elements
+// each, as two such blocks; the order of the products inside a block is irrelevant (oracle/mfma_f16_model.h).  So one
+// K = 32 instruction on operands (a, b) IS two K = 16 instructions on regrouped operands: the first takes from lane group
+// G the elements 4(G&1) .. 4(G&1)+3 of K = 32 lane group G>>1 (its blocks: K = 32 blocks 0, 1), the second the same of lane
+// group 2 + (G>>1) (blocks 2, 3).  The weights are read from LDS at the regrouped address, the activations are regrouped
+// across lanes once per layer.  Same blocks, same order, same bits as mlp_layer_h<..., K32 = true> on the K = 32 blob.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void regroup_k32(const h8 &b, int src_lane, bool upper, h4 &b01, h4 &b23)
+{
+    const u32x4 w = __builtin_bit_cast(u32x4, b);
+    uint32_t x01[4], x23[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        x01[k] = (uint32_t)__shfl((int)w[k], src_lane, 64);
+        x23[k] = (uint32_t)__shfl((int)w[k], src_lane + 32, 64);
+    }
+    b01 = __builtin_bit_cast(h4, u32x2{ upper ? x01[2] : x01[0], upper ? x01[3] : x01[1] });
+    b23 = __builtin_bit_cast(h4, u32x2{ upper ? x23[2] : x23[0], upper ? x23[3] : x23[1] });
+}
+
+template <int KS, int NB, int NT>
+__device__ __forceinline__ void mlp_layer_k32_blocks(const _Float16 *__restrict__ whi, const _Float16 *__restrict__ wlo, int lane,
+                                                     const h8 (&Bh)[NT][2], const h8 (&Bl)[NT][2], f4 (&D)[NT][4])
+{
+    const int g = lane >> 4, c = lane & 15;
+    const int src_lane = 16 * (g >> 1) + c;               // the K = 32 lane whose elements this lane feeds to blocks 0 / 1
+    const bool upper = (g & 1) != 0;
+    const int a01 = src_lane * 8 + (upper ? 4 : 0), a23 = a01 + 32 * 8;
+    h4 bh01[NT][KS], bh23[NT][KS], bl01[NT][KS], bl23[NT][KS];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            regroup_k32(Bh[j][ks], src_lane, upper, bh01[j][ks], bh23[j][ks]);
+            regroup_k32(Bl[j][ks], src_lane, upper, bl01[j][ks], bl23[j][ks]);
+        }
+    }
+    f4 acc[NT];
+#pragma unroll
+    for (int grp = 0; grp < NB * KS; ++grp) {
+        const int nb = grp / KS, ks = grp % KS;
+        if (ks == 0) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[j] = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
+        }
+        const h4 ah01 = *reinterpret_cast<const h4 *>(whi + grp * kFragHalves + a01);
+        const h4 ah23 = *reinterpret_cast<const h4 *>(whi + grp * kFragHalves + a23);
+        const h4 al01 = *reinterpret_cast<const h4 *>(wlo + grp * kFragHalves + a01);
+        const h4 al23 = *reinterpret_cast<const h4 *>(wlo + grp * kFragHalves + a23);
+        // the three products of the split, in mlp_layer_h's order: lo * hi, hi * lo, hi * hi
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(al01, bh01[j][ks], acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(al23, bh23[j][ks], acc[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah01, bl01[j][ks], acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah23, bl23[j][ks], acc[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah01, bh01[j][ks], acc[j], 0, 0, 0);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah23, bh23[j][ks], acc[j], 0, 0, 0);
+        }
+        if (ks == KS - 1) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) D[j][nb] = acc[j];
+        }
+    }
+}
+
+// a layer fed by a hidden layer: on the pair form, or (K32L: the blob has the K = 32 placements) on that form's blocks
+template <int KS, int NB, int NT, bool SPLIT, bool K32L>
+__device__ __forceinline__ void hidden_fed_layer(const _Float16 *__restrict__ whi, const _Float16 *__restrict__ wlo, int lane,
+                                                 const h8 (&Bh)[NT][2], const h8 (&Bl)[NT][2], f4 (&D)[NT][4])
+{
+    if constexpr (K32L) mlp_layer_k32_blocks<KS, NB, NT>(whi, wlo, lane, Bh, Bl, D);
+    else mlp_layer_h<KS, NB, NT, SPLIT>(whi, wlo, lane, Bh, Bl, D);
+}
+
+// ---- motion network, fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2) ------------------------------------------
+template <int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void move_kernel(MoveArgs A)
+{
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    using BL = Blob<false>;
+    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_eff = sample_count(A.n, A.n_dev);
+    const int64_t n_tiles = (n_eff + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
+    __syncthreads();
+
+    // eval frames: one timestamp for every sample, its two Frequency features of this lane computed once (field_kernel.hpp)
+    const bool shared_time = A.rays_mode && !A.t_per_ray;
+    float t_feat[2] = { 0.0f, 0.0f };
+    if (shared_time) {
+        const float t_all = A.timestamps[0];
+#pragma unroll
+        for (int S = 6; S < 8; ++S) t_feat[S - 6] = det_sinpi_phase(t_all * (float)(1 << (2 * (S & 1) + (g >> 1))), g & 1);
+    }
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
+        int lds_off = 0;
+        asm volatile("" : "+v"(lds_off));
+        const float *const lw = lds + lds_off;
+        float px[NT][3], tq[NT];
+        load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
+
+        float B[NT][16];
+        f4 D[NT][4];
+        // tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const bool odd = (g & 1) != 0;
+            const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
+            const float vxy = odd ? px[j][1] : px[j][0];
+            float p0, p1;
+            det_sinpi_both(vxy * sc0, p0, p1);
+            auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+            B[j][0] = __uint_as_float(sw[0]); B[j][2] = __uint_as_float(sw[1]);
+            det_sinpi_both(vxy * sc1, p0, p1);
+            sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+            B[j][1] = __uint_as_float(sw[0]); B[j][3] = __uint_as_float(sw[1]);
+            const float scz = odd ? sc1 : sc0;
+            det_sinpi_both(px[j][2] * scz, p0, p1);
+            sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+            B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
+            if (shared_time) {
+                B[j][6] = t_feat[0];
+                B[j][7] = t_feat[1];
+            } else {
+                det_sinpi_both(tq[j] * scz, p0, p1);
+                sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+                B[j][6] = __uint_as_float(sw[0]); B[j][7] = __uint_as_float(sw[1]);
+            }
+        }
+        mlp_layer<8, 4, NT>(lw + BL::M0, lane, B, D);
+        to_operand<4, true, NT>(D, B);
+        mlp_layer<16, 4, NT>(lw + BL::M1, lane, B, D);
+        to_operand<4, true, NT>(D, B);
+        mlp_layer<16, 4, NT>(lw + BL::M2, lane, B, D);
+        to_operand<4, true, NT>(D, B);
+        mlp_layer<16, 1, NT>(lw + BL::M3, lane, B, D);
+        move_store<NT>(A, D, px, tile * TILE, n_eff, g, c);
+    }
+}
+
+// ---- motion network on fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2; K32: the blob has half_kernel_k32's placements) ----
+template <bool SPLIT, bool K32, int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void move_half_kernel(MoveArgs A)
+{
+    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    using BL = HalfBlob<false>;
+    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_eff = sample_count(A.n, A.n_dev);
+    const int64_t n_tiles = (n_eff + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
+    if constexpr (SPLIT)
+        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        int lds_off = 0;
+        asm volatile("" : "+v"(lds_off));
+        const _Float16 *const whi = lds + lds_off;
+        const _Float16 *const wlo = whi + kMotionHalves;
+        float px[NT][3], tq[NT];
+        load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
+
+        h8 Bh[NT][2], Bl[NT][2];
+        f4 D[NT][4];
+        // tcnn Frequency(4): lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            float v = tq[j];
+            v = (g == 0) ? px[j][0] : v;
+            v = (g == 1) ? px[j][1] : v;
+            v = (g == 2) ? px[j][2] : v;
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
+            to_half8<SPLIT>(f, Bh[j][0], Bl[j][0]);
+        }
+        mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bh, Bl, D);
+        to_operand_h<NT, SPLIT>(D, Bh, Bl);
+        hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bh, Bl, D);
+        to_operand_h<NT, SPLIT>(D, Bh, Bl);
+        hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bh, Bl, D);
+        to_operand_h<NT, SPLIT>(D, Bh, Bl);
+        hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
+        move_store<NT>(A, D, px, tile * TILE, n_eff, g, c);
+    }
+}
+
+// SH coefficient g of the head's input (model.py:447-459), as the fused kernels evaluate it: lane group g normalises
+// only the direction component it needs (Y00 const, Y1-1 ~ -y, Y10 ~ z, Y11 ~ -x; tcnn maps the unit vector to [0,1]
+// and back).
+__device__ __forceinline__ float sh_component(const float *__restrict__ dir, int64_t s, int g)
+{
+    float dv[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) dv[a] = dir[3 * s + a];
+    const float nrm = __builtin_sqrtf((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]);
+    const float comp = (g == 1) ? dv[1] : (g == 2) ? dv[2] : dv[0];
+    const float u = (comp / nrm + 1.0f) / 2.0f;
+    const float vv = u * 2.0f - 1.0f;
+    const float coef = (g == 2) ? 0.48860251190291987f : -0.48860251190291987f;
+    return (g == 0) ? 0.28209479177387814f : coef * vv;
+}
+
+// colour channel a sits on accumulator row 4a = (lane group a, register 0): one sigmoid per lane
+template <int NT>
+__device__ __forceinline__ void rgb_store(const RgbArgs &A, const f4 (&D)[NT][4], int64_t tile_base, int g, int c)
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int64_t s = tile_base + 16 * j + c;
+        const float raw = D[j][0][0];
+        const float o1 = A.apply_act ? 1.0f / (1.0f + det_expf(-raw)) : raw;
+        if (g < 3 && s < A.n) A.rgb[3 * s + g] = o1;
+    }
+}
+
+// ---- colour head, fp32 MFMA chain (CED_MLP_F32) --------------------------------------------------------------------
+template <int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void rgb_kernel(RgbArgs A)
+{
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    constexpr int H0 = 0, H1 = H0 + layer_floats(4, 5), H2 = H1 + layer_floats(4, 16);
+    static_assert(H2 + layer_floats(1, 16) == kHeadFloats, "head layers");
+    __shared__ __attribute__((aligned(16))) float lds[kHeadFloats];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;
+
+    stage<THREADS>(lds, A.weights, kHeadFloats / 4, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        int lds_off = 0;
+        asm volatile("" : "+v"(lds_off));
+        const float *const lw = lds + lds_off;
+        float B[NT][16];
+        f4 D[NT][4];
+        // head input [SH(4), geo(15)], k = 4S + g: k-step 0 is SH_g, k-steps 1..3 geometry feature 4S + g - 4, k-step 4
+        // features 12 + g (g < 3) -- what the fused kernel's mlp_base leaves in those registers (base_out_neuron)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            int64_t s = tile * TILE + 16 * j + c;
+            s = s < A.n ? s : A.n - 1;
+            B[j][0] = sh_component(A.dir, s, g);
+#pragma unroll
+            for (int S = 1; S < 4; ++S) B[j][S] = A.geo[s * 15 + 4 * S + g - 4];
+            const float tail = A.geo[s * 15 + (g < 3 ? 12 + g : 14)];
+            B[j][4] = (g == 3) ? 0.0f : tail;
+        }
+        mlp_layer<5, 4, NT>(lw + H0, lane, B, D);
+        to_operand<4, true, NT>(D, B);
+        mlp_layer<16, 4, NT>(lw + H1, lane, B, D);
+        to_operand<4, true, NT>(D, B);
+        mlp_layer<16, 1, NT>(lw + H2, lane, B, D);
+        rgb_store<NT>(A, D, tile * TILE, g, c);
+    }
+}
+
+// ---- colour head on fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2, CED_MLP_F32_HEAD16X2) -------------------------------------
+template <bool SPLIT, bool K32, int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void rgb_half_kernel(RgbArgs A)
+{
+    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    using BL = Blob<false>;
+    __shared__ __attribute__((aligned(16))) _Float16 lds[kHeadHalves * (SPLIT ? 2 : 1)];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kHeadHalves / 8, tid);
+    if constexpr (SPLIT)
+        stage<THREADS>(lds + kHeadHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kHeadHalves / 8, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        int lds_off = 0;
+        asm volatile("" : "+v"(lds_off));
+        const _Float16 *const whi = lds + lds_off;
+        const _Float16 *const wlo = whi + kHeadHalves;
+        h8 Bh[NT][2], Bl[NT][2];
+        f4 D[NT][4];
+        // operand element 0 = SH_g, 1..4 = geometry features 4g .. 4g + 3 (feature 15 does not exist), saturated to the
+        // fp16 range as the fused kernels saturate their mlp_base outputs
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            int64_t s = tile * TILE + 16 * j + c;
+            s = s < A.n ? s : A.n - 1;
+            float hin[8];
+            hin[0] = sh_component(A.dir, s, g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = 4 * g + r < 15 ? 4 * g + r : 14;
+                hin[1 + r] = __builtin_amdgcn_fmed3f(A.geo[s * 15 + f], -kHalfMax, kHalfMax);
+            }
+            hin[4] = (g == 3) ? 0.0f : hin[4];
+            hin[5] = hin[6] = hin[7] = 0.0f;
+            to_half8<SPLIT>(hin, Bh[j][0], Bl[j][0]);
+        }
+        mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::HF_H0 * kFragHalves, wlo + BL::HF_H0 * kFragHalves, lane, Bh, Bl, D);
+        to_operand_h<NT, SPLIT>(D, Bh, Bl);
+        hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::HF_H1 * kFragHalves, wlo + BL::HF_H1 * kFragHalves, lane, Bh, Bl, D);
+        to_operand_h<NT, SPLIT>(D, Bh, Bl);
+        hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::HF_H2 * kFragHalves, wlo + BL::HF_H2 * kFragHalves, lane, Bh, Bl, D);
+        rgb_store<NT>(A, D, tile * TILE, g, c);
+    }
+}
+
+// Persistent launch: enough workgroups for the tiles, at most per_cu per CU (the descriptor's max_workgroups caps it).
+template <int NT, int THREADS, typename Kernel, typename Args>
+static void launch_tiles(Kernel kernel, const Args &A, int64_t n, int per_cu, int max_workgroups, void *stream)
+{
+    const int64_t n_tiles = (n + 16 * NT - 1) / (16 * NT);
+    constexpr int waves = THREADS / 64;
+    int64_t blocks = (n_tiles + waves - 1) / waves;
+    const int64_t cap = max_workgroups > 0 ? max_workgroups : (int64_t)kFieldBlocksDefault * per_cu;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
+}
+
+// the descriptor fields these entries read; the hash table is not touched, but its kind selects the blob's layout
+static int validate_desc(const ced_field_desc *d, const char *who)
+{
+    CED_REQUIRE(d != nullptr, "%s: null descriptor", who);
+    CED_REQUIRE(d->time_mode >= 0 && d->time_mode <= 2, "%s: time_mode=%d", who, d->time_mode);
+    CED_REQUIRE(d->packed_weights != nullptr, "%s: null packed_weights", who);
+    CED_REQUIRE(d->mlp_precision >= CED_MLP_F32 && d->mlp_precision <= CED_MLP_F32_HEAD16X2, "%s: mlp_precision=%d", who,
+                d->mlp_precision);
+    CED_REQUIRE((int64_t)d->packed_floats == ced_packed_weight_words(d->use_div_offsets, d->time_mode, d->mlp_precision),
+                "%s: packed_floats=%llu does not match this configuration (mlp_precision %d)", who,
+                (unsigned long long)d->packed_floats, d->mlp_precision);
+    CED_REQUIRE(d->max_workgroups >= 0 && d->max_workgroups <= 65536, "%s: max_workgroups=%d", who, d->max_workgroups);
+    return CED_OK;
+}
+
+static int launch_move(const ced_field_desc *d, MoveArgs &A, const char *who, void *stream)
+{
+    for (int i = 0; i < 6; ++i) A.aabb[i] = d->aabb[i];
+    A.moving_step = d->moving_step;
+    A.use_div = d->use_div_offsets ? 1 : 0;
+    A.weights = d->packed_weights;                    // every blob starts with the motion network
+    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
+    const int mw = d->max_workgroups;
+    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
+        launch_tiles<2, 512>(move_kernel<2, 512>, A, A.n, 2, mw, stream);
+    else if (d->mlp_precision == CED_MLP_F16)
+        launch_tiles<2, 512>(move_half_kernel<false, false, 2, 512>, A, A.n, 2, mw, stream);
+    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
+        launch_tiles<2, 512>(move_half_kernel<true, true, 2, 512>, A, A.n, 2, mw, stream);
+    else
+        launch_tiles<2, 512>(move_half_kernel<true, false, 2, 512>, A, A.n, 2, mw, stream);
+    return check_launch(who);
+}
+
+}  // namespace ced
+
+extern "C" int ced_field_move(const ced_field_desc *desc, int64_t n, const float *positions, const float *t, float *x_move,
+                              float *move, float *x_norm, uint8_t *selector, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_move");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_move: n < 0");
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(positions && t, "field_move: null positions/t");
+    CED_REQUIRE(x_move || move || x_norm || selector, "field_move: no output requested");
+    ced::MoveArgs A{};
+    A.n = n;
+    A.pos = positions; A.t = t;
+    A.x_move = x_move; A.move = move; A.x_norm = x_norm; A.selector = selector;
+    return ced::launch_move(desc, A, "field_move", stream);
+}
+
+extern "C" int ced_field_move_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_dev, const float *rays_o,
+                                   const float *rays_d, const int64_t *ray_indices, const float *t_starts,
+                                   const float *t_ends, const float *timestamps, int32_t t_per_ray, float *move,
+                                   float *x_norm, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_move_rays");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_move_rays: n < 0");
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && timestamps, "field_move_rays: null pointer");
+    CED_REQUIRE(move || x_norm, "field_move_rays: no output requested");
+    ced::MoveArgs A{};
+    A.n = n;
+    A.n_dev = n_dev;
+    A.rays_o = rays_o; A.rays_d = rays_d; A.ray_idx = ray_indices;
+    A.t0 = t_starts; A.t1 = t_ends; A.timestamps = timestamps;
+    A.rays_mode = 1; A.t_per_ray = t_per_ray ? 1 : 0;
+    A.move = move; A.x_norm = x_norm;
+    return ced::launch_move(desc, A, "field_move_rays", stream);
+}
+
+extern "C" int ced_field_rgb(const ced_field_desc *desc, int64_t n, const float *dirs, const float *embedding,
+                             int32_t apply_act, float *rgb, void *stream)
+{
+    using namespace ced;
+    int rc = validate_desc(desc, "field_rgb");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_rgb: n < 0");
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(dirs && embedding && rgb, "field_rgb: null pointer");
+    RgbArgs A{};
+    A.n = n;
+    A.dir = dirs; A.geo = embedding; A.apply_act = apply_act ? 1 : 0; A.rgb = rgb;
+    const bool te = desc->time_mode != 0;
+    const int mw = desc->max_workgroups;
+    if (desc->mlp_precision == CED_MLP_F32) {
+        A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
+        launch_tiles<2, 512>(rgb_kernel<2, 512>, A, n, 2, mw, stream);
+    } else if (desc->mlp_precision == CED_MLP_F32_HEAD16X2) {
+        // the mixed blob: fp16 fragments in the fp32 head's region, high parts then remainders, pair-form placements
+        A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
+        A.lo_halves = kHeadHalves;
+        launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512>, A, n, 2, mw, stream);
+    } else {
+        A.weights = reinterpret_cast<const _Float16 *>(desc->packed_weights) +
+                    (int64_t)(te ? HalfBlob<true>::H0 : HalfBlob<false>::H0) * kFragHalves;
+        A.lo_halves = (int64_t)(te ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
+        if (desc->mlp_precision == CED_MLP_F16)
+            launch_tiles<2, 512>(rgb_half_kernel<false, false, 2, 512>, A, n, 2, mw, stream);
+        else if (half_layout_k32(desc->time_mode, desc->mlp_precision, desc->hash.temporal))
+            launch_tiles<2, 512>(rgb_half_kernel<true, true, 2, 512>, A, n, 2, mw, stream);
+        else
+            launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512>, A, n, 2, mw, stream);
+    }
+    return check_launch("field_rgb");
+}

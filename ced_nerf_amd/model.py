@@ -216,6 +216,35 @@ class DNGPradianceField(torch.nn.Module):
                                None if t is None else t.reshape(-1).float().contiguous())
 
     @torch.no_grad()
+    def query_move(self, x: torch.Tensor, t: torch.Tensor, return_normalized: bool = False):
+        """cednerf/model.py:354-365: the motion network's displacement of x at time t.  x is viewed as [-1, 3], t as
+        [-1, 1]; returns (x_move, move), both [N, 3], move = xyz_wrap(Frequency(x, t)) * MOVING_STEP (plus the tanh'd fine
+        offsets with use_div_offsets) and x_move = x + move -- the values the fused forward computes internally, in this
+        field's mlp_precision, bit for bit (ced_field_move).  return_normalized=True also returns what query_density
+        derives from x_move (:378-383): x_norm = (x_move - aabb_min) / (aabb_max - aabb_min) and the boolean selector
+        all(0 < x_norm < 1)."""
+        if not x.is_cuda:
+            raise NotImplementedError("Only support cuda inputs: query_move runs on the HIP kernel (no CPU fallback).")
+        x_move, move, x_norm, selector = ops.field_move(
+            self._descriptor(), x.reshape(-1, 3).float().contiguous(), t.reshape(-1).float().contiguous(),
+            want=(True, True, return_normalized, return_normalized))
+        if return_normalized:
+            return x_move, move, x_norm, selector
+        return x_move, move
+
+    @torch.no_grad()
+    def _query_rgb(self, dir: torch.Tensor, embedding: torch.Tensor, apply_act: bool = True):
+        """cednerf/model.py:447-466: colour from view directions and the density branch's embedding
+        (results['base_mlp_out']): dir is normalised, mapped to [0, 1] and SH-encoded, mlp_head runs on
+        [SH(4), embedding(15)] in this field's mlp_precision, the sigmoid is applied iff apply_act.  Returns
+        embedding.shape[:-1] + [3]."""
+        if not (dir.is_cuda and embedding.is_cuda):
+            raise NotImplementedError("Only support cuda inputs: _query_rgb runs on the HIP kernel (no CPU fallback).")
+        rgb = ops.field_rgb(self._descriptor(), dir.reshape(-1, 3).float().contiguous(),
+                            embedding.reshape(-1, self.geo_feat_dim).float().contiguous(), apply_act)
+        return rgb.view(list(embedding.shape[:-1]) + [3])
+
+    @torch.no_grad()
     def query_density(self, x, t, return_feat: bool = False, return_interal: bool = False):
         """cednerf/model.py:367-445 (eval: no training-only `interal_output`)."""
         if return_interal and self.training and (self.use_feat_predict or self.use_weight_predict):
@@ -252,6 +281,15 @@ class DNGPradianceField(torch.nn.Module):
         per_ray = bool(self.training)
         return ops.field_forward_rays(self._descriptor(), rays_o, rays_d, ray_indices, t_starts, t_ends, ts, per_ray,
                                       want_rgb, n_dev=n_dev)
+
+    @torch.no_grad()
+    def query_move_rays(self, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, want_x_norm: bool = False,
+                        n_dev: Optional[torch.Tensor] = None):
+        """`query_move` at the samples `query_rays` evaluates (same positions, same per-ray / per-frame timestamps):
+        returns (move [S,3], x_norm [S,3] or None)."""
+        ts = timestamps.reshape(-1).float().contiguous()
+        return ops.field_move_rays(self._descriptor(), rays_o, rays_d, ray_indices, t_starts, t_ends, ts,
+                                   bool(self.training), want_x_norm, n_dev=n_dev)
 
 
 def make_occ_eval_fn(radiance_field: "DNGPradianceField", timestamps: torch.Tensor, render_step_size: float):

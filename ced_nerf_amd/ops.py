@@ -262,6 +262,60 @@ def field_forward_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_star
     return rgb, sigma
 
 
+def field_move(desc: _lib.FieldDesc, positions, t, want=(True, True, True, True)):
+    """ced_field_move: query_move plus the normalisation that follows it.  want = which of (x_move [n,3], move [n,3],
+    x_norm [n,3], selector [n] bool) to compute; the others come back as None."""
+    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
+    n = positions.shape[0]
+    assert positions.shape == (n, 3) and t.numel() == n
+    if not any(want):
+        raise ValueError("field_move: no output requested")
+    dev = positions.device
+    outs = [torch.empty((n, 3), device=dev, dtype=torch.float32) if w else None for w in want[:3]]
+    sel = torch.empty((n,), device=dev, dtype=torch.bool) if want[3] else None
+    rc = _lib.lib().ced_field_move(C.byref(desc), n, _p(positions), _p(t), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                                   _p(_as_u8(sel)), _stream())
+    _lib.check(rc, "field_move")
+    return outs[0], outs[1], outs[2], sel
+
+
+def field_move_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray: bool,
+                    want_x_norm: bool = False, n_dev: Optional[torch.Tensor] = None, out=None):
+    """ced_field_move_rays: (move [n,3], x_norm [n,3] or None) at the sample positions of `field_forward_rays`.
+    n_dev as there; out = (move, x_norm) buffers to write into instead of fresh ones."""
+    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
+    _chk(ray_indices, torch.int64, "ray_indices")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
+    _chk(timestamps, torch.float32, "timestamps")
+    n = ray_indices.shape[0]
+    assert t_starts.shape == (n,) and t_ends.shape == (n,)
+    if t_per_ray:
+        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
+    dev = rays_o.device
+    if out is not None:
+        move, x_norm = out
+        _chk(move, torch.float32, "out[0]"); _chk(x_norm, torch.float32, "out[1]", allow_none=True)
+        assert move.shape == (n, 3) and (x_norm is None or x_norm.shape == (n, 3))
+    else:
+        move = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        x_norm = torch.empty((n, 3), device=dev, dtype=torch.float32) if want_x_norm else None
+    rc = _lib.lib().ced_field_move_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices), _p(t_starts),
+                                        _p(t_ends), _p(timestamps), int(bool(t_per_ray)), _p(move), _p(x_norm), _stream())
+    _lib.check(rc, "field_move_rays")
+    return move, x_norm
+
+
+def field_rgb(desc: _lib.FieldDesc, directions, embedding, apply_act: bool = True):
+    """ced_field_rgb: mlp_head on [SH(directions), embedding [n,15]] -> rgb [n,3] (sigmoid iff apply_act)."""
+    _chk(directions, torch.float32, "directions"); _chk(embedding, torch.float32, "embedding")
+    n = directions.shape[0]
+    assert directions.shape == (n, 3) and embedding.shape == (n, 15), f"{directions.shape} v.s. {embedding.shape}"
+    rgb = torch.empty((n, 3), device=directions.device, dtype=torch.float32)
+    rc = _lib.lib().ced_field_rgb(C.byref(desc), n, _p(directions), _p(embedding), int(bool(apply_act)), _p(rgb), _stream())
+    _lib.check(rc, "field_rgb")
+    return rgb
+
+
 # ----------------------------------------------------------------------------------------------
 # compositing
 # ----------------------------------------------------------------------------------------------

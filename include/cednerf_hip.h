@@ -259,6 +259,31 @@ int ced_field_forward_rays(const ced_field_desc *desc, int64_t n, const int64_t 
                            const float *timestamps, int32_t t_per_ray, int32_t want_rgb,
                            float *rgb, float *sigma, void *stream);
 
+/* ---- the deformation field on its own ----
+ * DNGPradianceField.query_move(x, t) -- cednerf/model.py:354-365 -- with the normalisation that follows it in
+ * query_density (:378-383): tcnn Frequency encoding of (x, y, z, t), xyz_wrap, move = out * moving_step (with
+ * use_div_offsets: out[:3] * step + tanh(out[3:]) * step), x_move = x + move, x_norm = (x_move - aabb_min) /
+ * (aabb_max - aabb_min) (NOT clamped), selector = all(0 < x_norm < 1).  The motion network runs in the arithmetic
+ * desc->mlp_precision gives it inside ced_field_forward, on the same packed blob: the values are the ones the fused
+ * kernel computes internally, bit for bit.  The hash table is not read (desc->hash.temporal still says which blob layout
+ * the f16x2 mode uses).  x_move, move, x_norm [n,3] and selector [n] (uint8, 0 / 1) may each be NULL, not all of them. */
+int ced_field_move(const ced_field_desc *desc, int64_t n, const float *positions, const float *t,
+                   float *x_move, float *move, float *x_norm, uint8_t *selector, void *stream);
+
+/* The same at the sample positions of the sigma_fn / rgb_sigma_fn closures: positions, timestamps, t_per_ray and n_dev
+ * as in ced_field_forward_rays (samples past min(n, *n_dev) are left untouched).  move, x_norm [n,3]: either may be
+ * NULL, not both. */
+int ced_field_move_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_dev,
+                        const float *rays_o, const float *rays_d,
+                        const int64_t *ray_indices, const float *t_starts, const float *t_ends,
+                        const float *timestamps, int32_t t_per_ray, float *move, float *x_norm, void *stream);
+
+/* DNGPradianceField._query_rgb(dir, embedding, apply_act) -- cednerf/model.py:447-466: dirs [n,3] are normalised,
+ * mapped to [0,1], SH degree 2; mlp_head on [SH(4), embedding(15)]; the sigmoid iff apply_act.  embedding [n,15] is what
+ * ced_field_forward writes to `geo`; rgb [n,3].  The head runs in the arithmetic of desc->mlp_precision. */
+int ced_field_rgb(const ced_field_desc *desc, int64_t n, const float *dirs, const float *embedding,
+                  int32_t apply_act, float *rgb, void *stream);
+
 /* nerfacc.render_weight_from_density / render_transmittance_from_density with packed_info
  * [n_rays,2] = (start,count) -- call sites cednerf/render.py:52-54,81-87, cednerf/utils.py:274-281.
  * prefix_trans is per sample (NULL = 1); weights/trans/alphas may each be NULL. */
