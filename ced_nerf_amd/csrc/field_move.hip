@@ -1,7 +1,8 @@
 // The deformation field on its own: DNGPradianceField.query_move (cednerf/model.py:354-365) with the normalisation that
 // follows it (:378-383), and DNGPradianceField._query_rgb (:447-466).  Inside the fused field kernels the move vector and
 // the head's input only ever live in registers; these entries hand them out (ced_field_move, ced_field_move_rays) and
-// take the head's input from memory (ced_field_rgb).
+// take the head's input from memory (ced_field_rgb; ced_field_rgb_bcast for every embedding under every direction of a
+// shared list, without expanding either in memory).
 //
 // They are built from the fused kernels' own device code -- mlp_layer / to_operand (field_kernel.hpp), mlp_layer_h /
 // to_operand_h / to_half8 (field_half_device.hpp), the deterministic transcendentals of ced_common.hpp -- on the same
@@ -43,7 +44,8 @@ struct MoveArgs {
 
 struct RgbArgs {
     int64_t n;
-    const float *dir, *geo;                           // [n,3], [n,15]
+    const float *dir, *geo;                           // [n,3], [n,15]; broadcast: [n_dirs,3], [n / n_dirs,15]
+    int64_t n_dirs;                                   // broadcast only: row r reads embedding r / n_dirs, direction r % n_dirs
     int apply_act;
     float *rgb;                                       // [n,3]
     const void *weights;                              // the head's first layer inside the packed blob
@@ -376,6 +378,17 @@ __device__ __forceinline__ float sh_component(const float *__restrict__ dir, int
     return (g == 0) ? 0.28209479177387814f : coef * vv;
 }
 
+// the rows of `dir` and `geo` that output row s reads
+template <bool BCAST> __device__ __forceinline__ void rgb_rows(const RgbArgs &A, int64_t s, int64_t &sd, int64_t &se)
+{
+    if constexpr (BCAST) {
+        se = s / A.n_dirs;
+        sd = s - se * A.n_dirs;
+    } else {
+        sd = se = s;
+    }
+}
+
 // colour channel a sits on accumulator row 4a = (lane group a, register 0): one sigmoid per lane
 template <int NT>
 __device__ __forceinline__ void rgb_store(const RgbArgs &A, const f4 (&D)[NT][4], int64_t tile_base, int g, int c)
@@ -390,7 +403,7 @@ __device__ __forceinline__ void rgb_store(const RgbArgs &A, const f4 (&D)[NT][4]
 }
 
 // ---- colour head, fp32 MFMA chain (CED_MLP_F32) --------------------------------------------------------------------
-template <int NT, int THREADS>
+template <int NT, int THREADS, bool BCAST = false>
 __global__ __launch_bounds__(THREADS) void rgb_kernel(RgbArgs A)
 {
     constexpr int WAVES = THREADS / kWave;
@@ -419,10 +432,12 @@ __global__ __launch_bounds__(THREADS) void rgb_kernel(RgbArgs A)
         for (int j = 0; j < NT; ++j) {
             int64_t s = tile * TILE + 16 * j + c;
             s = s < A.n ? s : A.n - 1;
-            B[j][0] = sh_component(A.dir, s, g);
+            int64_t sd, se;
+            rgb_rows<BCAST>(A, s, sd, se);
+            B[j][0] = sh_component(A.dir, sd, g);
 #pragma unroll
-            for (int S = 1; S < 4; ++S) B[j][S] = A.geo[s * 15 + 4 * S + g - 4];
-            const float tail = A.geo[s * 15 + (g < 3 ? 12 + g : 14)];
+            for (int S = 1; S < 4; ++S) B[j][S] = A.geo[se * 15 + 4 * S + g - 4];
+            const float tail = A.geo[se * 15 + (g < 3 ? 12 + g : 14)];
             B[j][4] = (g == 3) ? 0.0f : tail;
         }
         mlp_layer<5, 4, NT>(lw + H0, lane, B, D);
@@ -435,7 +450,7 @@ __global__ __launch_bounds__(THREADS) void rgb_kernel(RgbArgs A)
 }
 
 // ---- colour head on fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2, CED_MLP_F32_HEAD16X2) -------------------------------------
-template <bool SPLIT, bool K32, int NT, int THREADS>
+template <bool SPLIT, bool K32, int NT, int THREADS, bool BCAST = false>
 __global__ __launch_bounds__(THREADS) void rgb_half_kernel(RgbArgs A)
 {
     static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
@@ -467,12 +482,14 @@ __global__ __launch_bounds__(THREADS) void rgb_half_kernel(RgbArgs A)
         for (int j = 0; j < NT; ++j) {
             int64_t s = tile * TILE + 16 * j + c;
             s = s < A.n ? s : A.n - 1;
+            int64_t sd, se;
+            rgb_rows<BCAST>(A, s, sd, se);
             float hin[8];
-            hin[0] = sh_component(A.dir, s, g);
+            hin[0] = sh_component(A.dir, sd, g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int f = 4 * g + r < 15 ? 4 * g + r : 14;
-                hin[1 + r] = __builtin_amdgcn_fmed3f(A.geo[s * 15 + f], -kHalfMax, kHalfMax);
+                hin[1 + r] = __builtin_amdgcn_fmed3f(A.geo[se * 15 + f], -kHalfMax, kHalfMax);
             }
             hin[4] = (g == 3) ? 0.0f : hin[4];
             hin[5] = hin[6] = hin[7] = 0.0f;
@@ -533,6 +550,34 @@ static int launch_move(const ced_field_desc *d, MoveArgs &A, const char *who, vo
     return check_launch(who);
 }
 
+// the head's kernel for the descriptor's arithmetic, on rows given one by one (ced_field_rgb) or as embedding x direction
+template <bool BCAST> static int launch_rgb(const ced_field_desc *desc, RgbArgs &A, const char *who, void *stream)
+{
+    const int64_t n = A.n;
+    const bool te = desc->time_mode != 0;
+    const int mw = desc->max_workgroups;
+    if (desc->mlp_precision == CED_MLP_F32) {
+        A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
+        launch_tiles<2, 512>(rgb_kernel<2, 512, BCAST>, A, n, 2, mw, stream);
+    } else if (desc->mlp_precision == CED_MLP_F32_HEAD16X2) {
+        // the mixed blob: fp16 fragments in the fp32 head's region, high parts then remainders, pair-form placements
+        A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
+        A.lo_halves = kHeadHalves;
+        launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512, BCAST>, A, n, 2, mw, stream);
+    } else {
+        A.weights = reinterpret_cast<const _Float16 *>(desc->packed_weights) +
+                    (int64_t)(te ? HalfBlob<true>::H0 : HalfBlob<false>::H0) * kFragHalves;
+        A.lo_halves = (int64_t)(te ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
+        if (desc->mlp_precision == CED_MLP_F16)
+            launch_tiles<2, 512>(rgb_half_kernel<false, false, 2, 512, BCAST>, A, n, 2, mw, stream);
+        else if (half_layout_k32(desc->time_mode, desc->mlp_precision, desc->hash.temporal))
+            launch_tiles<2, 512>(rgb_half_kernel<true, true, 2, 512, BCAST>, A, n, 2, mw, stream);
+        else
+            launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512, BCAST>, A, n, 2, mw, stream);
+    }
+    return check_launch(who);
+}
+
 }  // namespace ced
 
 extern "C" int ced_field_move(const ced_field_desc *desc, int64_t n, const float *positions, const float *t, float *x_move,
@@ -584,26 +629,22 @@ extern "C" int ced_field_rgb(const ced_field_desc *desc, int64_t n, const float 
     RgbArgs A{};
     A.n = n;
     A.dir = dirs; A.geo = embedding; A.apply_act = apply_act ? 1 : 0; A.rgb = rgb;
-    const bool te = desc->time_mode != 0;
-    const int mw = desc->max_workgroups;
-    if (desc->mlp_precision == CED_MLP_F32) {
-        A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
-        launch_tiles<2, 512>(rgb_kernel<2, 512>, A, n, 2, mw, stream);
-    } else if (desc->mlp_precision == CED_MLP_F32_HEAD16X2) {
-        // the mixed blob: fp16 fragments in the fp32 head's region, high parts then remainders, pair-form placements
-        A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
-        A.lo_halves = kHeadHalves;
-        launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512>, A, n, 2, mw, stream);
-    } else {
-        A.weights = reinterpret_cast<const _Float16 *>(desc->packed_weights) +
-                    (int64_t)(te ? HalfBlob<true>::H0 : HalfBlob<false>::H0) * kFragHalves;
-        A.lo_halves = (int64_t)(te ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
-        if (desc->mlp_precision == CED_MLP_F16)
-            launch_tiles<2, 512>(rgb_half_kernel<false, false, 2, 512>, A, n, 2, mw, stream);
-        else if (half_layout_k32(desc->time_mode, desc->mlp_precision, desc->hash.temporal))
-            launch_tiles<2, 512>(rgb_half_kernel<true, true, 2, 512>, A, n, 2, mw, stream);
-        else
-            launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512>, A, n, 2, mw, stream);
-    }
-    return check_launch("field_rgb");
+    return launch_rgb<false>(desc, A, "field_rgb", stream);
+}
+
+extern "C" int ced_field_rgb_bcast(const ced_field_desc *desc, int64_t m, int32_t n_dirs, const float *dirs,
+                                   const float *embedding, int32_t apply_act, float *rgb, void *stream)
+{
+    using namespace ced;
+    int rc = validate_desc(desc, "field_rgb_bcast");
+    if (rc) return rc;
+    CED_REQUIRE(m >= 0 && n_dirs >= 0, "field_rgb_bcast: m=%lld n_dirs=%d", (long long)m, n_dirs);
+    CED_REQUIRE(m <= INT64_MAX / 3 / (n_dirs > 0 ? n_dirs : 1), "field_rgb_bcast: m * n_dirs overflows");
+    if (m == 0 || n_dirs == 0) return CED_OK;
+    CED_REQUIRE(dirs && embedding && rgb, "field_rgb_bcast: null pointer");
+    RgbArgs A{};
+    A.n = m * n_dirs;
+    A.n_dirs = n_dirs;
+    A.dir = dirs; A.geo = embedding; A.apply_act = apply_act ? 1 : 0; A.rgb = rgb;
+    return launch_rgb<true>(desc, A, "field_rgb_bcast", stream);
 }

@@ -1,0 +1,315 @@
+"""The radiance field itself as sparse voxel volumes, one per time step: what vis.py:13-46 hands to nerfvis.add_nerf,
+up to the data nerfvis would consume, plus two plain file writers.
+
+The grid is reso^3 cells over the bounding cube of the field's box (vis.py:40-41).  Cell centres, the occupancy mask, the
+density threshold and the embedding x direction broadcast of the colour head run in HIP (csrc/bake.hip,
+ced_field_rgb_bcast); the density in between is the field's own `ced_field_forward`, so `sigma` and `embedding` are
+`query_density`'s bits in every mlp_precision.
+
+    python -m ced_nerf_amd.export --load_model model.pth --preset dnerf -df -te --times 0,0.5,1 --out volumes/
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import struct
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+
+_CPU = "Only support cuda inputs: the volume export runs on the HIP kernels (no CPU fallback)."
+
+
+def _cube(field, center, radius):
+    """vis.py:40-41 on field.aabb: centre of the box, largest half extent."""
+    aabb = field.aabb.detach().float().cpu()
+    if center is None:
+        center = ((aabb[3:] + aabb[:3]) / 2.0).tolist()
+    if radius is None:
+        radius = ((aabb[3:] - aabb[:3]) / 2.0).max().item()
+    return [float(c) for c in center], float(radius)
+
+
+def _check_grid(reso, center, radius):
+    if not isinstance(reso, (int, np.integer)) or isinstance(reso, bool) or not 1 <= int(reso) <= 2048:
+        raise ValueError(f"reso must be an int in 1 .. 2048, got {reso!r}")
+    if len(center) != 3 or not all(np.isfinite(c) for c in center):
+        raise ValueError(f"center must be 3 finite numbers, got {center!r}")
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError(f"radius must be positive and finite, got {radius!r}")
+
+
+def _origin_and_step(reso: int, center, radius: float):
+    """lo_a = center_a - radius, h = (2 radius) / reso in fp32: the values ced_bake_candidates derives"""
+    r = np.float32(radius)
+    lo = np.asarray(center, np.float32) - r
+    return lo, (np.float32(2.0) * r) / np.float32(reso)
+
+
+def voxel_centers(reso: int, center, radius: float, device="cuda") -> torch.Tensor:
+    """[reso^3, 3] centres of the cells of the cube [center - radius, center + radius]^3, flat index
+    (ix * reso + iy) * reso + iz: p_a = lo_a + (i_a + 0.5) * h_a in fp32, multiply then add -- the torch restatement of
+    what ced_bake_candidates computes per cell."""
+    center = [float(c) for c in center]
+    _check_grid(reso, center, radius)
+    lo, h = _origin_and_step(reso, center, radius)
+    i = torch.arange(int(reso), device=device, dtype=torch.float32) + 0.5
+    step = torch.tensor(float(h), device=device, dtype=torch.float32)
+    axes = [torch.tensor(float(lo[a]), device=device, dtype=torch.float32) + i * step for a in range(3)]
+    return torch.stack(torch.meshgrid(axes, indexing="ij"), dim=-1).reshape(-1, 3)
+
+
+def _check_dirs(dirs):
+    if dirs is None:
+        return None
+    if not isinstance(dirs, torch.Tensor):
+        dirs = torch.as_tensor(np.asarray(dirs, np.float32))
+    if dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] < 1:
+        raise ValueError(f"dirs must be [D, 3] with D >= 1, got {list(dirs.shape)}")
+    return dirs
+
+
+def _field_device(field) -> torch.device:
+    dev = field.hash_table.device
+    if dev.type != "cuda":
+        raise NotImplementedError(_CPU)
+    return dev
+
+
+def _time_value(t) -> float:
+    if isinstance(t, torch.Tensor):
+        if t.numel() != 1:
+            raise ValueError(f"t must be a float or a one-element tensor, got shape {list(t.shape)}")
+        return float(t.reshape(-1)[0].item())
+    return float(t)
+
+
+def _candidates(reso, center, radius, dev, estimator, max_cells_per_launch):
+    """(index [n], xyz [n,3]) of every cell worth evaluating, slab by slab"""
+    binaries = aabbs = None
+    if estimator is not None:
+        binaries, aabbs = estimator.binaries, estimator.aabbs
+        if not binaries.is_cuda:
+            raise NotImplementedError(_CPU)
+        binaries, aabbs = binaries.contiguous(), aabbs.float().contiguous()
+    total = int(reso) ** 3
+    parts = []
+    for first in range(0, total, max_cells_per_launch):
+        parts.append(ops.bake_candidates(reso, center, radius, first, min(max_cells_per_launch, total - first), dev,
+                                         binaries, aabbs))
+    if len(parts) == 1:
+        return parts[0]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+def _bake(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max_rows: int, meta: Dict) -> Dict:
+    desc = field._descriptor()
+    index, xyz = cand
+    n = index.shape[0]
+    parts = []
+    for a in range(0, n, max_rows):
+        b = min(n, a + max_rows)
+        tt = torch.full((b - a,), t, device=xyz.device, dtype=torch.float32)
+        _, sigma, emb = ops.field_forward(desc, xyz[a:b], tt, None, want_geo=True)
+        parts.append(ops.bake_select(index[a:b], xyz[a:b], sigma, emb, sigma_thresh))
+        del sigma, emb, tt
+    if len(parts) == 1:
+        kept = parts[0]
+    elif parts:
+        kept = tuple(torch.cat([p[k] for p in parts]) for k in range(4))
+    else:
+        dev = xyz.device
+        kept = (torch.empty((0,), device=dev, dtype=torch.int64), torch.empty((0, 3), device=dev),
+                torch.empty((0,), device=dev), torch.empty((0, 15), device=dev))
+    out = dict(index=kept[0], xyz=kept[1], sigma=kept[2], embedding=kept[3])
+    if dirs is not None:
+        out["rgb"] = ops.field_rgb_bcast(desc, dirs, kept[3], apply_act)
+    out.update(meta, t=t)
+    return out
+
+
+def _setup(field, reso, sigma_thresh, dirs, estimator, center, radius, max_cells_per_launch):
+    center, radius = _cube(field, center, radius)
+    _check_grid(reso, center, radius)
+    if int(max_cells_per_launch) < 1:
+        raise ValueError(f"max_cells_per_launch must be >= 1, got {max_cells_per_launch}")
+    dirs = _check_dirs(dirs)
+    dev = _field_device(field)
+    if dirs is not None:
+        if not dirs.is_cuda:
+            raise NotImplementedError(_CPU)
+        dirs = dirs.to(dev).float().contiguous()
+    return dev, center, radius, dirs, int(max_cells_per_launch)
+
+
+@torch.no_grad()
+def bake_sequence(field, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None,
+                  apply_act: bool = False, center=None, radius=None, max_cells_per_launch: int = 1 << 22) -> List[Dict]:
+    """`bake_volume` at every time of `times`: the candidate cells (the occupancy mask and the centres) are computed once
+    and reused for every time."""
+    dev, center, radius, dirs, max_cells = _setup(field, reso, sigma_thresh, dirs, estimator, center, radius,
+                                                  max_cells_per_launch)
+    times = [_time_value(t) for t in times]
+    with torch.cuda.device(dev):
+        cand = _candidates(int(reso), center, radius, dev, estimator, max_cells)
+        meta = dict(reso=int(reso), center=center, radius=radius, apply_act=bool(apply_act))
+        return [_bake(field, cand, t, float(sigma_thresh), dirs, apply_act, max_cells, meta) for t in times]
+
+
+def bake_volume(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None, apply_act: bool = False,
+                center=None, radius=None, max_cells_per_launch: int = 1 << 22) -> Dict:
+    """The occupied volume of `field` at time t (a float or a one-element tensor; every cell takes it): of the reso^3
+    cells over the cube [center - radius, center + radius]^3 (default: vis.py:40-41 on field.aabb) those with
+    density >= sigma_thresh, in ascending cell order.  Returns
+        index [M] int64 (flat cell index (ix * reso + iy) * reso + iz), xyz [M,3] (cell centres, `voxel_centers`' values),
+        sigma [M] and embedding [M,15] (query_density(xyz, t, return_feat=True)'s bits),
+        rgb [M,D,3] for dirs [D,3] (_query_rgb on every pair, sigmoid iff apply_act; absent without dirs),
+        reso, center, radius, t (and apply_act, for the file writers).
+    estimator: an OccGridEstimator; only cells its grid marks (smallest level that contains the centre) are evaluated.
+    Grids larger than max_cells_per_launch cells run in slabs; the result does not depend on that value."""
+    return bake_sequence(field, [t], reso, sigma_thresh, dirs, estimator, apply_act, center, radius,
+                         max_cells_per_launch)[0]
+
+
+def nerfvis_eval_fn(field, t=0.0):
+    """The eval_fn of vis.py:24-34 for nerfvis.Scene.add_nerf(..., use_dirs=True): x [N,1,3], dirs [1,D,3] ->
+    (rgb [N,D,3] before the activation, density [N,1]) at time t (the reference's commented version uses zeros)."""
+    t = _time_value(t)
+
+    @torch.no_grad()
+    def eval_fn(x: torch.Tensor, dirs: torch.Tensor):
+        if not (x.is_cuda and dirs.is_cuda):
+            raise NotImplementedError(_CPU)
+        pts = x.reshape(-1, 3)
+        tt = torch.full((pts.shape[0], 1), t, device=x.device, dtype=torch.float32)
+        res = field.query_density(pts, tt, return_feat=True)
+        rgb = ops.field_rgb_bcast(field._descriptor(), dirs.reshape(-1, 3).float().contiguous(),
+                                  res["base_mlp_out"].contiguous(), apply_act=False)
+        return rgb, res["density"]
+
+    return eval_fn
+
+
+# ---- files -----------------------------------------------------------------------------------------------------------
+_ARRAYS = ("index", "xyz", "sigma", "embedding", "rgb")
+
+
+def save_npz(path: str, volume: Dict) -> None:
+    """The volume's arrays and scalars as a numpy .npz (index, xyz, sigma, embedding, rgb if present, reso, center,
+    radius, t, apply_act: whether rgb holds colours after the sigmoid)."""
+    out = {k: volume[k].detach().cpu().numpy() for k in _ARRAYS if k in volume}
+    out.update(reso=np.int64(volume["reso"]), center=np.asarray(volume["center"], np.float32),
+               radius=np.float32(volume["radius"]), t=np.float32(volume["t"]),
+               apply_act=np.bool_(volume.get("apply_act", False)))
+    np.savez(path, **out)
+
+
+def ply_header(n: int) -> bytes:
+    return ("ply\nformat binary_little_endian 1.0\n"
+            f"element vertex {int(n)}\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            "property float sigma\nend_header\n").encode("ascii")
+
+
+PLY_RECORD = struct.Struct("<fffBBBf")            # 19 bytes per vertex, no padding
+
+
+def save_ply(path: str, volume: Dict, dirs_reduce: str = "mean") -> None:
+    """A binary little-endian point cloud: x y z, red green blue, sigma.  The colour is the sigmoid of rgb (applied here
+    unless the volume was baked with apply_act) averaged over the directions; grey 128 without rgb."""
+    if dirs_reduce != "mean":
+        raise ValueError(f"dirs_reduce={dirs_reduce!r}: only 'mean'")
+    xyz = volume["xyz"].detach().cpu().numpy().astype("<f4")
+    sigma = volume["sigma"].detach().cpu().numpy().astype("<f4")
+    n = xyz.shape[0]
+    if "rgb" in volume:
+        rgb = volume["rgb"].detach().cpu().numpy().astype(np.float64)
+        if not volume.get("apply_act", False):
+            rgb = 1.0 / (1.0 + np.exp(-rgb))
+        col = np.clip(np.rint(255.0 * rgb.mean(axis=1)), 0, 255).astype(np.uint8)
+    else:
+        col = np.full((n, 3), 128, np.uint8)
+    rec = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3), ("sigma", "<f4")]))
+    assert rec.dtype.itemsize == PLY_RECORD.size
+    rec["xyz"], rec["rgb"], rec["sigma"] = xyz, col, sigma
+    with open(path, "wb") as f:
+        f.write(ply_header(n))
+        f.write(rec.tobytes())
+
+
+def fibonacci_dirs(n: int) -> np.ndarray:
+    """n unit directions spread over the sphere (golden-angle spiral), [n,3] float32"""
+    k = np.arange(n, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * k / n
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], -1).astype(np.float32)
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------
+def make_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m ced_nerf_amd.export",
+                                description="Write the field of a model.pth as sparse voxel volumes, one per time")
+    p.add_argument("--load_model", required=True, metavar="PATH")
+    p.add_argument("--preset", required=True, choices=["dnerf", "hypernerf", "dynerf"])
+    p.add_argument("--assume_tcnn_layout", default=None, help="for a --load_model file written by the reference")
+    p.add_argument("--log2_hashmap_size", type=int, default=21)
+    p.add_argument("-ms", "--moving_step", type=float, default=None)
+    p.add_argument("-df", "--use_div_offsets", action="store_true")
+    p.add_argument("-f", "--use_feat_predict", action="store_true")
+    p.add_argument("-w", "--use_weight_predict", action="store_true")
+    p.add_argument("-te", "--use_time_embedding", action="store_true")
+    p.add_argument("-ta", "--use_time_attenuation", action="store_true")
+    p.add_argument("--times", type=parse_times, default=[0.0], help="comma-separated times in [0, 1], e.g. 0,0.5,1")
+    p.add_argument("--reso", type=int, default=128)
+    p.add_argument("--sigma_thresh", type=float, default=1.0)
+    p.add_argument("--n_dirs", type=int, default=0, help="view directions to evaluate the colour for (0: no colour)")
+    p.add_argument("--no_occupancy", action="store_true", help="evaluate every cell, not only those the grid marks")
+    p.add_argument("--device", default="cuda")
+    p.add_argument("--out", required=True, metavar="DIR")
+    return p
+
+
+def parse_times(text: str) -> List[float]:
+    try:
+        times = [float(v) for v in text.split(",") if v.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--times {text!r}: comma-separated numbers")
+    if not times:
+        raise argparse.ArgumentTypeError("--times: no time given")
+    return times
+
+
+def main(argv=None) -> int:
+    from . import checkpoint, trainer
+    a = make_parser().parse_args(argv)
+    if a.n_dirs < 0:
+        raise SystemExit("--n_dirs must be >= 0")
+    extra = {} if a.moving_step is None else dict(moving_step=a.moving_step)
+    cfg = trainer.resolve_config(a.preset, None, log2_hashmap_size=a.log2_hashmap_size, **extra)
+    ckpt = checkpoint.read_checkpoint(a.load_model)
+    state = ckpt["radiance_field"]
+    dtype = torch.float16 if checkpoint.is_reference_state(state) else state["hash_table"].dtype
+    field, estimator = trainer.build_modules(
+        cfg, torch.device(a.device), hash_dtype=dtype, use_div_offsets=a.use_div_offsets,
+        use_time_embedding=a.use_time_embedding, use_time_attenuation=a.use_time_attenuation,
+        use_feat_predict=a.use_feat_predict, use_weight_predict=a.use_weight_predict)
+    checkpoint.load_checkpoint(ckpt, field, estimator, assume_tcnn_layout=a.assume_tcnn_layout)
+    dirs = torch.from_numpy(fibonacci_dirs(a.n_dirs)).to(field.hash_table.device) if a.n_dirs else None
+    os.makedirs(a.out, exist_ok=True)
+    volumes = bake_sequence(field, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh, dirs=dirs,
+                            estimator=None if a.no_occupancy else estimator)
+    for i, vol in enumerate(volumes):
+        stem = os.path.join(a.out, f"volume_{i:04d}")
+        save_npz(stem + ".npz", vol)
+        save_ply(stem + ".ply", vol)
+        print(f"t={vol['t']:g}: {vol['index'].shape[0]} of {a.reso ** 3} cells -> {stem}.npz / .ply", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -316,6 +316,88 @@ def field_rgb(desc: _lib.FieldDesc, directions, embedding, apply_act: bool = Tru
     return rgb
 
 
+def field_rgb_bcast(desc: _lib.FieldDesc, directions, embedding, apply_act: bool = True):
+    """ced_field_rgb_bcast: mlp_head on every (embedding [m,15], direction [d,3]) pair -> rgb [m,d,3], neither input
+    expanded in memory; each row has the bits of `field_rgb` on the expanded inputs."""
+    _chk(directions, torch.float32, "directions"); _chk(embedding, torch.float32, "embedding")
+    m, d = embedding.shape[0], directions.shape[0]
+    assert directions.shape == (d, 3) and embedding.shape == (m, 15), f"{directions.shape} v.s. {embedding.shape}"
+    rgb = torch.empty((m, d, 3), device=embedding.device, dtype=torch.float32)
+    rc = _lib.lib().ced_field_rgb_bcast(C.byref(desc), m, d, _p(directions), _p(embedding), int(bool(apply_act)), _p(rgb),
+                                        _stream())
+    _lib.check(rc, "field_rgb_bcast")
+    return rgb
+
+
+# ----------------------------------------------------------------------------------------------
+# volume export (csrc/bake.hip)
+# ----------------------------------------------------------------------------------------------
+def _bake_workspace(n: int, dev):
+    nbytes = int(_lib.lib().ced_bake_workspace_bytes(n))
+    return torch.empty((nbytes // 8,), device=dev, dtype=torch.int64), nbytes
+
+
+def bake_candidates(reso: int, center, radius: float, first_cell: int, n_cells: int, device, binaries=None, aabbs=None):
+    """ced_bake_candidates on cells [first_cell, first_cell + n_cells) of the reso^3 grid over the cube
+    [center - radius, center + radius]^3: (index [n] int64 ascending, xyz [n,3]) of the cells an occupancy grid
+    (binaries [levels,R,R,R] bool, aabbs [levels,6]) marks -- all of them without one.  With a grid the count is read
+    back once, so the outputs are allocated at their size."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise NotImplementedError(f"Only support cuda inputs (device is {dev}).")
+    _check_current_device(dev.index, "device")
+    levels = res = 0
+    if binaries is not None:
+        binaries = _chk(_as_u8(binaries), torch.uint8, "binaries"); _chk(aabbs, torch.float32, "aabbs")
+        levels, res = binaries.shape[0], binaries.shape[1]
+        assert binaries.shape == (levels, res, res, res) and aabbs.shape == (levels, 6), (binaries.shape, aabbs.shape)
+    c3 = (C.c_float * 3)(*[float(v) for v in center])
+    ws, ws_bytes = _bake_workspace(n_cells, dev)
+    count = torch.empty((1,), device=dev, dtype=torch.int64)
+
+    def call(capacity, index, xyz):
+        rc = _lib.lib().ced_bake_candidates(int(reso), c3, float(radius), int(first_cell), int(n_cells), _p(binaries),
+                                            _p(aabbs), levels, res, capacity, _p(index), _p(xyz), _p(count), _p(ws),
+                                            ws_bytes, _stream())
+        _lib.check(rc, "bake_candidates")
+
+    n = int(n_cells)
+    if binaries is not None:
+        call(0, None, None)
+        n = int(count.item())
+    index = torch.empty((n,), device=dev, dtype=torch.int64)
+    xyz = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    if n > 0:
+        call(n, index, xyz)
+    return index, xyz
+
+
+def bake_select(index, xyz, sigma, embedding, sigma_thresh: float):
+    """ced_bake_select: the rows with sigma >= sigma_thresh (never a NaN), in their order: (index [m], xyz [m,3],
+    sigma [m], embedding [m,15]).  The count is read back once, so the outputs are allocated at their size."""
+    _chk(index, torch.int64, "index"); _chk(xyz, torch.float32, "xyz")
+    _chk(sigma, torch.float32, "sigma"); _chk(embedding, torch.float32, "embedding")
+    n = index.shape[0]
+    assert index.shape == (n,) and xyz.shape == (n, 3) and sigma.shape == (n,) and embedding.shape == (n, 15)
+    dev = index.device
+    ws, ws_bytes = _bake_workspace(n, dev)
+    count = torch.empty((1,), device=dev, dtype=torch.int64)
+
+    def call(capacity, outs):
+        rc = _lib.lib().ced_bake_select(n, _p(index), _p(xyz), _p(sigma), _p(embedding), float(sigma_thresh), capacity,
+                                        _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(count), _p(ws), ws_bytes,
+                                        _stream())
+        _lib.check(rc, "bake_select")
+
+    call(0, (None,) * 4)
+    m = int(count.item())
+    outs = (torch.empty((m,), device=dev, dtype=torch.int64), torch.empty((m, 3), device=dev, dtype=torch.float32),
+            torch.empty((m,), device=dev, dtype=torch.float32), torch.empty((m, 15), device=dev, dtype=torch.float32))
+    if m > 0:
+        call(m, outs)
+    return outs
+
+
 # ----------------------------------------------------------------------------------------------
 # compositing
 # ----------------------------------------------------------------------------------------------

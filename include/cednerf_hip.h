@@ -284,6 +284,37 @@ int ced_field_move_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_
 int ced_field_rgb(const ced_field_desc *desc, int64_t n, const float *dirs, const float *embedding,
                   int32_t apply_act, float *rgb, void *stream);
 
+/* The same head on m * n_dirs rows without expanding either input: row r = e * n_dirs + d reads embedding[e] ([m,15]) and
+ * dirs[d] ([n_dirs,3]); rgb [m, n_dirs, 3].  Each row's arithmetic is ced_field_rgb's: the bits are those of
+ * ced_field_rgb on the expanded inputs. */
+int ced_field_rgb_bcast(const ced_field_desc *desc, int64_t m, int32_t n_dirs, const float *dirs,
+                        const float *embedding, int32_t apply_act, float *rgb, void *stream);
+
+/* ---- volume export (vis.py:13-46: nerfvis.add_nerf's grid of the field, without nerfvis) ----
+ * The reso^3 cells of the cube [center - radius, center + radius]^3, flat index i = (ix * reso + iy) * reso + iz, centre
+ * p_a = lo_a + (i_a + 0.5f) * h with lo_a = center_a - radius and h = (2 * radius) / reso, all fp32, multiply then add.
+ * Both entries compact in input order (ascending cell index; no atomically claimed slots), write the first
+ * min(*count, capacity) kept rows and the number of kept rows to the device scalar *count; capacity = 0 only counts
+ * (outputs may be NULL).  workspace: ced_bake_workspace_bytes(n) bytes of device memory, n = n_cells resp. n. */
+int64_t ced_bake_workspace_bytes(int64_t n);
+
+/* Cells [first_cell, first_cell + n_cells) worth evaluating.  binaries [levels, R, R, R] (bytes) with aabbs [levels, 6]
+ * on the device: a cell is kept iff some level's box contains its centre (faces included) and, in the first such level,
+ * the grid cell clamp((int)(((p - min) / extent) * R), 0, R - 1) -- the marcher's expression -- is set.  binaries NULL:
+ * every cell is kept.  The levels must be ordered from the smallest box to the largest (OccGridEstimator's nested
+ * levels are): "smallest containing level" is the first in array order.  center_host: 3 floats on the host.  index [capacity] int64, xyz [capacity, 3]. */
+int ced_bake_candidates(int32_t reso, const float *center_host, float radius, int64_t first_cell, int64_t n_cells,
+                        const uint8_t *binaries, const float *aabbs, int32_t levels, int32_t grid_res,
+                        int64_t capacity, int64_t *index, float *xyz, int64_t *count, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+
+/* Of n candidate rows (index_in [n], xyz_in [n,3]) with ced_field_forward's sigma_in [n] and geo as embedding_in [n,15],
+ * the rows with sigma >= sigma_thresh (a NaN does not pass), copied to index / xyz / sigma / embedding. */
+int ced_bake_select(int64_t n, const int64_t *index_in, const float *xyz_in, const float *sigma_in,
+                    const float *embedding_in, float sigma_thresh, int64_t capacity, int64_t *index, float *xyz,
+                    float *sigma, float *embedding, int64_t *count, void *workspace, int64_t workspace_bytes,
+                    void *stream);
+
 /* nerfacc.render_weight_from_density / render_transmittance_from_density with packed_info
  * [n_rays,2] = (start,count) -- call sites cednerf/render.py:52-54,81-87, cednerf/utils.py:274-281.
  * prefix_trans is per sample (NULL = 1); weights/trans/alphas may each be NULL. */
