@@ -15,7 +15,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("CED_NERF_LIB", os.path.join(_PKG, "libcednerf_hip.so"))
 SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "field_half.hip", "field_mixed.hip", "field_move.hip", "frame.hip", "occgrid.hip",
            "raygen.hip", "wgrad.hip", "pixels.hip", "accel.hip", "linear.hip", "mlp.hip", "train_glue.hip", "losses.hip",
-           "metrics.hip", "train_batch.hip", "importance.hip", "bake.hip"]
+           "metrics.hip", "train_batch.hip", "importance.hip", "bake.hip", "mesh.hip"]
 MLP_F32, MLP_F16X2, MLP_F16, MLP_F32_HEAD16X2 = 0, 1, 2, 3          # ced_field_desc.mlp_precision
 # "f32+h16x2": sigma chain exact fp32 (counts / opacity / depth bit-identical to "f32"), colour head on split-fp16 MFMAs
 MLP_PRECISIONS = {"f32": MLP_F32, "f16x2": MLP_F16X2, "f16": MLP_F16, "f32+h16x2": MLP_F32_HEAD16X2}
@@ -111,6 +111,9 @@ PROTOTYPES = {
     "ced_bake_candidates": (C.c_int, [_i32, C.POINTER(C.c_float), _f, _i64, _i64, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp,
                                       _vp, _i64, _vp]),
     "ced_bake_select": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _f, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ced_mesh_workspace_bytes": (_i64, [_i32]),
+    "ced_mesh_vertices": (C.c_int, [_i32, C.POINTER(C.c_float), _f, _vp, _f, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ced_mesh_faces": (C.c_int, [_i32, _vp, _f, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "ced_render_weights": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ced_accumulate_along_rays": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "ced_reduce_along_rays": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),

@@ -7,6 +7,10 @@ ced_field_rgb_bcast); the density in between is the field's own `ced_field_forwa
 `query_density`'s bits in every mlp_precision.
 
     python -m ced_nerf_amd.export --load_model model.pth --preset dnerf -df -te --times 0,0.5,1 --out volumes/
+
+`extract_mesh` / `extract_mesh_sequence` turn the same lattice of cell centres into a triangle mesh per time step: naive
+surface nets on the device (csrc/mesh.hip), the vertices coloured by the field's own head.  `--mesh` writes them next to
+the volumes.
 """
 from __future__ import annotations
 
@@ -193,6 +197,80 @@ def nerfvis_eval_fn(field, t=0.0):
     return eval_fn
 
 
+# ---- meshes ----------------------------------------------------------------------------------------------------------
+MESH_MAX_RESO = 512                               # the dense density lattice is 4 * reso^3 bytes: 512 MiB
+
+
+def _check_mesh_reso(reso):
+    if not isinstance(reso, (int, np.integer)) or isinstance(reso, bool) or not 1 <= int(reso) <= MESH_MAX_RESO:
+        raise ValueError(f"reso must be an int in 1 .. {MESH_MAX_RESO} for a mesh, got {reso!r}")
+
+
+def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max_rows: int, meta: Dict) -> Dict:
+    desc = field._descriptor()
+    index, xyz = cand
+    reso, dev = meta["reso"], xyz.device
+    lattice = torch.zeros((reso ** 3,), device=dev, dtype=torch.float32)         # cells that are no candidates stay 0
+    for a in range(0, index.shape[0], max_rows):
+        b = min(index.shape[0], a + max_rows)
+        tt = torch.full((b - a,), t, device=dev, dtype=torch.float32)
+        _, sigma, _ = ops.field_forward(desc, xyz[a:b], tt, None, want_geo=False)
+        lattice.index_copy_(0, index[a:b], sigma)
+        del sigma, tt
+    vertices, normals, cube, faces = ops.mesh_surface_nets(lattice.view(reso, reso, reso), sigma_thresh, meta["center"],
+                                                           meta["radius"])
+    del lattice
+    v = vertices.shape[0]
+    res = field.query_density(vertices, torch.full((v, 1), t, device=dev, dtype=torch.float32), return_feat=True)
+    out = dict(vertices=vertices, normals=normals, faces=faces, cube=cube, sigma=res["density"].reshape(v),
+               embedding=res["base_mlp_out"])
+    if isinstance(dirs, str):                                                    # "normal": head-on, one direction each
+        head_on = torch.where((normals == 0).all(-1, keepdim=True), normals.new_tensor([0.0, 0.0, 1.0]), -normals)
+        out["rgb"] = field._query_rgb(head_on, out["embedding"], apply_act).view(v, 1, 3)
+    elif dirs is not None:
+        out["rgb"] = ops.field_rgb_bcast(desc, dirs, out["embedding"], apply_act)
+    out.update(meta, t=t)
+    return out
+
+
+@torch.no_grad()
+def extract_mesh_sequence(field, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None,
+                          apply_act: bool = False, center=None, radius=None,
+                          max_cells_per_launch: int = 1 << 22) -> List[Dict]:
+    """`extract_mesh` at every time of `times`: the candidate cells (the occupancy mask and the centres) are computed
+    once and reused for every time."""
+    _check_mesh_reso(reso)
+    by_normal = isinstance(dirs, str)
+    if by_normal and dirs != "normal":
+        raise ValueError(f"dirs must be None, a [D, 3] tensor or 'normal', got {dirs!r}")
+    dev, center, radius, tensor_dirs, max_cells = _setup(field, reso, sigma_thresh, None if by_normal else dirs, estimator,
+                                                         center, radius, max_cells_per_launch)
+    times = [_time_value(t) for t in times]
+    with torch.cuda.device(dev):
+        cand = _candidates(int(reso), center, radius, dev, estimator, max_cells)
+        meta = dict(reso=int(reso), center=center, radius=radius, sigma_thresh=float(sigma_thresh),
+                    apply_act=bool(apply_act))
+        return [_mesh(field, cand, t, float(sigma_thresh), "normal" if by_normal else tensor_dirs, apply_act, max_cells,
+                      meta) for t in times]
+
+
+def extract_mesh(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None, apply_act: bool = False,
+                 center=None, radius=None, max_cells_per_launch: int = 1 << 22) -> Dict:
+    """The iso-surface density == sigma_thresh of `field` at time t as a triangle mesh: naive surface nets (the
+    definition is in include/cednerf_hip.h) on the lattice of `voxel_centers`(reso, center, radius), reso <= 512, whose
+    densities are query_density's bits (0 at the cells an `estimator` does not mark).  Returns
+        vertices [V,3], normals [V,3] (unit, towards lower density; zero where the density gradient vanishes),
+        faces [F,3] int32 (counter-clockwise seen from outside), cube [V] int64 (the lattice cube of each vertex),
+        sigma [V] and embedding [V,15] (query_density(vertices, t, return_feat=True)'s bits),
+        rgb [V,D,3]: for dirs [D,3] _query_rgb on every pair; for dirs="normal" D = 1 and every vertex is viewed head-on,
+        along -normal ((0,0,1) where the normal is zero); the sigmoid iff apply_act; absent without dirs,
+        reso, center, radius, t, sigma_thresh, apply_act.
+    The mesh is closed away from the lattice border and open on it; its vertex and face order do not depend on the run
+    or on max_cells_per_launch."""
+    return extract_mesh_sequence(field, [t], reso, sigma_thresh, dirs, estimator, apply_act, center, radius,
+                                 max_cells_per_launch)[0]
+
+
 # ---- files -----------------------------------------------------------------------------------------------------------
 _ARRAYS = ("index", "xyz", "sigma", "embedding", "rgb")
 
@@ -241,6 +319,59 @@ def save_ply(path: str, volume: Dict, dirs_reduce: str = "mean") -> None:
         f.write(rec.tobytes())
 
 
+_MESH_ARRAYS = ("vertices", "normals", "faces", "cube", "sigma", "embedding", "rgb")
+
+
+def save_mesh_npz(path: str, mesh: Dict) -> None:
+    """The mesh's arrays and scalars as a numpy .npz (vertices, normals, faces, cube, sigma, embedding, rgb if present,
+    reso, center, radius, t, sigma_thresh, apply_act)."""
+    out = {k: mesh[k].detach().cpu().numpy() for k in _MESH_ARRAYS if k in mesh}
+    out.update(reso=np.int64(mesh["reso"]), center=np.asarray(mesh["center"], np.float32),
+               radius=np.float32(mesh["radius"]), t=np.float32(mesh["t"]), sigma_thresh=np.float32(mesh["sigma_thresh"]),
+               apply_act=np.bool_(mesh.get("apply_act", False)))
+    np.savez(path, **out)
+
+
+def mesh_ply_header(n_vertices: int, n_faces: int) -> bytes:
+    return ("ply\nformat binary_little_endian 1.0\n"
+            f"element vertex {int(n_vertices)}\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "property float nx\nproperty float ny\nproperty float nz\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            f"element face {int(n_faces)}\n"
+            "property list uchar int vertex_indices\nend_header\n").encode("ascii")
+
+
+MESH_PLY_VERTEX = struct.Struct("<ffffffBBB")     # 27 bytes per vertex, no padding
+MESH_PLY_FACE = struct.Struct("<Biii")            # 13 bytes per triangle: the count 3, then the vertex ids
+
+
+def save_mesh_ply(path: str, mesh: Dict) -> None:
+    """A binary little-endian triangle mesh: x y z nx ny nz red green blue per vertex, a uchar-counted int list per face.
+    The colour follows save_ply: the sigmoid of rgb (applied here unless the mesh was extracted with apply_act) averaged
+    over the directions; grey 128 without rgb."""
+    xyz = mesh["vertices"].detach().cpu().numpy().astype("<f4")
+    nrm = mesh["normals"].detach().cpu().numpy().astype("<f4")
+    tri = mesh["faces"].detach().cpu().numpy().astype("<i4")
+    n = xyz.shape[0]
+    if "rgb" in mesh:
+        rgb = mesh["rgb"].detach().cpu().numpy().astype(np.float64)
+        if not mesh.get("apply_act", False):
+            rgb = 1.0 / (1.0 + np.exp(-rgb))
+        col = np.clip(np.rint(255.0 * rgb.mean(axis=1)), 0, 255).astype(np.uint8)
+    else:
+        col = np.full((n, 3), 128, np.uint8)
+    vrec = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("rgb", "u1", 3)]))
+    frec = np.empty(tri.shape[0], dtype=np.dtype([("n", "u1"), ("ids", "<i4", 3)]))
+    assert vrec.dtype.itemsize == MESH_PLY_VERTEX.size and frec.dtype.itemsize == MESH_PLY_FACE.size
+    vrec["xyz"], vrec["normal"], vrec["rgb"] = xyz, nrm, col
+    frec["n"], frec["ids"] = 3, tri
+    with open(path, "wb") as f:
+        f.write(mesh_ply_header(n, tri.shape[0]))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
 def fibonacci_dirs(n: int) -> np.ndarray:
     """n unit directions spread over the sphere (golden-angle spiral), [n,3] float32"""
     k = np.arange(n, dtype=np.float64) + 0.5
@@ -269,9 +400,25 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--sigma_thresh", type=float, default=1.0)
     p.add_argument("--n_dirs", type=int, default=0, help="view directions to evaluate the colour for (0: no colour)")
     p.add_argument("--no_occupancy", action="store_true", help="evaluate every cell, not only those the grid marks")
+    p.add_argument("--mesh", action="store_true", help="also write a triangle mesh per time: mesh_%%04d.ply / .npz")
+    p.add_argument("--mesh_dirs", type=parse_mesh_dirs, default="normal", metavar="normal|N",
+                   help="view directions of the mesh colours: 'normal' (every vertex head-on) or N directions spread over "
+                        "the sphere and averaged (0: no colour)")
     p.add_argument("--device", default="cuda")
     p.add_argument("--out", required=True, metavar="DIR")
     return p
+
+
+def parse_mesh_dirs(text: str):
+    if text == "normal":
+        return text
+    try:
+        n = int(text)
+    except ValueError:
+        n = -1
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"--mesh_dirs {text!r}: 'normal' or a number of directions >= 0")
+    return n
 
 
 def parse_times(text: str) -> List[float]:
@@ -308,6 +455,19 @@ def main(argv=None) -> int:
         save_npz(stem + ".npz", vol)
         save_ply(stem + ".ply", vol)
         print(f"t={vol['t']:g}: {vol['index'].shape[0]} of {a.reso ** 3} cells -> {stem}.npz / .ply", flush=True)
+    if a.mesh:
+        if a.mesh_dirs == "normal" or a.mesh_dirs == 0:
+            mesh_dirs = a.mesh_dirs or None
+        else:
+            mesh_dirs = torch.from_numpy(fibonacci_dirs(a.mesh_dirs)).to(field.hash_table.device)
+        meshes = extract_mesh_sequence(field, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh, dirs=mesh_dirs,
+                                       estimator=None if a.no_occupancy else estimator)
+        for i, mesh in enumerate(meshes):
+            stem = os.path.join(a.out, f"mesh_{i:04d}")
+            save_mesh_npz(stem + ".npz", mesh)
+            save_mesh_ply(stem + ".ply", mesh)
+            print(f"t={mesh['t']:g}: {mesh['vertices'].shape[0]} vertices, {mesh['faces'].shape[0]} triangles -> "
+                  f"{stem}.npz / .ply", flush=True)
     return 0
 
 

@@ -399,6 +399,51 @@ def bake_select(index, xyz, sigma, embedding, sigma_thresh: float):
 
 
 # ----------------------------------------------------------------------------------------------
+# mesh export (csrc/mesh.hip)
+# ----------------------------------------------------------------------------------------------
+def mesh_surface_nets(lattice, thresh: float, center, radius: float):
+    """ced_mesh_vertices + ced_mesh_faces: naive surface nets (include/cednerf_hip.h has the definition) of the density
+    lattice [reso,reso,reso] f32 -- node (ix,iy,iz) at the volume export's cell centre -- at the iso-value thresh:
+    (vertices [V,3] f32, normals [V,3] f32, cube [V] int64 ascending cube ids, faces [F,3] int32).  Each count is read
+    back once, so the outputs are allocated at their size."""
+    _chk(lattice, torch.float32, "lattice")
+    reso = lattice.shape[0] if lattice.dim() == 3 else 0
+    if lattice.dim() != 3 or lattice.shape != (reso, reso, reso) or not 1 <= reso <= 512:
+        raise ValueError(f"lattice must be [reso, reso, reso] with reso in 1 .. 512, got {list(lattice.shape)}")
+    dev = lattice.device
+    L = _lib.lib()
+    c3 = (C.c_float * 3)(*[float(v) for v in center])
+    ws_bytes = int(L.ced_mesh_workspace_bytes(reso))
+    ws = torch.empty((ws_bytes // 8,), device=dev, dtype=torch.int64)
+    count = torch.empty((1,), device=dev, dtype=torch.int64)
+
+    def vertices_call(capacity, vertices, normals, cube):
+        rc = L.ced_mesh_vertices(reso, c3, float(radius), _p(lattice), float(thresh), capacity, _p(vertices), _p(normals),
+                                 _p(cube), _p(count), _p(ws), ws_bytes, _stream())
+        _lib.check(rc, "mesh_vertices")
+
+    vertices_call(0, None, None, None)
+    v = int(count.item())
+    vertices = torch.empty((v, 3), device=dev, dtype=torch.float32)
+    normals = torch.empty((v, 3), device=dev, dtype=torch.float32)
+    cube = torch.empty((v,), device=dev, dtype=torch.int64)
+    if v > 0:
+        vertices_call(v, vertices, normals, cube)
+
+    def faces_call(capacity, faces):
+        rc = L.ced_mesh_faces(reso, _p(lattice), float(thresh), _p(cube), v, capacity, _p(faces), _p(count), _p(ws),
+                              ws_bytes, _stream())
+        _lib.check(rc, "mesh_faces")
+
+    faces_call(0, None)
+    quads = int(count.item())
+    faces = torch.empty((2 * quads, 3), device=dev, dtype=torch.int32)
+    if quads > 0:
+        faces_call(quads, faces)
+    return vertices, normals, cube, faces
+
+
+# ----------------------------------------------------------------------------------------------
 # compositing
 # ----------------------------------------------------------------------------------------------
 def render_weights(packed_info, t_starts, t_ends, sigmas, prefix_trans=None, want=(True, True, True)):

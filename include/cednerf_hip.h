@@ -315,6 +315,41 @@ int ced_bake_select(int64_t n, const int64_t *index_in, const float *xyz_in, con
                     float *sigma, float *embedding, int64_t *count, void *workspace, int64_t workspace_bytes,
                     void *stream);
 
+/* ---- mesh export: naive surface nets on the lattice of cell centres ----
+ * Definition (issue "Extract a triangle mesh of the field per time step, in HIP"; tests/mesh_reference.py restates it in
+ * numpy).  All arithmetic is fp32, one rounding per operation.
+ * Lattice: reso nodes per axis (1 .. 512), node (ix,iy,iz) has id (ix * reso + iy) * reso + iz and the position of the
+ *   volume export's cell centre, lo_a + (i_a + 0.5f) * h.  S[n] = lattice[n]; in(n) = S[n] >= thresh (false for a NaN).
+ * Vertices: a cube is named by its lowest corner c (every coordinate < reso - 1) and is active when its 8 corners are
+ *   neither all inside nor all outside; the active cubes in ascending id are the vertices.  Its 12 edges are walked in the
+ *   order: (a,b,c') in (x,y,z),(y,z,x),(z,x,y); ob in 0,1; oc in 0,1; from corner p0 (p0[a] = 0, p0[b] = ob, p0[c'] = oc)
+ *   to p1 = p0 + e_a, s0 = S[p0], s1 = S[p1].  Always g[a] += (s1 - s0); if in(p0) != in(p1): mu = (thresh - s0) / (s1 - s0),
+ *   a non-finite mu becomes 0.5, mu is clamped to [0,1], acc += (p0 with its a-th component replaced by mu), cnt += 1.
+ *   u = acc / (float)cnt; vertex_a = lo_a + (((float)c_a + 0.5f) + u_a) * h; normal = -g / |g| with
+ *   |g| = sqrtf((g_x^2 + g_y^2) + g_z^2), the zero vector when |g| is 0 or not finite.
+ * Faces: lattice edge (n, a), n_a < reso - 1, has key 3 * id(n) + a and is active when in(n) != in(n + e_a) and
+ *   1 <= n_b, n_c' <= reso - 2 (all four cubes around it exist).  Its quad is the vertex ids of the cubes q0 = n - e_b - e_c',
+ *   q1 = n - e_c', q2 = n, q3 = n - e_b, as the triangles (q0,q1,q2),(q0,q2,q3) if in(n), else (q0,q2,q1),(q0,q3,q2):
+ *   outward-facing.  Faces ascend with the edge key; sign-changing edges on the lattice border emit none (the mesh is open
+ *   there) and vertices no face references are kept.
+ * Both entries compact in ascending item order (no atomically claimed slots), write the first min(*count, capacity) kept
+ * items and the number of kept items to the device scalar *count; capacity = 0 only counts (outputs may be NULL).
+ * workspace: ced_mesh_workspace_bytes(reso) bytes of device memory (-1 for a reso outside 1 .. 512). */
+int64_t ced_mesh_workspace_bytes(int32_t reso);
+
+/* lattice [reso^3] on the device, center_host: 3 floats on the host.  *count = V active cubes; vertices, normals
+ * [capacity, 3], cube [capacity] int64 (the cube ids, ascending). */
+int ced_mesh_vertices(int32_t reso, const float *center_host, float radius, const float *lattice, float thresh,
+                      int64_t capacity, float *vertices, float *normals, int64_t *cube, int64_t *count,
+                      void *workspace, int64_t workspace_bytes, void *stream);
+
+/* cube [n_vertices]: ALL of ced_mesh_vertices' cube ids for the same lattice and thresh (a face looks its four vertex
+ * ids up in it by binary search; an id that is absent gives -1).  *count = active edges (quads); faces [2 * capacity, 3]
+ * int32, the two triangles of a quad adjacent. */
+int ced_mesh_faces(int32_t reso, const float *lattice, float thresh, const int64_t *cube, int64_t n_vertices,
+                   int64_t capacity, int32_t *faces, int64_t *count, void *workspace, int64_t workspace_bytes,
+                   void *stream);
+
 /* nerfacc.render_weight_from_density / render_transmittance_from_density with packed_info
  * [n_rays,2] = (start,count) -- call sites cednerf/render.py:52-54,81-87, cednerf/utils.py:274-281.
  * prefix_trans is per sample (NULL = 1); weights/trans/alphas may each be NULL. */
