@@ -105,6 +105,8 @@ PROTOTYPES = {
                                          _vp, _vp, _vp]),
     "ced_field_move": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ced_field_move_rays": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "ced_field_move_inverse": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _i32, _f, _vp, _vp, _vp, _vp]),
+    "ced_field_track": (C.c_int, [C.POINTER(FieldDesc), _i64, _i64, _vp, _vp, _vp, _i32, _f, _vp, _vp, _vp, _vp]),
     "ced_field_rgb": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _i32, _vp, _vp]),
     "ced_field_rgb_bcast": (C.c_int, [C.POINTER(FieldDesc), _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ced_bake_workspace_bytes": (_i64, [_i64]),

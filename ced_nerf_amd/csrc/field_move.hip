@@ -2,7 +2,8 @@
 // follows it (:378-383), and DNGPradianceField._query_rgb (:447-466).  Inside the fused field kernels the move vector and
 // the head's input only ever live in registers; these entries hand them out (ced_field_move, ced_field_move_rays) and
 // take the head's input from memory (ced_field_rgb; ced_field_rgb_bcast for every embedding under every direction of a
-// shared list, without expanding either in memory).
+// shared list, without expanding either in memory).  ced_field_move_inverse / ced_field_track solve x + move(x, t) = c
+// for x by fixed-point iteration on the same device code, the iterate held in registers.
 //
 // They are built from the fused kernels' own device code -- mlp_layer / to_operand (field_kernel.hpp), mlp_layer_h /
 // to_operand_h / to_half8 (field_half_device.hpp), the deterministic transcendentals of ced_common.hpp -- on the same
@@ -40,6 +41,22 @@ struct MoveArgs {
     int use_div;
     const void *weights;                              // the motion network's first layer inside the packed blob
     int64_t lo_halves;                                // f16x2: halves from the plane of high parts to the plane of remainders
+};
+
+// the inverse of the warp by fixed-point iteration (ced_field_move_inverse, ced_field_track)
+struct TrackArgs {
+    int64_t n;                                        // rows
+    int64_t n_points;                                 // broadcast: row r reads target / start r % n_points, time r / n_points
+    int bcast;
+    const float *target, *t, *init;                   // [n,3], [n], [n,3] or null; broadcast: [P,3], [T], [P,3] or null
+    int max_iters;
+    float tol;
+    float *x, *step;                                  // [n,3], [n], either may be null
+    int32_t *evals;                                   // [n], may be null
+    float moving_step;
+    int use_div;
+    const void *weights;
+    int64_t lo_halves;
 };
 
 struct RgbArgs {
@@ -105,31 +122,44 @@ __device__ __forceinline__ void load_samples(const MoveArgs &A, int64_t tile_bas
     }
 }
 
-// query_move / normalise / selector (model.py:354-383) from the motion network's accumulators (rows natural: row a on
-// lane group 0 register a; rows 3,4,5 on (g0,r3), (g1,r0), (g1,r1)), as the fused kernels state it -- except that x_norm
-// leaves unclamped, as the reference returns it.  Lane group a < 3 stores component a, lane group 3 the selector.
+// query_move's `move` (model.py:354-365) from the motion network's accumulators (rows natural: row a on lane group 0
+// register a; rows 3,4,5 on (g0,r3), (g1,r0), (g1,r1)), as the fused kernels state it.  Every lane gets all three
+// components of its column's samples.
 template <int NT>
-__device__ __forceinline__ void move_store(const MoveArgs &A, const f4 (&D)[NT][4], const float (&px)[NT][3], int64_t tile_base,
+__device__ __forceinline__ void move_vector(const f4 (&D)[NT][4], float moving_step, int use_div, int c, float (&mv)[NT][3])
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float off = __shfl(D[j][0][a], c, 64);
+            float m = off * moving_step;
+            if (use_div) {
+                constexpr int kFineReg[3] = { 3, 0, 1 };
+                const float fine = __shfl(D[j][0][kFineReg[a]], (a == 0) ? c : 16 + c, 64);
+                const float e = det_expf(2.0f * fine);
+                const float th = 1.0f - 2.0f / (e + 1.0f);
+                m = m + th * moving_step;
+            }
+            mv[j][a] = m;
+        }
+    }
+}
+
+// x_move / normalise / selector (model.py:378-383) from `move` -- except that x_norm leaves unclamped, as the reference
+// returns it.  Lane group a < 3 stores component a, lane group 3 the selector.
+template <int NT>
+__device__ __forceinline__ void move_store(const MoveArgs &A, const float (&mv)[NT][3], const float (&px)[NT][3], int64_t tile_base,
                                            int64_t n_eff, int g, int c)
 {
     const float extent[3] = { A.aabb[3] - A.aabb[0], A.aabb[4] - A.aabb[1], A.aabb[5] - A.aabb[2] };
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
-        float mv[3], xm[3], xn[3];
+        float xm[3], xn[3];
         bool inside = true;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const float off = __shfl(D[j][0][a], c, 64);
-            float m = off * A.moving_step;
-            if (A.use_div) {
-                constexpr int kFineReg[3] = { 3, 0, 1 };
-                const float fine = __shfl(D[j][0][kFineReg[a]], (a == 0) ? c : 16 + c, 64);
-                const float e = det_expf(2.0f * fine);
-                const float th = 1.0f - 2.0f / (e + 1.0f);
-                m = m + th * A.moving_step;
-            }
-            mv[a] = m;
-            xm[a] = px[j][a] + m;
+            xm[a] = px[j][a] + mv[j][a];
             const float x = (xm[a] - A.aabb[a]) / extent[a];
             inside = inside && (x > 0.0f && x < 1.0f);
             xn[a] = x;
@@ -140,7 +170,7 @@ __device__ __forceinline__ void move_store(const MoveArgs &A, const f4 (&D)[NT][
             if (A.selector) A.selector[s] = inside ? 1 : 0;
             continue;
         }
-        const float o_move = (g == 0) ? mv[0] : (g == 1) ? mv[1] : mv[2];
+        const float o_move = (g == 0) ? mv[j][0] : (g == 1) ? mv[j][1] : mv[j][2];
         const float o_xm = (g == 0) ? xm[0] : (g == 1) ? xm[1] : xm[2];
         const float o_xn = (g == 0) ? xn[0] : (g == 1) ? xn[1] : xn[2];
         if (A.move) A.move[3 * s + g] = o_move;
@@ -234,13 +264,98 @@ __device__ __forceinline__ void hidden_fed_layer(const _Float16 *__restrict__ wh
     else mlp_layer_h<KS, NB, NT, SPLIT>(whi, wlo, lane, Bh, Bl, D);
 }
 
+// ---- the motion network on one wave tile: encode -> four layers -> move -------------------------------------------------
+// Shared by the kernels that hand `move` out once (move_kernel, move_half_kernel) and by the fixed-point loop that
+// evaluates it up to max_iters times on a position held in registers (track_kernel, track_half_kernel): one statement
+// of the arithmetic, so every evaluation has ced_field_move's bits.
+
+// fp32 chain: the two Frequency features of time tq that lane group g feeds (field_kernel.hpp: k = 4S + g, S = 6, 7)
+__device__ __forceinline__ void time_features(float tq, int g, float &f0, float &f1)
+{
+    const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
+    const float scz = (g & 1) != 0 ? sc1 : sc0;
+    float p0, p1;
+    det_sinpi_both(tq * scz, p0, p1);
+    const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+    f0 = __uint_as_float(sw[0]); f1 = __uint_as_float(sw[1]);
+}
+
+// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): lw = the staged layers M0..M3; time(j, f0, f1) gives the two time
+// features of column tile j where the encoding wants them (time_features, or values the caller holds already)
+template <int NT, typename Time>
+__device__ __forceinline__ void motion_move(const float *lw, int lane, const float (&px)[NT][3], Time time, float moving_step,
+                                            int use_div, float (&mv)[NT][3])
+{
+    using BL = Blob<false>;
+    const int g = lane >> 4, c = lane & 15;
+    float B[NT][16];
+    f4 D[NT][4];
+    // tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const bool odd = (g & 1) != 0;
+        const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
+        const float vxy = odd ? px[j][1] : px[j][0];
+        float p0, p1;
+        det_sinpi_both(vxy * sc0, p0, p1);
+        auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+        B[j][0] = __uint_as_float(sw[0]); B[j][2] = __uint_as_float(sw[1]);
+        det_sinpi_both(vxy * sc1, p0, p1);
+        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+        B[j][1] = __uint_as_float(sw[0]); B[j][3] = __uint_as_float(sw[1]);
+        const float scz = odd ? sc1 : sc0;
+        det_sinpi_both(px[j][2] * scz, p0, p1);
+        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+        B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
+        time(j, B[j][6], B[j][7]);
+    }
+    mlp_layer<8, 4, NT>(lw + BL::M0, lane, B, D);
+    to_operand<4, true, NT>(D, B);
+    mlp_layer<16, 4, NT>(lw + BL::M1, lane, B, D);
+    to_operand<4, true, NT>(D, B);
+    mlp_layer<16, 4, NT>(lw + BL::M2, lane, B, D);
+    to_operand<4, true, NT>(D, B);
+    mlp_layer<16, 1, NT>(lw + BL::M3, lane, B, D);
+    move_vector<NT>(D, moving_step, use_div, c, mv);
+}
+
+// fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2; K32: the blob has half_kernel_k32's placements): whi / wlo = the staged planes
+template <bool SPLIT, bool K32, int NT>
+__device__ __forceinline__ void motion_move_half(const _Float16 *whi, const _Float16 *wlo, int lane, const float (&px)[NT][3],
+                                                 const float (&tq)[NT], float moving_step, int use_div, float (&mv)[NT][3])
+{
+    using BL = HalfBlob<false>;
+    const int g = lane >> 4, c = lane & 15;
+    h8 Bh[NT][2], Bl[NT][2];
+    f4 D[NT][4];
+    // tcnn Frequency(4): lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        float v = tq[j];
+        v = (g == 0) ? px[j][0] : v;
+        v = (g == 1) ? px[j][1] : v;
+        v = (g == 2) ? px[j][2] : v;
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
+        to_half8<SPLIT>(f, Bh[j][0], Bl[j][0]);
+    }
+    mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bh, Bl, D);
+    to_operand_h<NT, SPLIT>(D, Bh, Bl);
+    hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bh, Bl, D);
+    to_operand_h<NT, SPLIT>(D, Bh, Bl);
+    hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bh, Bl, D);
+    to_operand_h<NT, SPLIT>(D, Bh, Bl);
+    hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
+    move_vector<NT>(D, moving_step, use_div, c, mv);
+}
+
 // ---- motion network, fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2) ------------------------------------------
 template <int NT, int THREADS>
 __global__ __launch_bounds__(THREADS) void move_kernel(MoveArgs A)
 {
     constexpr int WAVES = THREADS / kWave;
     constexpr int TILE = 16 * NT;
-    using BL = Blob<false>;
     __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -266,45 +381,17 @@ __global__ __launch_bounds__(THREADS) void move_kernel(MoveArgs A)
         int lds_off = 0;
         asm volatile("" : "+v"(lds_off));
         const float *const lw = lds + lds_off;
-        float px[NT][3], tq[NT];
+        float px[NT][3], tq[NT], mv[NT][3];
         load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
-
-        float B[NT][16];
-        f4 D[NT][4];
-        // tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const bool odd = (g & 1) != 0;
-            const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
-            const float vxy = odd ? px[j][1] : px[j][0];
-            float p0, p1;
-            det_sinpi_both(vxy * sc0, p0, p1);
-            auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-            B[j][0] = __uint_as_float(sw[0]); B[j][2] = __uint_as_float(sw[1]);
-            det_sinpi_both(vxy * sc1, p0, p1);
-            sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-            B[j][1] = __uint_as_float(sw[0]); B[j][3] = __uint_as_float(sw[1]);
-            const float scz = odd ? sc1 : sc0;
-            det_sinpi_both(px[j][2] * scz, p0, p1);
-            sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-            B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
+        const auto time = [&](int j, float &f0, float &f1) {
             if (shared_time) {
-                B[j][6] = t_feat[0];
-                B[j][7] = t_feat[1];
+                f0 = t_feat[0]; f1 = t_feat[1];
             } else {
-                det_sinpi_both(tq[j] * scz, p0, p1);
-                sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-                B[j][6] = __uint_as_float(sw[0]); B[j][7] = __uint_as_float(sw[1]);
+                time_features(tq[j], g, f0, f1);
             }
-        }
-        mlp_layer<8, 4, NT>(lw + BL::M0, lane, B, D);
-        to_operand<4, true, NT>(D, B);
-        mlp_layer<16, 4, NT>(lw + BL::M1, lane, B, D);
-        to_operand<4, true, NT>(D, B);
-        mlp_layer<16, 4, NT>(lw + BL::M2, lane, B, D);
-        to_operand<4, true, NT>(D, B);
-        mlp_layer<16, 1, NT>(lw + BL::M3, lane, B, D);
-        move_store<NT>(A, D, px, tile * TILE, n_eff, g, c);
+        };
+        motion_move<NT>(lw, lane, px, time, A.moving_step, A.use_div, mv);
+        move_store<NT>(A, mv, px, tile * TILE, n_eff, g, c);
     }
 }
 
@@ -315,7 +402,6 @@ __global__ __launch_bounds__(THREADS) void move_half_kernel(MoveArgs A)
     static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
     constexpr int WAVES = THREADS / kWave;
     constexpr int TILE = 16 * NT;
-    using BL = HalfBlob<false>;
     __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -334,31 +420,158 @@ __global__ __launch_bounds__(THREADS) void move_half_kernel(MoveArgs A)
         asm volatile("" : "+v"(lds_off));
         const _Float16 *const whi = lds + lds_off;
         const _Float16 *const wlo = whi + kMotionHalves;
-        float px[NT][3], tq[NT];
+        float px[NT][3], tq[NT], mv[NT][3];
         load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
+        motion_move_half<SPLIT, K32, NT>(whi, wlo, lane, px, tq, A.moving_step, A.use_div, mv);
+        move_store<NT>(A, mv, px, tile * TILE, n_eff, g, c);
+    }
+}
 
-        h8 Bh[NT][2], Bl[NT][2];
-        f4 D[NT][4];
-        // tcnn Frequency(4): lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
+// ---- the warp's inverse: x + move(x, t) = target by fixed-point iteration (include/cednerf_hip.h states it) -----------
+// A wave tile keeps target, time and the iterate of its 32 rows in registers (every lane group holds the same copy of
+// column c's rows) and calls the motion network's device function once per round.  A row that has met `step <= tol`
+// is frozen: its registers no longer take the round's result, so its outputs are those of the round it stopped at
+// whatever the other rows of the tile do (and MFMA columns do not mix).  The loop leaves early only when the ballot
+// finds no active row in the wave; rows past n are never active.
+template <int NT> struct TrackRows {
+    float target[NT][3], px[NT][3], tq[NT], step[NT];
+    int evals[NT];
+    bool active[NT];
+};
+
+template <int NT>
+__device__ __forceinline__ void track_load(const TrackArgs &A, int64_t tile_base, int c, TrackRows<NT> &R)
+{
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            float v = tq[j];
-            v = (g == 0) ? px[j][0] : v;
-            v = (g == 1) ? px[j][1] : v;
-            v = (g == 2) ? px[j][2] : v;
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
-            to_half8<SPLIT>(f, Bh[j][0], Bl[j][0]);
+    for (int j = 0; j < NT; ++j) {
+        const int64_t row = tile_base + 16 * j + c;
+        const int64_t s = row < A.n ? row : A.n - 1;                     // a ragged last tile repeats the last row
+        int64_t sp = s, st = s;
+        if (A.bcast) {
+            st = s / A.n_points;
+            sp = s - st * A.n_points;
         }
-        mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bh, Bl, D);
-        to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bh, Bl, D);
-        to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bh, Bl, D);
-        to_operand_h<NT, SPLIT>(D, Bh, Bl);
-        hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
-        move_store<NT>(A, D, px, tile * TILE, n_eff, g, c);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            R.target[j][a] = A.target[3 * sp + a];
+            R.px[j][a] = A.init ? A.init[3 * sp + a] : R.target[j][a];
+        }
+        R.tq[j] = A.t[st];
+        R.step[j] = __builtin_inff();
+        R.evals[j] = 0;
+        R.active[j] = row < A.n;
+    }
+}
+
+// one round on the rows still active: x_new = target - move, step = max_a |x_new[a] - x[a]|, freeze at step <= tol.
+// Returns whether any row of this lane is still active.
+template <int NT>
+__device__ __forceinline__ bool track_update(const float (&mv)[NT][3], float tol, TrackRows<NT> &R)
+{
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        float xn[3], d[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            xn[a] = R.target[j][a] - mv[j][a];
+            d[a] = __builtin_fabsf(xn[a] - R.px[j][a]);
+        }
+        const float step = fmaxf(fmaxf(d[0], d[1]), d[2]);
+        const bool on = R.active[j];                                     // a frozen row keeps what it has
+#pragma unroll
+        for (int a = 0; a < 3; ++a) R.px[j][a] = on ? xn[a] : R.px[j][a];
+        R.step[j] = on ? step : R.step[j];
+        R.evals[j] += on ? 1 : 0;
+        R.active[j] = on && !(step <= tol);                              // a NaN step stays active
+        any = any || R.active[j];
+    }
+    return any;
+}
+
+// lane group a < 3 stores component a of x, lane group 3 step and evals
+template <int NT>
+__device__ __forceinline__ void track_store(const TrackArgs &A, const TrackRows<NT> &R, int64_t tile_base, int g, int c)
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int64_t s = tile_base + 16 * j + c;
+        const float x0 = R.px[j][0], x1 = R.px[j][1], x2 = R.px[j][2];
+        const float o = (g == 0) ? x0 : (g == 1) ? x1 : x2;
+        if (s >= A.n) continue;
+        if (g == 3) {
+            if (A.step) A.step[s] = R.step[j];
+            if (A.evals) A.evals[s] = R.evals[j];
+            continue;
+        }
+        if (A.x) A.x[3 * s + g] = o;
+    }
+}
+
+template <int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void track_kernel(TrackArgs A)
+{
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        TrackRows<NT> R;
+        track_load<NT>(A, tile * TILE, c, R);
+        float tf[NT][2];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) time_features(R.tq[j], g, tf[j][0], tf[j][1]);   // the time does not move: once per tile
+        const auto time = [&](int j, float &f0, float &f1) { f0 = tf[j][0]; f1 = tf[j][1]; };
+        for (int it = 0; it < A.max_iters; ++it) {
+            // opaque LDS base per round: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
+            int lds_off = 0;
+            asm volatile("" : "+v"(lds_off));
+            float mv[NT][3];
+            motion_move<NT>(lds + lds_off, lane, R.px, time, A.moving_step, A.use_div, mv);
+            if (__ballot(track_update<NT>(mv, A.tol, R)) == 0) break;    // wave-uniform
+        }
+        track_store<NT>(A, R, tile * TILE, g, c);
+    }
+}
+
+template <bool SPLIT, bool K32, int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void track_half_kernel(TrackArgs A)
+{
+    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
+    if constexpr (SPLIT)
+        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        TrackRows<NT> R;
+        track_load<NT>(A, tile * TILE, c, R);
+        for (int it = 0; it < A.max_iters; ++it) {
+            int lds_off = 0;
+            asm volatile("" : "+v"(lds_off));
+            const _Float16 *const whi = lds + lds_off;
+            float mv[NT][3];
+            motion_move_half<SPLIT, K32, NT>(whi, whi + kMotionHalves, lane, R.px, R.tq, A.moving_step, A.use_div, mv);
+            if (__ballot(track_update<NT>(mv, A.tol, R)) == 0) break;    // wave-uniform
+        }
+        track_store<NT>(A, R, tile * TILE, g, c);
     }
 }
 
@@ -550,6 +763,32 @@ static int launch_move(const ced_field_desc *d, MoveArgs &A, const char *who, vo
     return check_launch(who);
 }
 
+// the fixed-point kernel for the descriptor's arithmetic: launch_move's four variants, the same launch geometry
+static int launch_track(const ced_field_desc *d, TrackArgs &A, const char *who, void *stream)
+{
+    A.moving_step = d->moving_step;
+    A.use_div = d->use_div_offsets ? 1 : 0;
+    A.weights = d->packed_weights;
+    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
+    const int mw = d->max_workgroups;
+    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
+        launch_tiles<2, 512>(track_kernel<2, 512>, A, A.n, 2, mw, stream);
+    else if (d->mlp_precision == CED_MLP_F16)
+        launch_tiles<2, 512>(track_half_kernel<false, false, 2, 512>, A, A.n, 2, mw, stream);
+    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
+        launch_tiles<2, 512>(track_half_kernel<true, true, 2, 512>, A, A.n, 2, mw, stream);
+    else
+        launch_tiles<2, 512>(track_half_kernel<true, false, 2, 512>, A, A.n, 2, mw, stream);
+    return check_launch(who);
+}
+
+static int validate_solve(int32_t max_iters, float tol, const char *who)
+{
+    CED_REQUIRE(max_iters >= 1 && max_iters <= 1024, "%s: max_iters=%d outside 1 .. 1024", who, max_iters);
+    CED_REQUIRE(tol >= 0.0f, "%s: tol=%g must be >= 0 (and not a NaN)", who, (double)tol);
+    return CED_OK;
+}
+
 // the head's kernel for the descriptor's arithmetic, on rows given one by one (ced_field_rgb) or as embedding x direction
 template <bool BCAST> static int launch_rgb(const ced_field_desc *desc, RgbArgs &A, const char *who, void *stream)
 {
@@ -615,6 +854,50 @@ extern "C" int ced_field_move_rays(const ced_field_desc *desc, int64_t n, const 
     A.rays_mode = 1; A.t_per_ray = t_per_ray ? 1 : 0;
     A.move = move; A.x_norm = x_norm;
     return ced::launch_move(desc, A, "field_move_rays", stream);
+}
+
+extern "C" int ced_field_move_inverse(const ced_field_desc *desc, int64_t n, const float *target, const float *t,
+                                      const float *init, int32_t max_iters, float tol, float *x, float *step,
+                                      int32_t *evals, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_move_inverse");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_move_inverse: n < 0");
+    rc = ced::validate_solve(max_iters, tol, "field_move_inverse");
+    if (rc) return rc;
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(target && t, "field_move_inverse: null target/t");
+    CED_REQUIRE(x || step || evals, "field_move_inverse: no output requested");
+    ced::TrackArgs A{};
+    A.n = n;
+    A.target = target; A.t = t; A.init = init;
+    A.max_iters = max_iters; A.tol = tol;
+    A.x = x; A.step = step; A.evals = evals;
+    return ced::launch_track(desc, A, "field_move_inverse", stream);
+}
+
+extern "C" int ced_field_track(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target,
+                               const float *times, const float *init, int32_t max_iters, float tol, float *x,
+                               float *step, int32_t *evals, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_track");
+    if (rc) return rc;
+    CED_REQUIRE(n_points >= 0 && n_times >= 0, "field_track: n_points=%lld n_times=%lld", (long long)n_points,
+                (long long)n_times);
+    CED_REQUIRE(n_points <= INT64_MAX / 3 / (n_times > 0 ? n_times : 1), "field_track: n_points * n_times overflows");
+    rc = ced::validate_solve(max_iters, tol, "field_track");
+    if (rc) return rc;
+    if (n_points == 0 || n_times == 0) return CED_OK;
+    CED_REQUIRE(target && times, "field_track: null target/times");
+    CED_REQUIRE(x || step || evals, "field_track: no output requested");
+    ced::TrackArgs A{};
+    A.n = n_points * n_times;
+    A.n_points = n_points;
+    A.bcast = 1;
+    A.target = target; A.t = times; A.init = init;
+    A.max_iters = max_iters; A.tol = tol;
+    A.x = x; A.step = step; A.evals = evals;
+    return ced::launch_track(desc, A, "field_track", stream);
 }
 
 extern "C" int ced_field_rgb(const ced_field_desc *desc, int64_t n, const float *dirs, const float *embedding,

@@ -11,6 +11,10 @@ ced_field_rgb_bcast); the density in between is the field's own `ced_field_forwa
 `extract_mesh` / `extract_mesh_sequence` turn the same lattice of cell centres into a triangle mesh per time step: naive
 surface nets on the device (csrc/mesh.hip), the vertices coloured by the field's own head.  `--mesh` writes them next to
 the volumes.
+
+`extract_mesh_tracked` / `track_mesh` give ONE mesh that moves instead: the mesh of a reference time, its faces shared by
+every time step, its vertices carried through time by inverting the warp (DNGPradianceField.track_points,
+ced_field_track).  `--mesh --mesh_track T_REF` writes it.
 """
 from __future__ import annotations
 
@@ -271,6 +275,55 @@ def extract_mesh(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None
                                  max_cells_per_launch)[0]
 
 
+# ---- a mesh that moves -----------------------------------------------------------------------------------------------
+_REF_KEYS = ("faces", "cube", "sigma", "embedding", "rgb", "normals")
+
+
+@torch.no_grad()
+def track_mesh(field, mesh: Dict, t_src, times: Sequence, max_iters: int = 32, tol: float = 1e-6) -> Dict:
+    """Carry the vertices of `mesh` (a dict from `extract_mesh`, extracted at time t_src) to every time of `times`: each
+    vertex is a material point, its canonical coordinate is query_move(vertex, t_src)[0], and its position at time t
+    solves x + move(x, t) = canonical (`DNGPradianceField.track_points`, started at the vertex).  Returns
+        vertices_t [T,V,3], converged [T,V] bool, step [T,V], evals [T,V] int32, canonical [V,3], times [T], t_ref,
+        faces, cube, sigma, embedding, normals (and rgb if present): the reference mesh's own, valid at t_ref ONLY --
+        faces are shared by all times; normals and colours are not recomputed per time,
+        reso, center, radius, sigma_thresh, apply_act.
+    The iteration has no damping: where the motion network is no contraction a vertex does not converge and is reported
+    in `converged`, its position the last iterate."""
+    max_iters, tol = ops.check_solve(max_iters, tol)
+    t_ref = _time_value(t_src)
+    times = [_time_value(t) for t in times]
+    vertices = mesh["vertices"]
+    if not vertices.is_cuda:
+        raise NotImplementedError(_CPU)
+    with torch.cuda.device(vertices.device):
+        tr = field.track_points(vertices, t_ref, times, max_iters=max_iters, tol=tol)
+    out = {k: mesh[k] for k in _REF_KEYS if k in mesh}
+    out.update({k: mesh[k] for k in ("reso", "center", "radius", "sigma_thresh", "apply_act") if k in mesh})
+    out.update(vertices_t=tr["positions"], converged=tr["converged"], step=tr["step"], evals=tr["evals"],
+               canonical=tr["canonical"], times=times, t_ref=t_ref)
+    return out
+
+
+@torch.no_grad()
+def extract_mesh_tracked(field, t_ref, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None,
+                         estimator=None, apply_act: bool = False, center=None, radius=None,
+                         max_cells_per_launch: int = 1 << 22, max_iters: int = 32, tol: float = 1e-6) -> Dict:
+    """`extract_mesh` at t_ref followed by `track_mesh` to `times`: one mesh with shared faces and per-time vertex
+    positions (see `track_mesh` for the result)."""
+    max_iters, tol = ops.check_solve(max_iters, tol)
+    mesh = extract_mesh(field, t_ref, reso, sigma_thresh, dirs, estimator, apply_act, center, radius, max_cells_per_launch)
+    return track_mesh(field, mesh, t_ref, times, max_iters=max_iters, tol=tol)
+
+
+def tracked_frame(tracked: Dict, k: int) -> Dict:
+    """Time step k of a tracked mesh as a dict `save_mesh_ply` writes: the vertices of that time, the shared faces, the
+    reference colours -- and no normals (they belong to t_ref only)."""
+    out = dict(vertices=tracked["vertices_t"][k], faces=tracked["faces"], t=tracked["times"][k])
+    out.update({key: tracked[key] for key in ("rgb", "apply_act") if key in tracked})
+    return out
+
+
 # ---- files -----------------------------------------------------------------------------------------------------------
 _ARRAYS = ("index", "xyz", "sigma", "embedding", "rgb")
 
@@ -332,26 +385,43 @@ def save_mesh_npz(path: str, mesh: Dict) -> None:
     np.savez(path, **out)
 
 
-def mesh_ply_header(n_vertices: int, n_faces: int) -> bytes:
+_TRACKED_ARRAYS = ("vertices_t", "converged", "step", "evals", "canonical") + _REF_KEYS
+
+
+def save_tracked_npz(path: str, tracked: Dict) -> None:
+    """A tracked mesh as a numpy .npz: vertices_t, converged, step, evals, canonical, times, t_ref, and the reference
+    mesh's faces, cube, sigma, embedding, normals, rgb, reso, center, radius, sigma_thresh -- each if present, so the
+    result of track_mesh on a hand-built mesh dict (vertices and faces only) is saved too -- and apply_act (False if absent)."""
+    out = {k: tracked[k].detach().cpu().numpy() for k in _TRACKED_ARRAYS if k in tracked}
+    out.update(times=np.asarray(tracked["times"], np.float32), t_ref=np.float32(tracked["t_ref"]))
+    kinds = dict(reso=np.int64, center=lambda v: np.asarray(v, np.float32), radius=np.float32, sigma_thresh=np.float32)
+    out.update({k: kind(tracked[k]) for k, kind in kinds.items() if k in tracked})   # track_mesh's rule: what the mesh had
+    out["apply_act"] = np.bool_(tracked.get("apply_act", False))
+    np.savez(path, **out)
+
+
+def mesh_ply_header(n_vertices: int, n_faces: int, normals: bool = True) -> bytes:
     return ("ply\nformat binary_little_endian 1.0\n"
             f"element vertex {int(n_vertices)}\n"
             "property float x\nproperty float y\nproperty float z\n"
-            "property float nx\nproperty float ny\nproperty float nz\n"
+            + ("property float nx\nproperty float ny\nproperty float nz\n" if normals else "") +
             "property uchar red\nproperty uchar green\nproperty uchar blue\n"
             f"element face {int(n_faces)}\n"
             "property list uchar int vertex_indices\nend_header\n").encode("ascii")
 
 
 MESH_PLY_VERTEX = struct.Struct("<ffffffBBB")     # 27 bytes per vertex, no padding
+MESH_PLY_VERTEX_PLAIN = struct.Struct("<fffBBB")  # 15 bytes per vertex of a mesh without normals
 MESH_PLY_FACE = struct.Struct("<Biii")            # 13 bytes per triangle: the count 3, then the vertex ids
 
 
 def save_mesh_ply(path: str, mesh: Dict) -> None:
     """A binary little-endian triangle mesh: x y z nx ny nz red green blue per vertex, a uchar-counted int list per face.
     The colour follows save_ply: the sigmoid of rgb (applied here unless the mesh was extracted with apply_act) averaged
-    over the directions; grey 128 without rgb."""
+    over the directions; grey 128 without rgb.  A mesh without `normals` (a frame of a tracked mesh, `tracked_frame`) is
+    written without the three normal properties: x y z red green blue per vertex."""
     xyz = mesh["vertices"].detach().cpu().numpy().astype("<f4")
-    nrm = mesh["normals"].detach().cpu().numpy().astype("<f4")
+    nrm = mesh["normals"].detach().cpu().numpy().astype("<f4") if "normals" in mesh else None
     tri = mesh["faces"].detach().cpu().numpy().astype("<i4")
     n = xyz.shape[0]
     if "rgb" in mesh:
@@ -361,13 +431,18 @@ def save_mesh_ply(path: str, mesh: Dict) -> None:
         col = np.clip(np.rint(255.0 * rgb.mean(axis=1)), 0, 255).astype(np.uint8)
     else:
         col = np.full((n, 3), 128, np.uint8)
-    vrec = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("rgb", "u1", 3)]))
     frec = np.empty(tri.shape[0], dtype=np.dtype([("n", "u1"), ("ids", "<i4", 3)]))
-    assert vrec.dtype.itemsize == MESH_PLY_VERTEX.size and frec.dtype.itemsize == MESH_PLY_FACE.size
-    vrec["xyz"], vrec["normal"], vrec["rgb"] = xyz, nrm, col
+    if nrm is None:
+        vrec = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)]))
+        assert vrec.dtype.itemsize == MESH_PLY_VERTEX_PLAIN.size and frec.dtype.itemsize == MESH_PLY_FACE.size
+        vrec["xyz"], vrec["rgb"] = xyz, col
+    else:
+        vrec = np.empty(n, dtype=np.dtype([("xyz", "<f4", 3), ("normal", "<f4", 3), ("rgb", "u1", 3)]))
+        assert vrec.dtype.itemsize == MESH_PLY_VERTEX.size and frec.dtype.itemsize == MESH_PLY_FACE.size
+        vrec["xyz"], vrec["normal"], vrec["rgb"] = xyz, nrm, col
     frec["n"], frec["ids"] = 3, tri
     with open(path, "wb") as f:
-        f.write(mesh_ply_header(n, tri.shape[0]))
+        f.write(mesh_ply_header(n, tri.shape[0], normals=nrm is not None))
         f.write(vrec.tobytes())
         f.write(frec.tobytes())
 
@@ -404,6 +479,11 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--mesh_dirs", type=parse_mesh_dirs, default="normal", metavar="normal|N",
                    help="view directions of the mesh colours: 'normal' (every vertex head-on) or N directions spread over "
                         "the sphere and averaged (0: no colour)")
+    p.add_argument("--mesh_track", type=float, default=None, metavar="T_REF",
+                   help="with --mesh: also write ONE mesh that moves -- the mesh of time T_REF, its vertices tracked to every "
+                        "time of --times by inverting the warp: tracked_%%04d.ply per time and tracked.npz")
+    p.add_argument("--track_iters", type=int, default=32, help="--mesh_track: most evaluations of the motion network per vertex and time")
+    p.add_argument("--track_tol", type=float, default=1e-6, help="--mesh_track: a vertex has converged when its last update is <= this")
     p.add_argument("--device", default="cuda")
     p.add_argument("--out", required=True, metavar="DIR")
     return p
@@ -436,6 +516,8 @@ def main(argv=None) -> int:
     a = make_parser().parse_args(argv)
     if a.n_dirs < 0:
         raise SystemExit("--n_dirs must be >= 0")
+    if a.mesh_track is not None and not a.mesh:
+        raise SystemExit("--mesh_track needs --mesh")
     extra = {} if a.moving_step is None else dict(moving_step=a.moving_step)
     cfg = trainer.resolve_config(a.preset, None, log2_hashmap_size=a.log2_hashmap_size, **extra)
     ckpt = checkpoint.read_checkpoint(a.load_model)
@@ -468,6 +550,21 @@ def main(argv=None) -> int:
             save_mesh_ply(stem + ".ply", mesh)
             print(f"t={mesh['t']:g}: {mesh['vertices'].shape[0]} vertices, {mesh['faces'].shape[0]} triangles -> "
                   f"{stem}.npz / .ply", flush=True)
+        if a.mesh_track is not None:
+            tracked = extract_mesh_tracked(field, a.mesh_track, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh,
+                                           dirs=mesh_dirs, estimator=None if a.no_occupancy else estimator,
+                                           max_iters=a.track_iters, tol=a.track_tol)
+            save_tracked_npz(os.path.join(a.out, "tracked.npz"), tracked)
+            n_vertices = tracked["vertices_t"].shape[1]
+            lost = (~tracked["converged"]).sum(dim=1).tolist()
+            for i, t in enumerate(tracked["times"]):
+                stem = os.path.join(a.out, f"tracked_{i:04d}")
+                save_mesh_ply(stem + ".ply", tracked_frame(tracked, i))
+                share = 100.0 * lost[i] / max(n_vertices, 1)
+                print(f"t={t:g}: {n_vertices} vertices tracked from t_ref={tracked['t_ref']:g}, {lost[i]} ({share:.2f} %) "
+                      f"not converged -> {stem}.ply", flush=True)
+            print(f"tracked mesh: {tracked['faces'].shape[0]} shared triangles -> {os.path.join(a.out, 'tracked.npz')}",
+                  flush=True)
     return 0
 
 

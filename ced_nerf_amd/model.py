@@ -233,6 +233,49 @@ class DNGPradianceField(torch.nn.Module):
         return x_move, move
 
     @torch.no_grad()
+    def query_move_inverse(self, c: torch.Tensor, t: torch.Tensor, max_iters: int = 32, tol: float = 1e-6,
+                           init: Optional[torch.Tensor] = None):
+        """The inverse of the warp: per row the x with x + move(x, t) = c, `move` being `query_move`'s.  The density at
+        (x, t) is the canonical density at x + move(x, t), so x is where the material point with canonical coordinate c
+        sits at time t.  Solved by fixed-point iteration x <- c - move(x, t) from init (default: c), at most max_iters
+        (1 .. 1024) evaluations of the motion network in this field's mlp_precision, stopped when the largest component
+        of the update is <= tol (ced_field_move_inverse; include/cednerf_hip.h states it operation by operation).
+        c is viewed as [-1, 3], t as [-1]; returns (x [N,3], step [N] the size of the last update, evals [N] int32).  A
+        row has converged iff step <= tol; the iteration converges where move(., t) is a contraction and reports the
+        rows where it did not (evals == max_iters, step > tol) instead of hiding them."""
+        max_iters, tol = ops.check_solve(max_iters, tol)
+        if not (c.is_cuda and t.is_cuda and (init is None or init.is_cuda)):
+            raise NotImplementedError("Only support cuda inputs: query_move_inverse runs on the HIP kernel (no CPU fallback).")
+        return ops.field_move_inverse(self._descriptor(), c.reshape(-1, 3).float().contiguous(),
+                                      t.reshape(-1).float().contiguous(),
+                                      None if init is None else init.reshape(-1, 3).float().contiguous(), max_iters, tol)
+
+    @torch.no_grad()
+    def track_points(self, x: torch.Tensor, t_src, times, max_iters: int = 32, tol: float = 1e-6) -> Dict:
+        """Where the material points seen at x [P,3] at time t_src (a number, a one-element tensor or [P]) sit at every
+        time of `times` ([T]: a sequence or a tensor).  Returns a dict:
+            canonical [P,3]  query_move(x, t_src)[0], the points' canonical coordinates,
+            positions [T,P,3], step [T,P], evals [T,P] int32  `query_move_inverse`(canonical, times[k]) started at x,
+            converged [T,P] bool  step <= tol,
+            times [T].
+        One launch for all P x T rows (ced_field_track), neither input expanded in memory."""
+        max_iters, tol = ops.check_solve(max_iters, tol)
+        if not x.is_cuda:
+            raise NotImplementedError("Only support cuda inputs: track_points runs on the HIP kernels (no CPU fallback).")
+        pts = x.reshape(-1, 3).float().contiguous()
+        n = pts.shape[0]
+        ts = torch.as_tensor(t_src, dtype=torch.float32, device=pts.device).reshape(-1)
+        if ts.numel() == 1:
+            ts = ts.expand(n)
+        elif ts.numel() != n:
+            raise ValueError(f"t_src must be a scalar or hold one time per point ({n}), got {ts.numel()} values")
+        tt = torch.as_tensor(times, dtype=torch.float32, device=pts.device).reshape(-1).contiguous()
+        desc = self._descriptor()
+        canonical = ops.field_move(desc, pts, ts.contiguous(), want=(True, False, False, False))[0]
+        positions, step, evals = ops.field_track(desc, canonical, tt, pts, max_iters, tol)
+        return dict(canonical=canonical, positions=positions, step=step, evals=evals, converged=step <= tol, times=tt)
+
+    @torch.no_grad()
     def _query_rgb(self, dir: torch.Tensor, embedding: torch.Tensor, apply_act: bool = True):
         """cednerf/model.py:447-466: colour from view directions and the density branch's embedding
         (results['base_mlp_out']): dir is normalised, mapped to [0, 1] and SH-encoded, mlp_head runs on

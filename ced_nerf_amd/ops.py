@@ -305,6 +305,63 @@ def field_move_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_starts,
     return move, x_norm
 
 
+MAX_SOLVE_ITERS = 1024                            # ced_field_move_inverse / ced_field_track: 1 <= max_iters <= 1024
+
+
+def check_solve(max_iters, tol):
+    """(max_iters, tol) of the fixed-point solve as (int, float), or ValueError: an int in 1 .. 1024, a number >= 0."""
+    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or not 1 <= int(max_iters) <= MAX_SOLVE_ITERS:
+        raise ValueError(f"max_iters must be an int in 1 .. {MAX_SOLVE_ITERS}, got {max_iters!r}")
+    try:
+        tol_f = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"tol must be a number >= 0, got {tol!r}") from None
+    if not tol_f >= 0.0:                          # refuses a NaN too
+        raise ValueError(f"tol must be a number >= 0, got {tol!r}")
+    return int(max_iters), tol_f
+
+
+def field_move_inverse(desc: _lib.FieldDesc, target, t, init=None, max_iters: int = 32, tol: float = 1e-6):
+    """ced_field_move_inverse: per row the solution x of x + move(x, t) = target by fixed-point iteration from init (or
+    from target), at most max_iters evaluations, stopped at step <= tol.  target [n,3], t [n], init [n,3] or None ->
+    (x [n,3], step [n], evals [n] int32); include/cednerf_hip.h states the iteration."""
+    max_iters, tol = check_solve(max_iters, tol)
+    _chk(target, torch.float32, "target"); _chk(t, torch.float32, "t"); _chk(init, torch.float32, "init", allow_none=True)
+    n = target.shape[0]
+    if target.shape != (n, 3) or t.numel() != n or (init is not None and init.shape != (n, 3)):
+        raise ValueError(f"target [n,3], t [n], init [n,3]: got {list(target.shape)}, {list(t.shape)}, "
+                         f"{None if init is None else list(init.shape)}")
+    dev = target.device
+    x = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    step = torch.empty((n,), device=dev, dtype=torch.float32)
+    evals = torch.empty((n,), device=dev, dtype=torch.int32)
+    rc = _lib.lib().ced_field_move_inverse(C.byref(desc), n, _p(target), _p(t), _p(init), max_iters, tol, _p(x), _p(step),
+                                           _p(evals), _stream())
+    _lib.check(rc, "field_move_inverse")
+    return x, step, evals
+
+
+def field_track(desc: _lib.FieldDesc, target, times, init=None, max_iters: int = 32, tol: float = 1e-6):
+    """ced_field_track: `field_move_inverse` for every (time, point) pair without expanding either input.  target [P,3],
+    times [T], init [P,3] or None (shared by all times) -> (x [T,P,3], step [T,P], evals [T,P] int32), each row with
+    the bits of `field_move_inverse` on the expanded rows."""
+    max_iters, tol = check_solve(max_iters, tol)
+    _chk(target, torch.float32, "target"); _chk(times, torch.float32, "times")
+    _chk(init, torch.float32, "init", allow_none=True)
+    p, nt = target.shape[0], times.shape[0]
+    if target.shape != (p, 3) or times.shape != (nt,) or (init is not None and init.shape != (p, 3)):
+        raise ValueError(f"target [P,3], times [T], init [P,3]: got {list(target.shape)}, {list(times.shape)}, "
+                         f"{None if init is None else list(init.shape)}")
+    dev = target.device
+    x = torch.empty((nt, p, 3), device=dev, dtype=torch.float32)
+    step = torch.empty((nt, p), device=dev, dtype=torch.float32)
+    evals = torch.empty((nt, p), device=dev, dtype=torch.int32)
+    rc = _lib.lib().ced_field_track(C.byref(desc), p, nt, _p(target), _p(times), _p(init), max_iters, tol, _p(x), _p(step),
+                                    _p(evals), _stream())
+    _lib.check(rc, "field_track")
+    return x, step, evals
+
+
 def field_rgb(desc: _lib.FieldDesc, directions, embedding, apply_act: bool = True):
     """ced_field_rgb: mlp_head on [SH(directions), embedding [n,15]] -> rgb [n,3] (sigmoid iff apply_act)."""
     _chk(directions, torch.float32, "directions"); _chk(embedding, torch.float32, "embedding")

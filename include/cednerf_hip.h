@@ -278,6 +278,34 @@ int ced_field_move_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_
                         const int64_t *ray_indices, const float *t_starts, const float *t_ends,
                         const float *timestamps, int32_t t_per_ray, float *move, float *x_norm, void *stream);
 
+/* ---- the warp's inverse: where a material point sits at time t ----
+ * The density at (x, t) is the canonical density at c = x + move(x, t), `move` being ced_field_move's.  A material point
+ * with canonical coordinate c therefore sits at time t at the solution x of  x + move(x, t) = c.  These entries solve it
+ * by fixed-point iteration.  Per row, with target c, time t, a start (init's row, or c when init is NULL),
+ * max_iters = K (1 .. 1024) and tol (>= 0), every operation in fp32 with one rounding:
+ *     x = start; evals = 0; step = +inf
+ *     repeat while evals < K:
+ *         m = move(x, t)                      -- ced_field_move's `move` at (x, t) in desc->mlp_precision, bit for bit
+ *         x_new[a] = c[a] - m[a]              -- one subtraction per component
+ *         step = fmaxf(fmaxf(|x_new[0] - x[0]|, |x_new[1] - x[1]|), |x_new[2] - x[2]|)
+ *         x = x_new; evals += 1
+ *         if step <= tol: stop                -- false for a NaN step: such a row runs all K rounds
+ * Outputs: x [n,3], step [n] (the size of the last update), evals [n] int32; each may be NULL, not all.  A row has
+ * converged iff step <= tol.  There is no damping, no Newton step and no Jacobian: the iteration converges where
+ * move(., t) is a contraction (its Lipschitz constant scales with moving_step) and reports the rows where it did not
+ * through step and evals == K.  A row's result does not depend on n or on the other rows: a finished row is frozen while
+ * its wave goes on, and a wave stops early only when all of its rows are frozen. */
+int ced_field_move_inverse(const ced_field_desc *desc, int64_t n, const float *target, const float *t,
+                           const float *init, int32_t max_iters, float tol, float *x, float *step,
+                           int32_t *evals, void *stream);
+
+/* The same for every (time, point) pair without expanding either input: row r = k * n_points + p takes times[k]
+ * ([n_times]), target[p] and init[p] ([n_points,3]; init may be NULL); x [n_times, n_points, 3], step and evals
+ * [n_times, n_points].  Each row has the bits of ced_field_move_inverse on the expanded rows. */
+int ced_field_track(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target,
+                    const float *times, const float *init, int32_t max_iters, float tol, float *x,
+                    float *step, int32_t *evals, void *stream);
+
 /* DNGPradianceField._query_rgb(dir, embedding, apply_act) -- cednerf/model.py:447-466: dirs [n,3] are normalised,
  * mapped to [0,1], SH degree 2; mlp_head on [SH(4), embedding(15)]; the sigmoid iff apply_act.  embedding [n,15] is what
  * ced_field_forward writes to `geo`; rgb [n,3].  The head runs in the arithmetic of desc->mlp_precision. */
