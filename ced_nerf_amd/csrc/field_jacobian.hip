@@ -1,0 +1,573 @@
+// The derivative of the motion network: ced_field_move_jacobian hands out move(x, t) and its 3 x 4 Jacobian with respect
+// to (x, y, z, t) from one launch, and ced_field_move_inverse_newton / ced_field_track_newton solve x + move(x, t) = c by
+// Newton's method on that Jacobian, the iterate held in registers (include/cednerf_hip.h states every operation).
+//
+// Forward mode: the Jacobian of a sample is four tangent vectors pushed through the four layers beside the primal.  A
+// tangent is one more MFMA column, so the tangents of a 16-sample primal tile are four 16-column operand tiles that go
+// through the SAME layer functions on the same staged weights (mlp_layer; mlp_layer_h / hidden_fed_layer), in the
+// arithmetic the descriptor selects: MFMA columns do not mix, so the primal tile computes ced_field_move's bits whatever
+// stands beside it.  The encoding's tangent is built from the primal features the lane already holds (the derivative of
+// sin(2^k pi v + phase) is 2^k pi times the other phase of the same frequency, negated for a cosine), a hidden layer's
+// tangent is zeroed wherever the PRIMAL pre-activation is not > 0, and the output applies the tanh's derivative
+// 1 - th^2 to the fine offsets.
+//
+// Shape: field_move.hip's (persistent workgroups of 512 threads, the motion network's layers staged into LDS once), with
+// ONE 16-sample primal tile per wave iteration instead of two: primal + four tangents are five operand tiles and five
+// accumulator tiles (80 + 80 registers on the fp32 chain), which fit the 256 registers of a wave at two waves per SIMD
+// without scratch; two primal tiles would not.
+#include "field_move_device.hpp"
+
+namespace ced {
+
+struct JacArgs {
+    int64_t n;
+    const float *pos, *t;                             // [n,3], [n]
+    float *move, *jac;                                // [n,3], [n,12]; either may be null
+    float moving_step;
+    int use_div;
+    const void *weights;
+    int64_t lo_halves;
+};
+
+constexpr int kDirs = 4;                              // tangent directions: x, y, z, t
+constexpr float kPiF = 3.14159274101257324f;          // the pi of det_sinpi_phase
+
+// The two encodings, line for line as motion_move / motion_move_half state them (field_move_device.hpp), on their own
+// here because the tangents are built from the features before the first layer consumes them.
+// fp32 chain: tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g): B[j][0 .. 7]
+template <int NT, typename Time>
+__device__ __forceinline__ void motion_encode(const float (&px)[NT][3], Time time, int g, float (&B)[NT][16])
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const bool odd = (g & 1) != 0;
+        const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
+        const float vxy = odd ? px[j][1] : px[j][0];
+        float p0, p1;
+        det_sinpi_both(vxy * sc0, p0, p1);
+        auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+        B[j][0] = __uint_as_float(sw[0]); B[j][2] = __uint_as_float(sw[1]);
+        det_sinpi_both(vxy * sc1, p0, p1);
+        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+        B[j][1] = __uint_as_float(sw[0]); B[j][3] = __uint_as_float(sw[1]);
+        const float scz = odd ? sc1 : sc0;
+        det_sinpi_both(px[j][2] * scz, p0, p1);
+        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
+        B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
+        time(j, B[j][6], B[j][7]);
+    }
+}
+
+// fp16 operands: lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
+__device__ __forceinline__ void motion_features_half(const float (&px)[3], float tq, int g, float (&f)[8])
+{
+    float v = tq;
+    v = (g == 0) ? px[0] : v;
+    v = (g == 1) ? px[1] : v;
+    v = (g == 2) ? px[2] : v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
+}
+
+// ---- tangents on the fp32 MFMA chain ---------------------------------------------------------------------------------
+// Tangent tile 4j + b of primal tile j is d/d(x,y,z,t)_b.  Feature k = 4S + g of the operand (lane group g, k-step S)
+// belongs to dimension S / 2, frequency 2^(g/2) (S even) or 4 * 2^(g/2) (S odd), phase g & 1; its partner of the other
+// phase sits on lane group g ^ 1 of the same k-step.
+template <int NP>
+__device__ __forceinline__ void encode_tangent(const float (&Bp)[NP][16], int g, float (&Bt)[kDirs * NP][16])
+{
+    const float sc0 = (float)(1 << (g >> 1));
+    const float w0 = kPiF * sc0, w1 = kPiF * (4.0f * sc0);              // exact: powers of two
+    const bool cosine = (g & 1) != 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+#pragma unroll
+        for (int S = 0; S < 8; ++S) {
+            const float partner = __shfl_xor(Bp[j][S], 16, 64);
+            const float w = (S & 1) != 0 ? w1 : w0;
+            const float d = (cosine ? -w : w) * partner;
+#pragma unroll
+            for (int b = 0; b < kDirs; ++b) Bt[kDirs * j + b][S] = (S >> 1) == b ? d : 0.0f;
+        }
+#pragma unroll
+        for (int b = 0; b < kDirs; ++b) {
+#pragma unroll
+            for (int S = 8; S < 16; ++S) Bt[kDirs * j + b][S] = 0.0f;
+        }
+    }
+}
+
+// a hidden layer's tangents as the next layer's operand: zero wherever the primal pre-activation is not > 0
+template <int NP>
+__device__ __forceinline__ void tangent_operand(const f4 (&Dp)[NP][4], const f4 (&Dt)[kDirs * NP][4], float (&Bt)[kDirs * NP][16])
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+#pragma unroll
+        for (int b = 0; b < kDirs; ++b) {
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) Bt[kDirs * j + b][4 * nb + q] = Dp[j][nb][q] > 0.0f ? Dt[kDirs * j + b][nb][q] : 0.0f;
+            }
+        }
+    }
+}
+
+// jac[4a + b] = d move_a / d(x,y,z,t)_b from the last layer's accumulators, rows placed as move_vector reads them:
+//   without fine offsets   (d off_a) * step
+//   with                   (d off_a + (1 - th_a * th_a) * d fine_a) * step,   th_a = move_vector's tanh value
+// every operation rounded on its own.  Every lane gets all twelve entries of its column's samples.
+template <int NP>
+__device__ __forceinline__ void jacobian_vector(const f4 (&Dp)[NP][4], const f4 (&Dt)[kDirs * NP][4], float moving_step, int use_div,
+                                                int c, float (&J)[NP][12])
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            constexpr int kFineReg[3] = { 3, 0, 1 };
+            const int fine_lane = (a == 0) ? c : 16 + c;
+            float slope = 0.0f;
+            if (use_div) {
+                const float fine = __shfl(Dp[j][0][kFineReg[a]], fine_lane, 64);
+                const float e = det_expf(2.0f * fine);
+                const float th = 1.0f - 2.0f / (e + 1.0f);
+                slope = 1.0f - th * th;
+            }
+#pragma unroll
+            for (int b = 0; b < kDirs; ++b) {
+                float v = __shfl(Dt[kDirs * j + b][0][a], c, 64);
+                if (use_div) {
+                    const float dfine = __shfl(Dt[kDirs * j + b][0][kFineReg[a]], fine_lane, 64);
+                    v = v + slope * dfine;
+                }
+                J[j][4 * a + b] = v * moving_step;
+            }
+        }
+    }
+}
+
+// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): motion_move with the four tangent tiles beside each primal tile
+template <int NP, typename Time>
+__device__ __forceinline__ void motion_move_jacobian(const float *lw, int lane, const float (&px)[NP][3], Time time,
+                                                     float moving_step, int use_div, float (&mv)[NP][3], float (&J)[NP][12])
+{
+    using BL = Blob<false>;
+    constexpr int NTT = kDirs * NP;
+    const int g = lane >> 4, c = lane & 15;
+    float Bp[NP][16], Bt[NTT][16];
+    f4 Dp[NP][4], Dt[NTT][4];
+    motion_encode<NP>(px, time, g, Bp);
+    encode_tangent<NP>(Bp, g, Bt);
+    mlp_layer<8, 4, NP>(lw + BL::M0, lane, Bp, Dp);
+    mlp_layer<8, 4, NTT>(lw + BL::M0, lane, Bt, Dt);
+    tangent_operand<NP>(Dp, Dt, Bt);
+    to_operand<4, true, NP>(Dp, Bp);
+    mlp_layer<16, 4, NP>(lw + BL::M1, lane, Bp, Dp);
+    mlp_layer<16, 4, NTT>(lw + BL::M1, lane, Bt, Dt);
+    tangent_operand<NP>(Dp, Dt, Bt);
+    to_operand<4, true, NP>(Dp, Bp);
+    mlp_layer<16, 4, NP>(lw + BL::M2, lane, Bp, Dp);
+    mlp_layer<16, 4, NTT>(lw + BL::M2, lane, Bt, Dt);
+    tangent_operand<NP>(Dp, Dt, Bt);
+    to_operand<4, true, NP>(Dp, Bp);
+    mlp_layer<16, 1, NP>(lw + BL::M3, lane, Bp, Dp);
+    mlp_layer<16, 1, NTT>(lw + BL::M3, lane, Bt, Dt);
+    move_vector<NP>(Dp, moving_step, use_div, c, mv);
+    jacobian_vector<NP>(Dp, Dt, moving_step, use_div, c, J);
+}
+
+// ---- tangents on the fp16 MFMAs ----------------------------------------------------------------------------------------
+// a hidden layer's tangents as the next layer's operand: zero wherever the primal pre-activation is not > 0, saturated to
+// the fp16 range on both sides, rounded (f16) or split (f16x2) exactly as to_operand_h treats the primal
+template <int NP, bool SPLIT>
+__device__ __forceinline__ void tangent_operand_h(const f4 (&Dp)[NP][4], const f4 (&Dt)[kDirs * NP][4], h8 (&Bh)[kDirs * NP][2],
+                                                  h8 (&Bl)[kDirs * NP][2])
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+#pragma unroll
+        for (int b = 0; b < kDirs; ++b) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float d = __builtin_amdgcn_fmed3f(Dt[kDirs * j + b][2 * ks + (e >> 2)][e & 3], -kHalfMax, kHalfMax);
+                    v[e] = Dp[j][2 * ks + (e >> 2)][e & 3] > 0.0f ? d : 0.0f;
+                }
+                to_half8<SPLIT>(v, Bh[kDirs * j + b][ks], Bl[kDirs * j + b][ks]);
+            }
+        }
+    }
+}
+
+// fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2; K32: the blob has half_kernel_k32's placements): motion_move_half with the four
+// tangent tiles beside each primal tile.  Lane group g owns dimension g, so the tangent of direction b is nonzero on
+// lane group b alone: element e = 2 * freq + phase is 2^freq pi times element e ^ 1, negated for a cosine, formed in
+// fp32 from the fp32 features and then rounded / split like them.
+template <bool SPLIT, bool K32, int NP>
+__device__ __forceinline__ void motion_move_jacobian_half(const _Float16 *whi, const _Float16 *wlo, int lane, const float (&px)[NP][3],
+                                                          const float (&tq)[NP], float moving_step, int use_div, float (&mv)[NP][3],
+                                                          float (&J)[NP][12])
+{
+    using BL = HalfBlob<false>;
+    constexpr int NTT = kDirs * NP;
+    const int g = lane >> 4, c = lane & 15;
+    h8 Bph[NP][2], Bpl[NP][2], Bth[NTT][2], Btl[NTT][2];
+    f4 Dp[NP][4], Dt[NTT][4];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        float f[8], d[8];
+        motion_features_half(px[j], tq[j], g, f);
+        to_half8<SPLIT>(f, Bph[j][0], Bpl[j][0]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float w = kPiF * (float)(1 << (e >> 1));
+            d[e] = ((e & 1) != 0 ? -w : w) * f[e ^ 1];
+        }
+#pragma unroll
+        for (int b = 0; b < kDirs; ++b) {
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (g == b) ? d[e] : 0.0f;
+            to_half8<SPLIT>(v, Bth[kDirs * j + b][0], Btl[kDirs * j + b][0]);
+        }
+    }
+    mlp_layer_h<1, 4, NP, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bph, Bpl, Dp);
+    mlp_layer_h<1, 4, NTT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bth, Btl, Dt);
+    tangent_operand_h<NP, SPLIT>(Dp, Dt, Bth, Btl);
+    to_operand_h<NP, SPLIT>(Dp, Bph, Bpl);
+    hidden_fed_layer<2, 4, NP, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bph, Bpl, Dp);
+    hidden_fed_layer<2, 4, NTT, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bth, Btl, Dt);
+    tangent_operand_h<NP, SPLIT>(Dp, Dt, Bth, Btl);
+    to_operand_h<NP, SPLIT>(Dp, Bph, Bpl);
+    hidden_fed_layer<2, 4, NP, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bph, Bpl, Dp);
+    hidden_fed_layer<2, 4, NTT, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bth, Btl, Dt);
+    tangent_operand_h<NP, SPLIT>(Dp, Dt, Bth, Btl);
+    to_operand_h<NP, SPLIT>(Dp, Bph, Bpl);
+    hidden_fed_layer<2, 1, NP, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bph, Bpl, Dp);
+    hidden_fed_layer<2, 1, NTT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bth, Btl, Dt);
+    move_vector<NP>(Dp, moving_step, use_div, c, mv);
+    jacobian_vector<NP>(Dp, Dt, moving_step, use_div, c, J);
+}
+
+// ---- ced_field_move_jacobian ---------------------------------------------------------------------------------------------
+// position and time of sample c of each 16-sample column tile; a ragged last tile repeats the last sample (never stored)
+template <int NP>
+__device__ __forceinline__ void jac_load(const JacArgs &A, int64_t tile_base, int c, float (&px)[NP][3], float (&tq)[NP])
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        int64_t s = tile_base + 16 * j + c;
+        s = s < A.n ? s : A.n - 1;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) px[j][a] = A.pos[3 * s + a];
+        tq[j] = A.t[s];
+    }
+}
+
+// lane group a < 3 stores component a of move and row a of the Jacobian
+template <int NP>
+__device__ __forceinline__ void jac_store(const JacArgs &A, const float (&mv)[NP][3], const float (&J)[NP][12], int64_t tile_base,
+                                          int g, int c)
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int64_t s = tile_base + 16 * j + c;
+        const bool stores = s < A.n && g < 3;
+        // named values first: a select between array elements would become a load at a selected address
+        const float m0 = mv[j][0], m1 = mv[j][1], m2 = mv[j][2];
+        const float o_move = (g == 0) ? m0 : (g == 1) ? m1 : m2;
+        if (stores && A.move) A.move[3 * s + g] = o_move;
+#pragma unroll
+        for (int b = 0; b < kDirs; ++b) {
+            const float j0 = J[j][b], j1 = J[j][4 + b], j2 = J[j][8 + b];
+            const float o_jac = (g == 0) ? j0 : (g == 1) ? j1 : j2;
+            if (stores && A.jac) A.jac[12 * s + 4 * g + b] = o_jac;
+        }
+    }
+}
+
+template <int NP, int THREADS>
+__global__ __launch_bounds__(THREADS) void jacobian_kernel(JacArgs A)
+{
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NP;
+    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
+        int lds_off = 0;
+        asm volatile("" : "+v"(lds_off));
+        float px[NP][3], tq[NP], mv[NP][3], J[NP][12];
+        jac_load<NP>(A, tile * TILE, c, px, tq);
+        const auto time = [&](int j, float &f0, float &f1) { time_features(tq[j], g, f0, f1); };
+        motion_move_jacobian<NP>(lds + lds_off, lane, px, time, A.moving_step, A.use_div, mv, J);
+        jac_store<NP>(A, mv, J, tile * TILE, g, c);
+    }
+}
+
+template <bool SPLIT, bool K32, int NP, int THREADS>
+__global__ __launch_bounds__(THREADS) void jacobian_half_kernel(JacArgs A)
+{
+    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NP;
+    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
+    if constexpr (SPLIT)
+        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        int lds_off = 0;
+        asm volatile("" : "+v"(lds_off));
+        const _Float16 *const whi = lds + lds_off;
+        float px[NP][3], tq[NP], mv[NP][3], J[NP][12];
+        jac_load<NP>(A, tile * TILE, c, px, tq);
+        motion_move_jacobian_half<SPLIT, K32, NP>(whi, whi + kMotionHalves, lane, px, tq, A.moving_step, A.use_div, mv, J);
+        jac_store<NP>(A, mv, J, tile * TILE, g, c);
+    }
+}
+
+// ---- the warp's inverse by Newton's method (include/cednerf_hip.h states it) ----------------------------------------------
+// The rows, their load and their store are the fixed-point kernels' (TrackRows: target, time and iterate of a wave tile
+// in registers, every lane group the same copy of column c's rows); `step` holds the residual.  One round on the rows
+// still active: r = (x + m) - c, res = max |r_a|, freeze at res <= tol; a row that goes on takes the Newton step
+// x <- x - (I + J_x)^-1 r by the adjugate, or the fixed-point step x <- x - r where the determinant is too small or the
+// step not finite.  `last`: round max_iters evaluates the residual of the x it was given and moves nothing.  Returns
+// whether any row of this lane is still active.
+template <int NT>
+__device__ __forceinline__ bool newton_update(const float (&mv)[NT][3], const float (&J)[NT][12], float tol, bool last, TrackRows<NT> &R)
+{
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        float r[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) r[a] = __fsub_rn(__fadd_rn(R.px[j][a], mv[j][a]), R.target[j][a]);
+        const float res = fmaxf(fmaxf(__builtin_fabsf(r[0]), __builtin_fabsf(r[1])), __builtin_fabsf(r[2]));
+        const bool on = R.active[j];                                     // a frozen row keeps what it has
+        R.step[j] = on ? res : R.step[j];
+        R.evals[j] += on ? 1 : 0;
+        R.active[j] = on && !(res <= tol);                               // a NaN residual stays active
+        any = any || R.active[j];
+
+        float Am[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int b = 0; b < 3; ++b) Am[a][b] = (a == b) ? __fadd_rn(1.0f, J[j][4 * a + b]) : J[j][4 * a + b];
+        }
+        // cofactors C[a][b] of A; adj = C^T
+        float Cf[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, b1 = (b + 1) % 3, b2 = (b + 2) % 3;
+                Cf[a][b] = __fsub_rn(__fmul_rn(Am[a1][b1], Am[a2][b2]), __fmul_rn(Am[a1][b2], Am[a2][b1]));
+            }
+        }
+        const float det = __fadd_rn(__fadd_rn(__fmul_rn(Am[0][0], Cf[0][0]), __fmul_rn(Am[0][1], Cf[0][1])), __fmul_rn(Am[0][2], Cf[0][2]));
+        float d[3];
+        bool fine = __builtin_fabsf(det) >= 9.5367431640625e-07f;        // 2^-20; false for a NaN
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float num = __fadd_rn(__fadd_rn(__fmul_rn(Cf[0][a], r[0]), __fmul_rn(Cf[1][a], r[1])), __fmul_rn(Cf[2][a], r[2]));
+            d[a] = __fdiv_rn(num, det);
+            fine = fine && __builtin_fabsf(d[a]) < __builtin_inff();     // finite: false for an infinity and for a NaN
+        }
+        const bool go = R.active[j] && !last;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float xn = __fsub_rn(R.px[j][a], fine ? d[a] : r[a]);
+            R.px[j][a] = go ? xn : R.px[j][a];
+        }
+    }
+    return any;
+}
+
+template <int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void newton_kernel(TrackArgs A)
+{
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        TrackRows<NT> R;
+        track_load<NT>(A, tile * TILE, c, R);
+        float tf[NT][2];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) time_features(R.tq[j], g, tf[j][0], tf[j][1]);   // the time does not move: once per tile
+        const auto time = [&](int j, float &f0, float &f1) { f0 = tf[j][0]; f1 = tf[j][1]; };
+        for (int it = 0; it < A.max_iters; ++it) {
+            // opaque LDS base per round: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
+            int lds_off = 0;
+            asm volatile("" : "+v"(lds_off));
+            float mv[NT][3], J[NT][12];
+            motion_move_jacobian<NT>(lds + lds_off, lane, R.px, time, A.moving_step, A.use_div, mv, J);
+            if (__ballot(newton_update<NT>(mv, J, A.tol, it + 1 == A.max_iters, R)) == 0) break;   // wave-uniform
+        }
+        track_store<NT>(A, R, tile * TILE, g, c);
+    }
+}
+
+template <bool SPLIT, bool K32, int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void newton_half_kernel(TrackArgs A)
+{
+    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int g = lane >> 4, c = lane & 15;
+    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
+    if constexpr (SPLIT)
+        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
+    __syncthreads();
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+        TrackRows<NT> R;
+        track_load<NT>(A, tile * TILE, c, R);
+        for (int it = 0; it < A.max_iters; ++it) {
+            int lds_off = 0;
+            asm volatile("" : "+v"(lds_off));
+            const _Float16 *const whi = lds + lds_off;
+            float mv[NT][3], J[NT][12];
+            motion_move_jacobian_half<SPLIT, K32, NT>(whi, whi + kMotionHalves, lane, R.px, R.tq, A.moving_step, A.use_div, mv, J);
+            if (__ballot(newton_update<NT>(mv, J, A.tol, it + 1 == A.max_iters, R)) == 0) break;   // wave-uniform
+        }
+        track_store<NT>(A, R, tile * TILE, g, c);
+    }
+}
+
+// the kernel for the descriptor's arithmetic: launch_move's four variants, one primal tile per wave iteration
+template <typename Args> static void motion_args(const ced_field_desc *d, Args &A)
+{
+    A.moving_step = d->moving_step;
+    A.use_div = d->use_div_offsets ? 1 : 0;
+    A.weights = d->packed_weights;                    // every blob starts with the motion network
+    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
+}
+
+static int launch_jacobian(const ced_field_desc *d, JacArgs &A, const char *who, void *stream)
+{
+    motion_args(d, A);
+    const int mw = d->max_workgroups;
+    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
+        launch_tiles<1, 512>(jacobian_kernel<1, 512>, A, A.n, 2, mw, stream);
+    else if (d->mlp_precision == CED_MLP_F16)
+        launch_tiles<1, 512>(jacobian_half_kernel<false, false, 1, 512>, A, A.n, 2, mw, stream);
+    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
+        launch_tiles<1, 512>(jacobian_half_kernel<true, true, 1, 512>, A, A.n, 2, mw, stream);
+    else
+        launch_tiles<1, 512>(jacobian_half_kernel<true, false, 1, 512>, A, A.n, 2, mw, stream);
+    return check_launch(who);
+}
+
+static int launch_newton(const ced_field_desc *d, TrackArgs &A, const char *who, void *stream)
+{
+    motion_args(d, A);
+    const int mw = d->max_workgroups;
+    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
+        launch_tiles<1, 512>(newton_kernel<1, 512>, A, A.n, 2, mw, stream);
+    else if (d->mlp_precision == CED_MLP_F16)
+        launch_tiles<1, 512>(newton_half_kernel<false, false, 1, 512>, A, A.n, 2, mw, stream);
+    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
+        launch_tiles<1, 512>(newton_half_kernel<true, true, 1, 512>, A, A.n, 2, mw, stream);
+    else
+        launch_tiles<1, 512>(newton_half_kernel<true, false, 1, 512>, A, A.n, 2, mw, stream);
+    return check_launch(who);
+}
+
+}  // namespace ced
+
+extern "C" int ced_field_move_jacobian(const ced_field_desc *desc, int64_t n, const float *positions, const float *t, float *move,
+                                       float *jac, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_move_jacobian");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_move_jacobian: n < 0");
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(positions && t, "field_move_jacobian: null positions/t");
+    CED_REQUIRE(move || jac, "field_move_jacobian: no output requested");
+    ced::JacArgs A{};
+    A.n = n;
+    A.pos = positions; A.t = t;
+    A.move = move; A.jac = jac;
+    return ced::launch_jacobian(desc, A, "field_move_jacobian", stream);
+}
+
+extern "C" int ced_field_move_inverse_newton(const ced_field_desc *desc, int64_t n, const float *target, const float *t,
+                                             const float *init, int32_t max_iters, float tol, float *x, float *step,
+                                             int32_t *evals, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_move_inverse_newton");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_move_inverse_newton: n < 0");
+    rc = ced::validate_solve(max_iters, tol, "field_move_inverse_newton");
+    if (rc) return rc;
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(target && t, "field_move_inverse_newton: null target/t");
+    CED_REQUIRE(x || step || evals, "field_move_inverse_newton: no output requested");
+    ced::TrackArgs A{};
+    A.n = n;
+    A.target = target; A.t = t; A.init = init;
+    A.max_iters = max_iters; A.tol = tol;
+    A.x = x; A.step = step; A.evals = evals;
+    return ced::launch_newton(desc, A, "field_move_inverse_newton", stream);
+}
+
+extern "C" int ced_field_track_newton(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target,
+                                      const float *times, const float *init, int32_t max_iters, float tol, float *x,
+                                      float *step, int32_t *evals, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_track_newton");
+    if (rc) return rc;
+    CED_REQUIRE(n_points >= 0 && n_times >= 0, "field_track_newton: n_points=%lld n_times=%lld", (long long)n_points,
+                (long long)n_times);
+    CED_REQUIRE(n_points <= INT64_MAX / 3 / (n_times > 0 ? n_times : 1), "field_track_newton: n_points * n_times overflows");
+    rc = ced::validate_solve(max_iters, tol, "field_track_newton");
+    if (rc) return rc;
+    if (n_points == 0 || n_times == 0) return CED_OK;
+    CED_REQUIRE(target && times, "field_track_newton: null target/times");
+    CED_REQUIRE(x || step || evals, "field_track_newton: no output requested");
+    ced::TrackArgs A{};
+    A.n = n_points * n_times;
+    A.n_points = n_points;
+    A.bcast = 1;
+    A.target = target; A.t = times; A.init = init;
+    A.max_iters = max_iters; A.tol = tol;
+    A.x = x; A.step = step; A.evals = evals;
+    return ced::launch_newton(desc, A, "field_track_newton", stream);
+}

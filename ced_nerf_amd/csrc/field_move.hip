@@ -23,6 +23,7 @@
 #include "field_device.hpp"
 #include "field_half_device.hpp"
 #include "field_kernel.hpp"
+#include "field_move_device.hpp"
 
 namespace ced {
 
@@ -43,22 +44,6 @@ struct MoveArgs {
     int64_t lo_halves;                                // f16x2: halves from the plane of high parts to the plane of remainders
 };
 
-// the inverse of the warp by fixed-point iteration (ced_field_move_inverse, ced_field_track)
-struct TrackArgs {
-    int64_t n;                                        // rows
-    int64_t n_points;                                 // broadcast: row r reads target / start r % n_points, time r / n_points
-    int bcast;
-    const float *target, *t, *init;                   // [n,3], [n], [n,3] or null; broadcast: [P,3], [T], [P,3] or null
-    int max_iters;
-    float tol;
-    float *x, *step;                                  // [n,3], [n], either may be null
-    int32_t *evals;                                   // [n], may be null
-    float moving_step;
-    int use_div;
-    const void *weights;
-    int64_t lo_halves;
-};
-
 struct RgbArgs {
     int64_t n;
     const float *dir, *geo;                           // [n,3], [n,15]; broadcast: [n_dirs,3], [n / n_dirs,15]
@@ -69,24 +54,12 @@ struct RgbArgs {
     int64_t lo_halves;
 };
 
-static_assert(HalfBlob<true>::B0 == HalfBlob<false>::B0 && Blob<true>::B0 == Blob<false>::B0,
-              "the motion network sits at the start of the blob with or without a time encoding");
-constexpr int kMotionFloats = Blob<false>::B0;                                  // fp32 layers M0..M3
-constexpr int kMotionHalves = HalfBlob<false>::B0 * kFragHalves;                // the same as fp16 fragments, one plane
 constexpr int kHeadFloats = Blob<false>::TOTAL - Blob<false>::H0;               // fp32 layers H0..H2
 constexpr int kHeadHalves = Blob<false>::HEAD_FRAGS * kFragHalves;
 static_assert(HalfBlob<false>::FRAGS - HalfBlob<false>::H0 == Blob<false>::HEAD_FRAGS &&
               HalfBlob<false>::H1 - HalfBlob<false>::H0 == Blob<false>::HF_H1 &&
               HalfBlob<false>::H2 - HalfBlob<false>::H0 == Blob<false>::HF_H2,
               "the head's fragments are laid out alike in the half blobs and in the mixed blob");
-
-// `count` 16-byte words of weights into LDS
-template <int THREADS> __device__ __forceinline__ void stage(void *dst, const void *src, int count, int tid)
-{
-    const f4 *s = reinterpret_cast<const f4 *>(src);
-    f4 *d = reinterpret_cast<f4 *>(dst);
-    for (int i = tid; i < count; i += THREADS) d[i] = s[i];
-}
 
 __device__ __forceinline__ int64_t sample_count(int64_t n, const int64_t *n_dev)
 {
@@ -122,30 +95,6 @@ __device__ __forceinline__ void load_samples(const MoveArgs &A, int64_t tile_bas
     }
 }
 
-// query_move's `move` (model.py:354-365) from the motion network's accumulators (rows natural: row a on lane group 0
-// register a; rows 3,4,5 on (g0,r3), (g1,r0), (g1,r1)), as the fused kernels state it.  Every lane gets all three
-// components of its column's samples.
-template <int NT>
-__device__ __forceinline__ void move_vector(const f4 (&D)[NT][4], float moving_step, int use_div, int c, float (&mv)[NT][3])
-{
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float off = __shfl(D[j][0][a], c, 64);
-            float m = off * moving_step;
-            if (use_div) {
-                constexpr int kFineReg[3] = { 3, 0, 1 };
-                const float fine = __shfl(D[j][0][kFineReg[a]], (a == 0) ? c : 16 + c, 64);
-                const float e = det_expf(2.0f * fine);
-                const float th = 1.0f - 2.0f / (e + 1.0f);
-                m = m + th * moving_step;
-            }
-            mv[j][a] = m;
-        }
-    }
-}
-
 // x_move / normalise / selector (model.py:378-383) from `move` -- except that x_norm leaves unclamped, as the reference
 // returns it.  Lane group a < 3 stores component a, lane group 3 the selector.
 template <int NT>
@@ -177,177 +126,6 @@ __device__ __forceinline__ void move_store(const MoveArgs &A, const float (&mv)[
         if (A.x_move) A.x_move[3 * s + g] = o_xm;
         if (A.x_norm) A.x_norm[3 * s + g] = o_xn;
     }
-}
-
-// ---- a K = 32 layer without the K-doubled instruction --------------------------------------------------------------
-// v_mfma_f32_16x16x32_f16 consumes lane group q's eight operand elements as block q of eight products, q = 0..3, each
-// block rounded once onto the accumulator; v_mfma_f32_16x16x16_f16 consumes lane groups {0,1}, then {2,3}, four elements
-// each, as two such blocks; the order of the products inside a block is irrelevant (oracle/mfma_f16_model.h).  So one
-// K = 32 instruction on operands (a, b) IS two K = 16 instructions on regrouped operands: the first takes from lane group
-// G the elements 4(G&1) .. 4(G&1)+3 of K = 32 lane group G>>1 (its blocks: K = 32 blocks 0, 1), the second the same of lane
-// group 2 + (G>>1) (blocks 2, 3).  The weights are read from LDS at the regrouped address, the activations are regrouped
-// across lanes once per layer.  Same blocks, same order, same bits as mlp_layer_h<..., K32 = true> on the K = 32 blob.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void regroup_k32(const h8 &b, int src_lane, bool upper, h4 &b01, h4 &b23)
-{
-    const u32x4 w = __builtin_bit_cast(u32x4, b);
-    uint32_t x01[4], x23[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        x01[k] = (uint32_t)__shfl((int)w[k], src_lane, 64);
-        x23[k] = (uint32_t)__shfl((int)w[k], src_lane + 32, 64);
-    }
-    b01 = __builtin_bit_cast(h4, u32x2{ upper ? x01[2] : x01[0], upper ? x01[3] : x01[1] });
-    b23 = __builtin_bit_cast(h4, u32x2{ upper ? x23[2] : x23[0], upper ? x23[3] : x23[1] });
-}
-
-template <int KS, int NB, int NT>
-__device__ __forceinline__ void mlp_layer_k32_blocks(const _Float16 *__restrict__ whi, const _Float16 *__restrict__ wlo, int lane,
-                                                     const h8 (&Bh)[NT][2], const h8 (&Bl)[NT][2], f4 (&D)[NT][4])
-{
-    const int g = lane >> 4, c = lane & 15;
-    const int src_lane = 16 * (g >> 1) + c;               // the K = 32 lane whose elements this lane feeds to blocks 0 / 1
-    const bool upper = (g & 1) != 0;
-    const int a01 = src_lane * 8 + (upper ? 4 : 0), a23 = a01 + 32 * 8;
-    h4 bh01[NT][KS], bh23[NT][KS], bl01[NT][KS], bl23[NT][KS];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            regroup_k32(Bh[j][ks], src_lane, upper, bh01[j][ks], bh23[j][ks]);
-            regroup_k32(Bl[j][ks], src_lane, upper, bl01[j][ks], bl23[j][ks]);
-        }
-    }
-    f4 acc[NT];
-#pragma unroll
-    for (int grp = 0; grp < NB * KS; ++grp) {
-        const int nb = grp / KS, ks = grp % KS;
-        if (ks == 0) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[j] = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
-        }
-        const h4 ah01 = *reinterpret_cast<const h4 *>(whi + grp * kFragHalves + a01);
-        const h4 ah23 = *reinterpret_cast<const h4 *>(whi + grp * kFragHalves + a23);
-        const h4 al01 = *reinterpret_cast<const h4 *>(wlo + grp * kFragHalves + a01);
-        const h4 al23 = *reinterpret_cast<const h4 *>(wlo + grp * kFragHalves + a23);
-        // the three products of the split, in mlp_layer_h's order: lo * hi, hi * lo, hi * hi
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(al01, bh01[j][ks], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(al23, bh23[j][ks], acc[j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah01, bl01[j][ks], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah23, bl23[j][ks], acc[j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah01, bh01[j][ks], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah23, bh23[j][ks], acc[j], 0, 0, 0);
-        }
-        if (ks == KS - 1) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) D[j][nb] = acc[j];
-        }
-    }
-}
-
-// a layer fed by a hidden layer: on the pair form, or (K32L: the blob has the K = 32 placements) on that form's blocks
-template <int KS, int NB, int NT, bool SPLIT, bool K32L>
-__device__ __forceinline__ void hidden_fed_layer(const _Float16 *__restrict__ whi, const _Float16 *__restrict__ wlo, int lane,
-                                                 const h8 (&Bh)[NT][2], const h8 (&Bl)[NT][2], f4 (&D)[NT][4])
-{
-    if constexpr (K32L) mlp_layer_k32_blocks<KS, NB, NT>(whi, wlo, lane, Bh, Bl, D);
-    else mlp_layer_h<KS, NB, NT, SPLIT>(whi, wlo, lane, Bh, Bl, D);
-}
-
-// ---- the motion network on one wave tile: encode -> four layers -> move -------------------------------------------------
-// Shared by the kernels that hand `move` out once (move_kernel, move_half_kernel) and by the fixed-point loop that
-// evaluates it up to max_iters times on a position held in registers (track_kernel, track_half_kernel): one statement
-// of the arithmetic, so every evaluation has ced_field_move's bits.
-
-// fp32 chain: the two Frequency features of time tq that lane group g feeds (field_kernel.hpp: k = 4S + g, S = 6, 7)
-__device__ __forceinline__ void time_features(float tq, int g, float &f0, float &f1)
-{
-    const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
-    const float scz = (g & 1) != 0 ? sc1 : sc0;
-    float p0, p1;
-    det_sinpi_both(tq * scz, p0, p1);
-    const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-    f0 = __uint_as_float(sw[0]); f1 = __uint_as_float(sw[1]);
-}
-
-// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): lw = the staged layers M0..M3; time(j, f0, f1) gives the two time
-// features of column tile j where the encoding wants them (time_features, or values the caller holds already)
-template <int NT, typename Time>
-__device__ __forceinline__ void motion_move(const float *lw, int lane, const float (&px)[NT][3], Time time, float moving_step,
-                                            int use_div, float (&mv)[NT][3])
-{
-    using BL = Blob<false>;
-    const int g = lane >> 4, c = lane & 15;
-    float B[NT][16];
-    f4 D[NT][4];
-    // tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const bool odd = (g & 1) != 0;
-        const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
-        const float vxy = odd ? px[j][1] : px[j][0];
-        float p0, p1;
-        det_sinpi_both(vxy * sc0, p0, p1);
-        auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        B[j][0] = __uint_as_float(sw[0]); B[j][2] = __uint_as_float(sw[1]);
-        det_sinpi_both(vxy * sc1, p0, p1);
-        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        B[j][1] = __uint_as_float(sw[0]); B[j][3] = __uint_as_float(sw[1]);
-        const float scz = odd ? sc1 : sc0;
-        det_sinpi_both(px[j][2] * scz, p0, p1);
-        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
-        time(j, B[j][6], B[j][7]);
-    }
-    mlp_layer<8, 4, NT>(lw + BL::M0, lane, B, D);
-    to_operand<4, true, NT>(D, B);
-    mlp_layer<16, 4, NT>(lw + BL::M1, lane, B, D);
-    to_operand<4, true, NT>(D, B);
-    mlp_layer<16, 4, NT>(lw + BL::M2, lane, B, D);
-    to_operand<4, true, NT>(D, B);
-    mlp_layer<16, 1, NT>(lw + BL::M3, lane, B, D);
-    move_vector<NT>(D, moving_step, use_div, c, mv);
-}
-
-// fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2; K32: the blob has half_kernel_k32's placements): whi / wlo = the staged planes
-template <bool SPLIT, bool K32, int NT>
-__device__ __forceinline__ void motion_move_half(const _Float16 *whi, const _Float16 *wlo, int lane, const float (&px)[NT][3],
-                                                 const float (&tq)[NT], float moving_step, int use_div, float (&mv)[NT][3])
-{
-    using BL = HalfBlob<false>;
-    const int g = lane >> 4, c = lane & 15;
-    h8 Bh[NT][2], Bl[NT][2];
-    f4 D[NT][4];
-    // tcnn Frequency(4): lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        float v = tq[j];
-        v = (g == 0) ? px[j][0] : v;
-        v = (g == 1) ? px[j][1] : v;
-        v = (g == 2) ? px[j][2] : v;
-        float f[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
-        to_half8<SPLIT>(f, Bh[j][0], Bl[j][0]);
-    }
-    mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bh, Bl, D);
-    to_operand_h<NT, SPLIT>(D, Bh, Bl);
-    hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M1 * kFragHalves, wlo + BL::M1 * kFragHalves, lane, Bh, Bl, D);
-    to_operand_h<NT, SPLIT>(D, Bh, Bl);
-    hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::M2 * kFragHalves, wlo + BL::M2 * kFragHalves, lane, Bh, Bl, D);
-    to_operand_h<NT, SPLIT>(D, Bh, Bl);
-    hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
-    move_vector<NT>(D, moving_step, use_div, c, mv);
 }
 
 // ---- motion network, fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2) ------------------------------------------
@@ -424,87 +202,6 @@ __global__ __launch_bounds__(THREADS) void move_half_kernel(MoveArgs A)
         load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
         motion_move_half<SPLIT, K32, NT>(whi, wlo, lane, px, tq, A.moving_step, A.use_div, mv);
         move_store<NT>(A, mv, px, tile * TILE, n_eff, g, c);
-    }
-}
-
-// ---- the warp's inverse: x + move(x, t) = target by fixed-point iteration (include/cednerf_hip.h states it) -----------
-// A wave tile keeps target, time and the iterate of its 32 rows in registers (every lane group holds the same copy of
-// column c's rows) and calls the motion network's device function once per round.  A row that has met `step <= tol`
-// is frozen: its registers no longer take the round's result, so its outputs are those of the round it stopped at
-// whatever the other rows of the tile do (and MFMA columns do not mix).  The loop leaves early only when the ballot
-// finds no active row in the wave; rows past n are never active.
-template <int NT> struct TrackRows {
-    float target[NT][3], px[NT][3], tq[NT], step[NT];
-    int evals[NT];
-    bool active[NT];
-};
-
-template <int NT>
-__device__ __forceinline__ void track_load(const TrackArgs &A, int64_t tile_base, int c, TrackRows<NT> &R)
-{
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int64_t row = tile_base + 16 * j + c;
-        const int64_t s = row < A.n ? row : A.n - 1;                     // a ragged last tile repeats the last row
-        int64_t sp = s, st = s;
-        if (A.bcast) {
-            st = s / A.n_points;
-            sp = s - st * A.n_points;
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            R.target[j][a] = A.target[3 * sp + a];
-            R.px[j][a] = A.init ? A.init[3 * sp + a] : R.target[j][a];
-        }
-        R.tq[j] = A.t[st];
-        R.step[j] = __builtin_inff();
-        R.evals[j] = 0;
-        R.active[j] = row < A.n;
-    }
-}
-
-// one round on the rows still active: x_new = target - move, step = max_a |x_new[a] - x[a]|, freeze at step <= tol.
-// Returns whether any row of this lane is still active.
-template <int NT>
-__device__ __forceinline__ bool track_update(const float (&mv)[NT][3], float tol, TrackRows<NT> &R)
-{
-    bool any = false;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        float xn[3], d[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            xn[a] = R.target[j][a] - mv[j][a];
-            d[a] = __builtin_fabsf(xn[a] - R.px[j][a]);
-        }
-        const float step = fmaxf(fmaxf(d[0], d[1]), d[2]);
-        const bool on = R.active[j];                                     // a frozen row keeps what it has
-#pragma unroll
-        for (int a = 0; a < 3; ++a) R.px[j][a] = on ? xn[a] : R.px[j][a];
-        R.step[j] = on ? step : R.step[j];
-        R.evals[j] += on ? 1 : 0;
-        R.active[j] = on && !(step <= tol);                              // a NaN step stays active
-        any = any || R.active[j];
-    }
-    return any;
-}
-
-// lane group a < 3 stores component a of x, lane group 3 step and evals
-template <int NT>
-__device__ __forceinline__ void track_store(const TrackArgs &A, const TrackRows<NT> &R, int64_t tile_base, int g, int c)
-{
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int64_t s = tile_base + 16 * j + c;
-        const float x0 = R.px[j][0], x1 = R.px[j][1], x2 = R.px[j][2];
-        const float o = (g == 0) ? x0 : (g == 1) ? x1 : x2;
-        if (s >= A.n) continue;
-        if (g == 3) {
-            if (A.step) A.step[s] = R.step[j];
-            if (A.evals) A.evals[s] = R.evals[j];
-            continue;
-        }
-        if (A.x) A.x[3 * s + g] = o;
     }
 }
 
@@ -717,33 +414,6 @@ __global__ __launch_bounds__(THREADS) void rgb_half_kernel(RgbArgs A)
     }
 }
 
-// Persistent launch: enough workgroups for the tiles, at most per_cu per CU (the descriptor's max_workgroups caps it).
-template <int NT, int THREADS, typename Kernel, typename Args>
-static void launch_tiles(Kernel kernel, const Args &A, int64_t n, int per_cu, int max_workgroups, void *stream)
-{
-    const int64_t n_tiles = (n + 16 * NT - 1) / (16 * NT);
-    constexpr int waves = THREADS / 64;
-    int64_t blocks = (n_tiles + waves - 1) / waves;
-    const int64_t cap = max_workgroups > 0 ? max_workgroups : (int64_t)kFieldBlocksDefault * per_cu;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
-}
-
-// the descriptor fields these entries read; the hash table is not touched, but its kind selects the blob's layout
-static int validate_desc(const ced_field_desc *d, const char *who)
-{
-    CED_REQUIRE(d != nullptr, "%s: null descriptor", who);
-    CED_REQUIRE(d->time_mode >= 0 && d->time_mode <= 2, "%s: time_mode=%d", who, d->time_mode);
-    CED_REQUIRE(d->packed_weights != nullptr, "%s: null packed_weights", who);
-    CED_REQUIRE(d->mlp_precision >= CED_MLP_F32 && d->mlp_precision <= CED_MLP_F32_HEAD16X2, "%s: mlp_precision=%d", who,
-                d->mlp_precision);
-    CED_REQUIRE((int64_t)d->packed_floats == ced_packed_weight_words(d->use_div_offsets, d->time_mode, d->mlp_precision),
-                "%s: packed_floats=%llu does not match this configuration (mlp_precision %d)", who,
-                (unsigned long long)d->packed_floats, d->mlp_precision);
-    CED_REQUIRE(d->max_workgroups >= 0 && d->max_workgroups <= 65536, "%s: max_workgroups=%d", who, d->max_workgroups);
-    return CED_OK;
-}
-
 static int launch_move(const ced_field_desc *d, MoveArgs &A, const char *who, void *stream)
 {
     for (int i = 0; i < 6; ++i) A.aabb[i] = d->aabb[i];
@@ -780,13 +450,6 @@ static int launch_track(const ced_field_desc *d, TrackArgs &A, const char *who, 
     else
         launch_tiles<2, 512>(track_half_kernel<true, false, 2, 512>, A, A.n, 2, mw, stream);
     return check_launch(who);
-}
-
-static int validate_solve(int32_t max_iters, float tol, const char *who)
-{
-    CED_REQUIRE(max_iters >= 1 && max_iters <= 1024, "%s: max_iters=%d outside 1 .. 1024", who, max_iters);
-    CED_REQUIRE(tol >= 0.0f, "%s: tol=%g must be >= 0 (and not a NaN)", who, (double)tol);
-    return CED_OK;
 }
 
 // the head's kernel for the descriptor's arithmetic, on rows given one by one (ced_field_rgb) or as embedding x direction

@@ -280,47 +280,77 @@ _REF_KEYS = ("faces", "cube", "sigma", "embedding", "rgb", "normals")
 
 
 @torch.no_grad()
-def track_mesh(field, mesh: Dict, t_src, times: Sequence, max_iters: int = 32, tol: float = 1e-6) -> Dict:
+def track_mesh(field, mesh: Dict, t_src, times: Sequence, max_iters: int = 32, tol: float = 1e-6,
+               method: str = "fixed_point", normals: bool = False, velocities: bool = False) -> Dict:
     """Carry the vertices of `mesh` (a dict from `extract_mesh`, extracted at time t_src) to every time of `times`: each
     vertex is a material point, its canonical coordinate is query_move(vertex, t_src)[0], and its position at time t
-    solves x + move(x, t) = canonical (`DNGPradianceField.track_points`, started at the vertex).  Returns
+    solves x + move(x, t) = canonical (`DNGPradianceField.track_points`, started at the vertex; `method` as there).  Returns
         vertices_t [T,V,3], converged [T,V] bool, step [T,V], evals [T,V] int32, canonical [V,3], times [T], t_ref,
         faces, cube, sigma, embedding, normals (and rgb if present): the reference mesh's own, valid at t_ref ONLY --
-        faces are shared by all times; normals and colours are not recomputed per time,
-        reso, center, radius, sigma_thresh, apply_act.
-    The iteration has no damping: where the motion network is no contraction a vertex does not converge and is reported
-    in `converged`, its position the last iterate."""
+        faces are shared by all times; colours are not recomputed per time,
+        reso, center, radius, sigma_thresh, apply_act,
+        normals=True (the mesh must have normals): normals_t [T,V,3], the reference normals carried along.  The surface
+        is a level set of the canonical density pulled back through the warp, whose gradient at (x, t) is
+        (I + J_x(x, t))^T times the canonical gradient, so n_t is (I + J_t(x_t))^T (I + J_ref(x_ref))^-T n_ref, normalised,
+        velocities=True: velocities_t [T,V,3] and det_t [T,V], `DNGPradianceField.query_velocity` at the tracked vertices.
+    Neither solver is damped: a vertex that does not converge is reported in `converged`, its position the last iterate."""
     max_iters, tol = ops.check_solve(max_iters, tol)
+    ops.check_method(method)
     t_ref = _time_value(t_src)
     times = [_time_value(t) for t in times]
     vertices = mesh["vertices"]
+    if normals and "normals" not in mesh:
+        raise ValueError("normals=True needs a mesh with normals")
     if not vertices.is_cuda:
         raise NotImplementedError(_CPU)
     with torch.cuda.device(vertices.device):
-        tr = field.track_points(vertices, t_ref, times, max_iters=max_iters, tol=tol)
+        tr = field.track_points(vertices, t_ref, times, max_iters=max_iters, tol=tol, method=method)
+        moving = {}
+        if normals or velocities:
+            n_v = vertices.shape[0]
+            tt = tr["times"].repeat_interleave(n_v)
+            jac_t = field.query_move_jacobian(tr["positions"].reshape(-1, 3), tt)[1].view(len(times), n_v, 3, 4)
+            grad_t, inv_t, det_t = ops.warp_gradient(jac_t)
+            if normals:
+                jac_ref = field.query_move_jacobian(vertices, torch.full((n_v,), t_ref, device=vertices.device))[1]
+                inv_ref = ops.warp_gradient(jac_ref)[1]
+                canonical_grad = (inv_ref.transpose(-1, -2) @ mesh["normals"][..., None])          # [V,3,1]
+                n_t = (grad_t.transpose(-1, -2) @ canonical_grad).squeeze(-1)
+                # a zero reference normal (vanishing density gradient) stays zero
+                moving["normals_t"] = n_t / n_t.norm(dim=-1, keepdim=True).clamp_min(torch.finfo(n_t.dtype).tiny)
+            if velocities:
+                moving["velocities_t"] = -(inv_t @ jac_t[..., 3:]).squeeze(-1)
+                moving["det_t"] = det_t
     out = {k: mesh[k] for k in _REF_KEYS if k in mesh}
     out.update({k: mesh[k] for k in ("reso", "center", "radius", "sigma_thresh", "apply_act") if k in mesh})
     out.update(vertices_t=tr["positions"], converged=tr["converged"], step=tr["step"], evals=tr["evals"],
                canonical=tr["canonical"], times=times, t_ref=t_ref)
+    out.update(moving)
     return out
 
 
 @torch.no_grad()
 def extract_mesh_tracked(field, t_ref, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None,
                          estimator=None, apply_act: bool = False, center=None, radius=None,
-                         max_cells_per_launch: int = 1 << 22, max_iters: int = 32, tol: float = 1e-6) -> Dict:
+                         max_cells_per_launch: int = 1 << 22, max_iters: int = 32, tol: float = 1e-6,
+                         method: str = "fixed_point", normals: bool = False, velocities: bool = False) -> Dict:
     """`extract_mesh` at t_ref followed by `track_mesh` to `times`: one mesh with shared faces and per-time vertex
-    positions (see `track_mesh` for the result)."""
+    positions (see `track_mesh` for the result, `method`, `normals` and `velocities`)."""
     max_iters, tol = ops.check_solve(max_iters, tol)
+    ops.check_method(method)
     mesh = extract_mesh(field, t_ref, reso, sigma_thresh, dirs, estimator, apply_act, center, radius, max_cells_per_launch)
-    return track_mesh(field, mesh, t_ref, times, max_iters=max_iters, tol=tol)
+    return track_mesh(field, mesh, t_ref, times, max_iters=max_iters, tol=tol, method=method, normals=normals,
+                      velocities=velocities)
 
 
 def tracked_frame(tracked: Dict, k: int) -> Dict:
     """Time step k of a tracked mesh as a dict `save_mesh_ply` writes: the vertices of that time, the shared faces, the
-    reference colours -- and no normals (they belong to t_ref only)."""
+    reference colours -- and that time's normals where the mesh was tracked with normals=True (`normals_t`); the
+    reference normals belong to t_ref only and are never used."""
     out = dict(vertices=tracked["vertices_t"][k], faces=tracked["faces"], t=tracked["times"][k])
     out.update({key: tracked[key] for key in ("rgb", "apply_act") if key in tracked})
+    if "normals_t" in tracked:
+        out["normals"] = tracked["normals_t"][k]
     return out
 
 
@@ -385,11 +415,12 @@ def save_mesh_npz(path: str, mesh: Dict) -> None:
     np.savez(path, **out)
 
 
-_TRACKED_ARRAYS = ("vertices_t", "converged", "step", "evals", "canonical") + _REF_KEYS
+_TRACKED_ARRAYS = ("vertices_t", "converged", "step", "evals", "canonical", "normals_t", "velocities_t", "det_t") + _REF_KEYS
 
 
 def save_tracked_npz(path: str, tracked: Dict) -> None:
-    """A tracked mesh as a numpy .npz: vertices_t, converged, step, evals, canonical, times, t_ref, and the reference
+    """A tracked mesh as a numpy .npz: vertices_t, converged, step, evals, canonical, times, t_ref, the moving normals_t,
+    velocities_t and det_t where the mesh was tracked with them, and the reference
     mesh's faces, cube, sigma, embedding, normals, rgb, reso, center, radius, sigma_thresh -- each if present, so the
     result of track_mesh on a hand-built mesh dict (vertices and faces only) is saved too -- and apply_act (False if absent)."""
     out = {k: tracked[k].detach().cpu().numpy() for k in _TRACKED_ARRAYS if k in tracked}
@@ -484,6 +515,11 @@ def make_parser() -> argparse.ArgumentParser:
                         "time of --times by inverting the warp: tracked_%%04d.ply per time and tracked.npz")
     p.add_argument("--track_iters", type=int, default=32, help="--mesh_track: most evaluations of the motion network per vertex and time")
     p.add_argument("--track_tol", type=float, default=1e-6, help="--mesh_track: a vertex has converged when its last update is <= this")
+    p.add_argument("--mesh_track_method", choices=ops.SOLVE_METHODS, default="fixed_point",
+                   help="--mesh_track: how the warp is inverted -- the fixed-point iteration, or Newton's method on the warp's "
+                        "Jacobian, which converges on most vertices the fixed point loses")
+    p.add_argument("--mesh_track_normals", action="store_true",
+                   help="--mesh_track: carry the normals along (tracked_%%04d.ply get normals, tracked.npz gets normals_t)")
     p.add_argument("--device", default="cuda")
     p.add_argument("--out", required=True, metavar="DIR")
     return p
@@ -553,7 +589,8 @@ def main(argv=None) -> int:
         if a.mesh_track is not None:
             tracked = extract_mesh_tracked(field, a.mesh_track, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh,
                                            dirs=mesh_dirs, estimator=None if a.no_occupancy else estimator,
-                                           max_iters=a.track_iters, tol=a.track_tol)
+                                           max_iters=a.track_iters, tol=a.track_tol, method=a.mesh_track_method,
+                                           normals=a.mesh_track_normals)
             save_tracked_npz(os.path.join(a.out, "tracked.npz"), tracked)
             n_vertices = tracked["vertices_t"].shape[1]
             lost = (~tracked["converged"]).sum(dim=1).tolist()

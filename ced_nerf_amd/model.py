@@ -233,8 +233,30 @@ class DNGPradianceField(torch.nn.Module):
         return x_move, move
 
     @torch.no_grad()
+    def query_move_jacobian(self, x: torch.Tensor, t: torch.Tensor):
+        """The motion network's displacement and its derivative: (move [N,3], jac [N,3,4]) with jac[n, a, b] =
+        d move_a / d (x, y, z, t)_b at (x, t), by forward mode through the network in this field's mlp_precision, from
+        one launch (ced_field_move_jacobian; include/cednerf_hip.h states the operation order).  `move` has
+        `query_move`'s bits.  I + jac[:, :, :3] is the deformation gradient of the warp x -> x + move(x, t), jac[:, :, 3]
+        its time derivative at a fixed x.  In "f16" the derivative is that of the fp16-rounded network, whose ReLU
+        masks differ from the exact network's on a few rows."""
+        if not (x.is_cuda and t.is_cuda):
+            raise NotImplementedError("Only support cuda inputs: query_move_jacobian runs on the HIP kernel (no CPU fallback).")
+        return ops.field_move_jacobian(self._descriptor(), x.reshape(-1, 3).float().contiguous(),
+                                       t.reshape(-1).float().contiguous())
+
+    @torch.no_grad()
+    def query_velocity(self, x: torch.Tensor, t: torch.Tensor):
+        """The velocity of the material point that sits at x at time t (the scene flow): its canonical coordinate
+        c = x + move(x, t) does not change, so (I + J_x) v + d move / dt = 0 and v = -(I + J_x)^-1 d move / dt.
+        Returns (v [N,3], det [N]) with det = det(I + J_x); where det <= 0 the warp folds and v means little."""
+        _, jac = self.query_move_jacobian(x, t)
+        _, inv, det = ops.warp_gradient(jac)
+        return -(inv @ jac[..., 3:]).squeeze(-1), det
+
+    @torch.no_grad()
     def query_move_inverse(self, c: torch.Tensor, t: torch.Tensor, max_iters: int = 32, tol: float = 1e-6,
-                           init: Optional[torch.Tensor] = None):
+                           init: Optional[torch.Tensor] = None, method: str = "fixed_point"):
         """The inverse of the warp: per row the x with x + move(x, t) = c, `move` being `query_move`'s.  The density at
         (x, t) is the canonical density at x + move(x, t), so x is where the material point with canonical coordinate c
         sits at time t.  Solved by fixed-point iteration x <- c - move(x, t) from init (default: c), at most max_iters
@@ -242,24 +264,31 @@ class DNGPradianceField(torch.nn.Module):
         of the update is <= tol (ced_field_move_inverse; include/cednerf_hip.h states it operation by operation).
         c is viewed as [-1, 3], t as [-1]; returns (x [N,3], step [N] the size of the last update, evals [N] int32).  A
         row has converged iff step <= tol; the iteration converges where move(., t) is a contraction and reports the
-        rows where it did not (evals == max_iters, step > tol) instead of hiding them."""
+        rows where it did not (evals == max_iters, step > tol) instead of hiding them.
+        method="newton" solves the same equation by Newton's method on `query_move_jacobian`, fused into one launch
+        (ced_field_move_inverse_newton): `step` is then the max-norm residual |x + move(x, t) - c| of the returned x, a row
+        has converged iff step <= tol, it converges on most rows where the fixed point does not, and where the warp folds
+        (det(I + J_x) <= 0) it may land on another preimage of c.  An unknown method raises ValueError."""
         max_iters, tol = ops.check_solve(max_iters, tol)
+        solve = ops.field_move_inverse_newton if ops.check_method(method) == "newton" else ops.field_move_inverse
         if not (c.is_cuda and t.is_cuda and (init is None or init.is_cuda)):
             raise NotImplementedError("Only support cuda inputs: query_move_inverse runs on the HIP kernel (no CPU fallback).")
-        return ops.field_move_inverse(self._descriptor(), c.reshape(-1, 3).float().contiguous(),
-                                      t.reshape(-1).float().contiguous(),
-                                      None if init is None else init.reshape(-1, 3).float().contiguous(), max_iters, tol)
+        return solve(self._descriptor(), c.reshape(-1, 3).float().contiguous(), t.reshape(-1).float().contiguous(),
+                     None if init is None else init.reshape(-1, 3).float().contiguous(), max_iters, tol)
 
     @torch.no_grad()
-    def track_points(self, x: torch.Tensor, t_src, times, max_iters: int = 32, tol: float = 1e-6) -> Dict:
+    def track_points(self, x: torch.Tensor, t_src, times, max_iters: int = 32, tol: float = 1e-6,
+                     method: str = "fixed_point") -> Dict:
         """Where the material points seen at x [P,3] at time t_src (a number, a one-element tensor or [P]) sit at every
         time of `times` ([T]: a sequence or a tensor).  Returns a dict:
             canonical [P,3]  query_move(x, t_src)[0], the points' canonical coordinates,
             positions [T,P,3], step [T,P], evals [T,P] int32  `query_move_inverse`(canonical, times[k]) started at x,
             converged [T,P] bool  step <= tol,
             times [T].
-        One launch for all P x T rows (ced_field_track), neither input expanded in memory."""
+        One launch for all P x T rows (ced_field_track; method="newton": ced_field_track_newton, see
+        `query_move_inverse`), neither input expanded in memory."""
         max_iters, tol = ops.check_solve(max_iters, tol)
+        track = ops.field_track_newton if ops.check_method(method) == "newton" else ops.field_track
         if not x.is_cuda:
             raise NotImplementedError("Only support cuda inputs: track_points runs on the HIP kernels (no CPU fallback).")
         pts = x.reshape(-1, 3).float().contiguous()
@@ -272,7 +301,7 @@ class DNGPradianceField(torch.nn.Module):
         tt = torch.as_tensor(times, dtype=torch.float32, device=pts.device).reshape(-1).contiguous()
         desc = self._descriptor()
         canonical = ops.field_move(desc, pts, ts.contiguous(), want=(True, False, False, False))[0]
-        positions, step, evals = ops.field_track(desc, canonical, tt, pts, max_iters, tol)
+        positions, step, evals = track(desc, canonical, tt, pts, max_iters, tol)
         return dict(canonical=canonical, positions=positions, step=step, evals=evals, converged=step <= tol, times=tt)
 
     @torch.no_grad()

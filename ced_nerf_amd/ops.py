@@ -321,10 +321,17 @@ def check_solve(max_iters, tol):
     return int(max_iters), tol_f
 
 
-def field_move_inverse(desc: _lib.FieldDesc, target, t, init=None, max_iters: int = 32, tol: float = 1e-6):
-    """ced_field_move_inverse: per row the solution x of x + move(x, t) = target by fixed-point iteration from init (or
-    from target), at most max_iters evaluations, stopped at step <= tol.  target [n,3], t [n], init [n,3] or None ->
-    (x [n,3], step [n], evals [n] int32); include/cednerf_hip.h states the iteration."""
+SOLVE_METHODS = ("fixed_point", "newton")        # how the warp's inverse is solved
+
+
+def check_method(method) -> str:
+    """`method` of the inverse solvers, or ValueError."""
+    if method not in SOLVE_METHODS:
+        raise ValueError(f"method must be one of {SOLVE_METHODS}, got {method!r}")
+    return method
+
+
+def _move_inverse(entry: str, desc, target, t, init, max_iters, tol):
     max_iters, tol = check_solve(max_iters, tol)
     _chk(target, torch.float32, "target"); _chk(t, torch.float32, "t"); _chk(init, torch.float32, "init", allow_none=True)
     n = target.shape[0]
@@ -335,16 +342,13 @@ def field_move_inverse(desc: _lib.FieldDesc, target, t, init=None, max_iters: in
     x = torch.empty((n, 3), device=dev, dtype=torch.float32)
     step = torch.empty((n,), device=dev, dtype=torch.float32)
     evals = torch.empty((n,), device=dev, dtype=torch.int32)
-    rc = _lib.lib().ced_field_move_inverse(C.byref(desc), n, _p(target), _p(t), _p(init), max_iters, tol, _p(x), _p(step),
-                                           _p(evals), _stream())
-    _lib.check(rc, "field_move_inverse")
+    rc = getattr(_lib.lib(), "ced_" + entry)(C.byref(desc), n, _p(target), _p(t), _p(init), max_iters, tol, _p(x), _p(step),
+                                             _p(evals), _stream())
+    _lib.check(rc, entry)
     return x, step, evals
 
 
-def field_track(desc: _lib.FieldDesc, target, times, init=None, max_iters: int = 32, tol: float = 1e-6):
-    """ced_field_track: `field_move_inverse` for every (time, point) pair without expanding either input.  target [P,3],
-    times [T], init [P,3] or None (shared by all times) -> (x [T,P,3], step [T,P], evals [T,P] int32), each row with
-    the bits of `field_move_inverse` on the expanded rows."""
+def _track(entry: str, desc, target, times, init, max_iters, tol):
     max_iters, tol = check_solve(max_iters, tol)
     _chk(target, torch.float32, "target"); _chk(times, torch.float32, "times")
     _chk(init, torch.float32, "init", allow_none=True)
@@ -356,10 +360,66 @@ def field_track(desc: _lib.FieldDesc, target, times, init=None, max_iters: int =
     x = torch.empty((nt, p, 3), device=dev, dtype=torch.float32)
     step = torch.empty((nt, p), device=dev, dtype=torch.float32)
     evals = torch.empty((nt, p), device=dev, dtype=torch.int32)
-    rc = _lib.lib().ced_field_track(C.byref(desc), p, nt, _p(target), _p(times), _p(init), max_iters, tol, _p(x), _p(step),
-                                    _p(evals), _stream())
-    _lib.check(rc, "field_track")
+    rc = getattr(_lib.lib(), "ced_" + entry)(C.byref(desc), p, nt, _p(target), _p(times), _p(init), max_iters, tol, _p(x),
+                                             _p(step), _p(evals), _stream())
+    _lib.check(rc, entry)
     return x, step, evals
+
+
+def field_move_inverse(desc: _lib.FieldDesc, target, t, init=None, max_iters: int = 32, tol: float = 1e-6):
+    """ced_field_move_inverse: per row the solution x of x + move(x, t) = target by fixed-point iteration from init (or
+    from target), at most max_iters evaluations, stopped at step <= tol.  target [n,3], t [n], init [n,3] or None ->
+    (x [n,3], step [n], evals [n] int32); include/cednerf_hip.h states the iteration."""
+    return _move_inverse("field_move_inverse", desc, target, t, init, max_iters, tol)
+
+
+def field_track(desc: _lib.FieldDesc, target, times, init=None, max_iters: int = 32, tol: float = 1e-6):
+    """ced_field_track: `field_move_inverse` for every (time, point) pair without expanding either input.  target [P,3],
+    times [T], init [P,3] or None (shared by all times) -> (x [T,P,3], step [T,P], evals [T,P] int32), each row with
+    the bits of `field_move_inverse` on the expanded rows."""
+    return _track("field_track", desc, target, times, init, max_iters, tol)
+
+
+def field_move_jacobian(desc: _lib.FieldDesc, positions, t, want=(True, True)):
+    """ced_field_move_jacobian: (move [n,3], jac [n,3,4]) at positions [n,3], t [n], from one launch.  jac[r, a, b] =
+    d move_a / d (x, y, z, t)_b by forward mode through the motion network in desc's mlp_precision; `move` has
+    `field_move`'s bits.  want = which of the two to compute; the other comes back as None."""
+    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
+    n = positions.shape[0]
+    if positions.shape != (n, 3) or t.numel() != n:
+        raise ValueError(f"positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
+    if not any(want):
+        raise ValueError("field_move_jacobian: no output requested")
+    dev = positions.device
+    move = torch.empty((n, 3), device=dev, dtype=torch.float32) if want[0] else None
+    jac = torch.empty((n, 3, 4), device=dev, dtype=torch.float32) if want[1] else None
+    rc = _lib.lib().ced_field_move_jacobian(C.byref(desc), n, _p(positions), _p(t), _p(move), _p(jac), _stream())
+    _lib.check(rc, "field_move_jacobian")
+    return move, jac
+
+
+def field_move_inverse_newton(desc: _lib.FieldDesc, target, t, init=None, max_iters: int = 32, tol: float = 1e-6):
+    """ced_field_move_inverse_newton: `field_move_inverse`'s arguments and outputs, solved by Newton's method on
+    `field_move_jacobian` (include/cednerf_hip.h states the iteration).  `step` is the max-norm residual
+    |x + move(x, t) - target| of the returned x; a row has converged iff step <= tol."""
+    return _move_inverse("field_move_inverse_newton", desc, target, t, init, max_iters, tol)
+
+
+def field_track_newton(desc: _lib.FieldDesc, target, times, init=None, max_iters: int = 32, tol: float = 1e-6):
+    """ced_field_track_newton: `field_track`'s broadcast on the Newton iteration, each row with the bits of
+    `field_move_inverse_newton` on the expanded rows."""
+    return _track("field_track_newton", desc, target, times, init, max_iters, tol)
+
+
+def warp_gradient(jac: torch.Tensor):
+    """The 3 x 3 algebra of the warp's derivative, shared by the velocity and the moving normals: from jac [..., 3, 4]
+    (`field_move_jacobian`) the deformation gradient A = I + jac[..., :3] [..., 3, 3], its inverse by the adjugate and
+    its determinant [...], in jac's dtype.  Where det is 0 the inverse is not finite."""
+    A = jac[..., :3] + torch.eye(3, device=jac.device, dtype=jac.dtype)
+    rows = [torch.linalg.cross(A[..., (a + 1) % 3, :], A[..., (a + 2) % 3, :], dim=-1) for a in range(3)]
+    cof = torch.stack(rows, -2)                                          # cofactors: cof[a] = A[a+1] x A[a+2]
+    det = (A[..., 0, :] * cof[..., 0, :]).sum(-1)
+    return A, cof.transpose(-1, -2) / det[..., None, None], det
 
 
 def field_rgb(desc: _lib.FieldDesc, directions, embedding, apply_act: bool = True):

@@ -306,6 +306,59 @@ int ced_field_track(const ced_field_desc *desc, int64_t n_points, int64_t n_time
                     const float *times, const float *init, int32_t max_iters, float tol, float *x,
                     float *step, int32_t *evals, void *stream);
 
+/* ---- the derivative of the warp ----
+ * move [n,3] and jac [n,12], jac[r, 4a + b] = d move_a / d (x, y, z, t)_b, from one launch; either may be NULL, not
+ * both.  `move` is ced_field_move's `move`, bit for bit, in desc->mlp_precision.  The Jacobian is computed in forward
+ * mode: four tangent vectors per sample (directions b = x, y, z, t) pushed through the four layers beside the primal,
+ * as four more matrix-instruction columns on the same weights, in this order:
+ *   encoding   the feature sin(2^k pi v_d + phase) of dimension d has the tangent, for direction b == d,
+ *                  w * q   with w = fp32(pi) * 2^k (exact) and q the primal feature of the OTHER phase of that frequency,
+ *              negated when the feature itself is the cosine; for b != d it is 0.  fp32 chain: q is the fp32 feature.
+ *              f16 / f16x2: the product is formed in fp32 from the fp32 features, then rounded to fp16 / split into
+ *              hi + lo like the primal features.
+ *   layers     every layer multiplies the tangents by the layer's weights in the mode's own layer arithmetic (fp32
+ *              MFMA chain in ascending k; fp16 or split-fp16 blocks with fp32 accumulation, the f16x2 blob's two
+ *              layouts included), exactly as it multiplies the primal.
+ *   ReLU       a hidden layer's tangent is set to 0 wherever the PRIMAL pre-activation is not > 0; f16 / f16x2: it is
+ *              then clamped to +-65504 and rounded / split like the primal activation.
+ *   output     with (off, fine) the last layer's rows and (d off, d fine) their tangents, step = moving_step:
+ *                  use_div_offsets == 0:   jac = (d off_a) * step
+ *                  otherwise:              s = 1 - th_a * th_a;   jac = (d off_a + s * d fine_a) * step
+ *              th_a being the tanh value ced_field_move computes for `move`; every operation one fp32 rounding. */
+int ced_field_move_jacobian(const ced_field_desc *desc, int64_t n, const float *positions, const float *t,
+                            float *move, float *jac, void *stream);
+
+/* The warp's inverse by Newton's method on that Jacobian: arguments, outputs and refusals of ced_field_move_inverse.
+ * Per row, with target c, time t, a start (init's row, or c when init is NULL), max_iters = K and tol, every line in
+ * fp32, every product, sum, difference and quotient rounded on its own (no fused multiply-add):
+ *     x = start
+ *     for k = 1 .. K:
+ *         (m, J) = ced_field_move_jacobian at (x, t)           -- its bits, in desc->mlp_precision
+ *         r[a] = (x[a] + m[a]) - c[a]
+ *         step = fmaxf(fmaxf(|r[0]|, |r[1]|), |r[2]|);  evals = k
+ *         if step <= tol or k == K: stop                      -- `step <= tol` is false for a NaN
+ *         A = I + J[:, :3]                                      -- A[a][a] = 1.0f + J[a][a], A[a][b] = J[a][b]
+ *         C[a][b] = A[a+1][b+1] * A[a+2][b+2] - A[a+1][b+2] * A[a+2][b+1]      -- cofactors, indices mod 3
+ *         det = (A[0][0] * C[0][0] + A[0][1] * C[0][1]) + A[0][2] * C[0][2]
+ *         d[a] = ((C[0][a] * r[0] + C[1][a] * r[1]) + C[2][a] * r[2]) / det    -- the adjugate is C transposed
+ *         if !(|det| >= 2^-20) or some d[a] is not finite: d = r               -- the fixed-point step
+ *         x[a] = x[a] - d[a]
+ * Outputs: x [n,3], step [n], evals [n] int32.  `step` is the max-norm residual |x + move(x, t) - c| of the RETURNED x,
+ * and a row has converged iff step <= tol.  There is no line search and no damping: rows that do not converge are
+ * reported through step and evals == K, as by the fixed-point entries.  Where the warp folds (det(I + J_x) <= 0
+ * somewhere between the start and a solution) the equation has several solutions and Newton may land on another
+ * preimage of c than the fixed-point iteration, or on none.  A row's result does not depend on n or on the other rows
+ * (finished rows are frozen, a wave leaves the loop when all of its rows are). */
+int ced_field_move_inverse_newton(const ced_field_desc *desc, int64_t n, const float *target, const float *t,
+                                  const float *init, int32_t max_iters, float tol, float *x, float *step,
+                                  int32_t *evals, void *stream);
+
+/* ced_field_track's broadcast (row r = k * n_points + p) on the Newton iteration: each row has the bits of
+ * ced_field_move_inverse_newton on the expanded rows. */
+int ced_field_track_newton(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target,
+                           const float *times, const float *init, int32_t max_iters, float tol, float *x,
+                           float *step, int32_t *evals, void *stream);
+
 /* DNGPradianceField._query_rgb(dir, embedding, apply_act) -- cednerf/model.py:447-466: dirs [n,3] are normalised,
  * mapped to [0,1], SH degree 2; mlp_head on [SH(4), embedding(15)]; the sigmoid iff apply_act.  embedding [n,15] is what
  * ced_field_forward writes to `geo`; rgb [n,3].  The head runs in the arithmetic of desc->mlp_precision. */
