@@ -11,8 +11,9 @@
 // tangent is zeroed wherever the PRIMAL pre-activation is not > 0, and the output applies the tanh's derivative
 // 1 - th^2 to the fine offsets.
 //
-// Shape: field_move.hip's (persistent workgroups of 512 threads, the motion network's layers staged into LDS once), with
-// ONE 16-sample primal tile per wave iteration instead of two: primal + four tangents are five operand tiles and five
+// Shape: field_move.hip's (tile_kernel of field_move_device.hpp with the ops JacobianOp and NewtonOp: persistent workgroups
+// of 512 threads, the motion network's layers staged into LDS once), with ONE 16-sample primal tile per wave iteration
+// instead of two: primal + four tangents are five operand tiles and five
 // accumulator tiles (80 + 80 registers on the fp32 chain), which fit the 256 registers of a wave at two waves per SIMD
 // without scratch; two primal tiles would not.
 #include "field_move_device.hpp"
@@ -31,43 +32,6 @@ struct JacArgs {
 
 constexpr int kDirs = 4;                              // tangent directions: x, y, z, t
 constexpr float kPiF = 3.14159274101257324f;          // the pi of det_sinpi_phase
-
-// The two encodings, line for line as motion_move / motion_move_half state them (field_move_device.hpp), on their own
-// here because the tangents are built from the features before the first layer consumes them.
-// fp32 chain: tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g): B[j][0 .. 7]
-template <int NT, typename Time>
-__device__ __forceinline__ void motion_encode(const float (&px)[NT][3], Time time, int g, float (&B)[NT][16])
-{
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const bool odd = (g & 1) != 0;
-        const float sc0 = (float)(1 << (g >> 1)), sc1 = 4.0f * sc0;
-        const float vxy = odd ? px[j][1] : px[j][0];
-        float p0, p1;
-        det_sinpi_both(vxy * sc0, p0, p1);
-        auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        B[j][0] = __uint_as_float(sw[0]); B[j][2] = __uint_as_float(sw[1]);
-        det_sinpi_both(vxy * sc1, p0, p1);
-        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        B[j][1] = __uint_as_float(sw[0]); B[j][3] = __uint_as_float(sw[1]);
-        const float scz = odd ? sc1 : sc0;
-        det_sinpi_both(px[j][2] * scz, p0, p1);
-        sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
-        B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
-        time(j, B[j][6], B[j][7]);
-    }
-}
-
-// fp16 operands: lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
-__device__ __forceinline__ void motion_features_half(const float (&px)[3], float tq, int g, float (&f)[8])
-{
-    float v = tq;
-    v = (g == 0) ? px[0] : v;
-    v = (g == 1) ? px[1] : v;
-    v = (g == 2) ? px[2] : v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
-}
 
 // ---- tangents on the fp32 MFMA chain ---------------------------------------------------------------------------------
 // Tangent tile 4j + b of primal tile j is d/d(x,y,z,t)_b.  Feature k = 4S + g of the operand (lane group g, k-step S)
@@ -126,32 +90,25 @@ __device__ __forceinline__ void jacobian_vector(const f4 (&Dp)[NP][4], const f4 
     for (int j = 0; j < NP; ++j) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            constexpr int kFineReg[3] = { 3, 0, 1 };
-            const int fine_lane = (a == 0) ? c : 16 + c;
             float slope = 0.0f;
             if (use_div) {
-                const float fine = __shfl(Dp[j][0][kFineReg[a]], fine_lane, 64);
-                const float e = det_expf(2.0f * fine);
-                const float th = 1.0f - 2.0f / (e + 1.0f);
+                const float th = fine_tanh(fine_row(Dp[j][0], a, c));
                 slope = 1.0f - th * th;
             }
 #pragma unroll
             for (int b = 0; b < kDirs; ++b) {
                 float v = __shfl(Dt[kDirs * j + b][0][a], c, 64);
-                if (use_div) {
-                    const float dfine = __shfl(Dt[kDirs * j + b][0][kFineReg[a]], fine_lane, 64);
-                    v = v + slope * dfine;
-                }
+                if (use_div) v = v + slope * fine_row(Dt[kDirs * j + b][0], a, c);
                 J[j][4 * a + b] = v * moving_step;
             }
         }
     }
 }
 
-// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): motion_move with the four tangent tiles beside each primal tile
+// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): motion_move_f32 with the four tangent tiles beside each primal tile
 template <int NP, typename Time>
-__device__ __forceinline__ void motion_move_jacobian(const float *lw, int lane, const float (&px)[NP][3], Time time,
-                                                     float moving_step, int use_div, float (&mv)[NP][3], float (&J)[NP][12])
+__device__ __forceinline__ void motion_move_jacobian_f32(const float *lw, int lane, const float (&px)[NP][3], const Time &time,
+                                                         float moving_step, int use_div, float (&mv)[NP][3], float (&J)[NP][12])
 {
     using BL = Blob<false>;
     constexpr int NTT = kDirs * NP;
@@ -207,9 +164,9 @@ __device__ __forceinline__ void tangent_operand_h(const f4 (&Dp)[NP][4], const f
 // tangent tiles beside each primal tile.  Lane group g owns dimension g, so the tangent of direction b is nonzero on
 // lane group b alone: element e = 2 * freq + phase is 2^freq pi times element e ^ 1, negated for a cosine, formed in
 // fp32 from the fp32 features and then rounded / split like them.
-template <bool SPLIT, bool K32, int NP>
+template <bool SPLIT, bool K32, int NP, typename Time>
 __device__ __forceinline__ void motion_move_jacobian_half(const _Float16 *whi, const _Float16 *wlo, int lane, const float (&px)[NP][3],
-                                                          const float (&tq)[NP], float moving_step, int use_div, float (&mv)[NP][3],
+                                                          const Time &time, float moving_step, int use_div, float (&mv)[NP][3],
                                                           float (&J)[NP][12])
 {
     using BL = HalfBlob<false>;
@@ -220,7 +177,7 @@ __device__ __forceinline__ void motion_move_jacobian_half(const _Float16 *whi, c
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
         float f[8], d[8];
-        motion_features_half(px[j], tq[j], g, f);
+        motion_features_half(px[j], time.value(j), g, f);
         to_half8<SPLIT>(f, Bph[j][0], Bpl[j][0]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -253,21 +210,18 @@ __device__ __forceinline__ void motion_move_jacobian_half(const _Float16 *whi, c
     jacobian_vector<NP>(Dp, Dt, moving_step, use_div, c, J);
 }
 
-// ---- ced_field_move_jacobian ---------------------------------------------------------------------------------------------
-// position and time of sample c of each 16-sample column tile; a ragged last tile repeats the last sample (never stored)
-template <int NP>
-__device__ __forceinline__ void jac_load(const JacArgs &A, int64_t tile_base, int c, float (&px)[NP][3], float (&tq)[NP])
+// the chain with its tangents in the arithmetic of the staged weights W; w = the tile's LDS base
+template <typename W, int NP, typename Time>
+__device__ __forceinline__ void motion_move_jacobian(const typename W::Elem *w, int lane, const float (&px)[NP][3], const Time &time,
+                                                     float moving_step, int use_div, float (&mv)[NP][3], float (&J)[NP][12])
 {
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        int64_t s = tile_base + 16 * j + c;
-        s = s < A.n ? s : A.n - 1;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) px[j][a] = A.pos[3 * s + a];
-        tq[j] = A.t[s];
-    }
+    if constexpr (W::kHalf)
+        motion_move_jacobian_half<W::kSplit, W::kK32, NP>(w, w + W::kPlane, lane, px, time, moving_step, use_div, mv, J);
+    else
+        motion_move_jacobian_f32<NP>(w, lane, px, time, moving_step, use_div, mv, J);
 }
 
+// ---- ced_field_move_jacobian ---------------------------------------------------------------------------------------------
 // lane group a < 3 stores component a of move and row a of the Jacobian
 template <int NP>
 __device__ __forceinline__ void jac_store(const JacArgs &A, const float (&mv)[NP][3], const float (&J)[NP][12], int64_t tile_base,
@@ -290,61 +244,19 @@ __device__ __forceinline__ void jac_store(const JacArgs &A, const float (&mv)[NP
     }
 }
 
-template <int NP, int THREADS>
-__global__ __launch_bounds__(THREADS) void jacobian_kernel(JacArgs A)
-{
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NP;
-    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
-        int lds_off = 0;
-        asm volatile("" : "+v"(lds_off));
+struct JacobianOp : TileOp {
+    using Args = JacArgs;
+    template <typename W, int NP>
+    __device__ __forceinline__ static void tile(const JacArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base, int64_t,
+                                                int lane)
+    {
+        const int g = lane >> 4, c = lane & 15;
         float px[NP][3], tq[NP], mv[NP][3], J[NP][12];
-        jac_load<NP>(A, tile * TILE, c, px, tq);
-        const auto time = [&](int j, float &f0, float &f1) { time_features(tq[j], g, f0, f1); };
-        motion_move_jacobian<NP>(lds + lds_off, lane, px, time, A.moving_step, A.use_div, mv, J);
-        jac_store<NP>(A, mv, J, tile * TILE, g, c);
+        load_points<NP>(A.pos, A.t, A.n, tile_base, c, px, tq);
+        motion_move_jacobian<W, NP>(w, lane, px, RowTime<NP>{ tq }, A.moving_step, A.use_div, mv, J);
+        jac_store<NP>(A, mv, J, tile_base, g, c);
     }
-}
-
-template <bool SPLIT, bool K32, int NP, int THREADS>
-__global__ __launch_bounds__(THREADS) void jacobian_half_kernel(JacArgs A)
-{
-    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NP;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
-    if constexpr (SPLIT)
-        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        int lds_off = 0;
-        asm volatile("" : "+v"(lds_off));
-        const _Float16 *const whi = lds + lds_off;
-        float px[NP][3], tq[NP], mv[NP][3], J[NP][12];
-        jac_load<NP>(A, tile * TILE, c, px, tq);
-        motion_move_jacobian_half<SPLIT, K32, NP>(whi, whi + kMotionHalves, lane, px, tq, A.moving_step, A.use_div, mv, J);
-        jac_store<NP>(A, mv, J, tile * TILE, g, c);
-    }
-}
+};
 
 // ---- the warp's inverse by Newton's method (include/cednerf_hip.h states it) ----------------------------------------------
 // The rows, their load and their store are the fixed-point kernels' (TrackRows: target, time and iterate of a wave tile
@@ -404,111 +316,24 @@ __device__ __forceinline__ bool newton_update(const float (&mv)[NT][3], const fl
     return any;
 }
 
-template <int NT, int THREADS>
-__global__ __launch_bounds__(THREADS) void newton_kernel(TrackArgs A)
-{
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+struct NewtonOp : TileOp {
+    using Args = TrackArgs;
+    template <typename W, int NT>
+    __device__ __forceinline__ static void tile(const TrackArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base,
+                                                int64_t, int lane)
+    {
+        const int g = lane >> 4, c = lane & 15;
         TrackRows<NT> R;
-        track_load<NT>(A, tile * TILE, c, R);
-        float tf[NT][2];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) time_features(R.tq[j], g, tf[j][0], tf[j][1]);   // the time does not move: once per tile
-        const auto time = [&](int j, float &f0, float &f1) { f0 = tf[j][0]; f1 = tf[j][1]; };
+        track_load<NT>(A, tile_base, c, R);
+        const HeldTime<NT> time = hold_time<W, NT>(R.tq, g);
         for (int it = 0; it < A.max_iters; ++it) {
-            // opaque LDS base per round: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
-            int lds_off = 0;
-            asm volatile("" : "+v"(lds_off));
             float mv[NT][3], J[NT][12];
-            motion_move_jacobian<NT>(lds + lds_off, lane, R.px, time, A.moving_step, A.use_div, mv, J);
+            motion_move_jacobian<W, NT>(opaque(w), lane, R.px, time, A.moving_step, A.use_div, mv, J);
             if (__ballot(newton_update<NT>(mv, J, A.tol, it + 1 == A.max_iters, R)) == 0) break;   // wave-uniform
         }
-        track_store<NT>(A, R, tile * TILE, g, c);
+        track_store<NT>(A, R, tile_base, g, c);
     }
-}
-
-template <bool SPLIT, bool K32, int NT, int THREADS>
-__global__ __launch_bounds__(THREADS) void newton_half_kernel(TrackArgs A)
-{
-    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
-    if constexpr (SPLIT)
-        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        TrackRows<NT> R;
-        track_load<NT>(A, tile * TILE, c, R);
-        for (int it = 0; it < A.max_iters; ++it) {
-            int lds_off = 0;
-            asm volatile("" : "+v"(lds_off));
-            const _Float16 *const whi = lds + lds_off;
-            float mv[NT][3], J[NT][12];
-            motion_move_jacobian_half<SPLIT, K32, NT>(whi, whi + kMotionHalves, lane, R.px, R.tq, A.moving_step, A.use_div, mv, J);
-            if (__ballot(newton_update<NT>(mv, J, A.tol, it + 1 == A.max_iters, R)) == 0) break;   // wave-uniform
-        }
-        track_store<NT>(A, R, tile * TILE, g, c);
-    }
-}
-
-// the kernel for the descriptor's arithmetic: launch_move's four variants, one primal tile per wave iteration
-template <typename Args> static void motion_args(const ced_field_desc *d, Args &A)
-{
-    A.moving_step = d->moving_step;
-    A.use_div = d->use_div_offsets ? 1 : 0;
-    A.weights = d->packed_weights;                    // every blob starts with the motion network
-    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
-}
-
-static int launch_jacobian(const ced_field_desc *d, JacArgs &A, const char *who, void *stream)
-{
-    motion_args(d, A);
-    const int mw = d->max_workgroups;
-    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
-        launch_tiles<1, 512>(jacobian_kernel<1, 512>, A, A.n, 2, mw, stream);
-    else if (d->mlp_precision == CED_MLP_F16)
-        launch_tiles<1, 512>(jacobian_half_kernel<false, false, 1, 512>, A, A.n, 2, mw, stream);
-    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
-        launch_tiles<1, 512>(jacobian_half_kernel<true, true, 1, 512>, A, A.n, 2, mw, stream);
-    else
-        launch_tiles<1, 512>(jacobian_half_kernel<true, false, 1, 512>, A, A.n, 2, mw, stream);
-    return check_launch(who);
-}
-
-static int launch_newton(const ced_field_desc *d, TrackArgs &A, const char *who, void *stream)
-{
-    motion_args(d, A);
-    const int mw = d->max_workgroups;
-    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
-        launch_tiles<1, 512>(newton_kernel<1, 512>, A, A.n, 2, mw, stream);
-    else if (d->mlp_precision == CED_MLP_F16)
-        launch_tiles<1, 512>(newton_half_kernel<false, false, 1, 512>, A, A.n, 2, mw, stream);
-    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
-        launch_tiles<1, 512>(newton_half_kernel<true, true, 1, 512>, A, A.n, 2, mw, stream);
-    else
-        launch_tiles<1, 512>(newton_half_kernel<true, false, 1, 512>, A, A.n, 2, mw, stream);
-    return check_launch(who);
-}
+};
 
 }  // namespace ced
 
@@ -525,49 +350,21 @@ extern "C" int ced_field_move_jacobian(const ced_field_desc *desc, int64_t n, co
     A.n = n;
     A.pos = positions; A.t = t;
     A.move = move; A.jac = jac;
-    return ced::launch_jacobian(desc, A, "field_move_jacobian", stream);
+    return ced::launch_motion<ced::JacobianOp, 1>(desc, A, "field_move_jacobian", stream);
 }
 
 extern "C" int ced_field_move_inverse_newton(const ced_field_desc *desc, int64_t n, const float *target, const float *t,
                                              const float *init, int32_t max_iters, float tol, float *x, float *step,
                                              int32_t *evals, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_move_inverse_newton");
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "field_move_inverse_newton: n < 0");
-    rc = ced::validate_solve(max_iters, tol, "field_move_inverse_newton");
-    if (rc) return rc;
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(target && t, "field_move_inverse_newton: null target/t");
-    CED_REQUIRE(x || step || evals, "field_move_inverse_newton: no output requested");
-    ced::TrackArgs A{};
-    A.n = n;
-    A.target = target; A.t = t; A.init = init;
-    A.max_iters = max_iters; A.tol = tol;
-    A.x = x; A.step = step; A.evals = evals;
-    return ced::launch_newton(desc, A, "field_move_inverse_newton", stream);
+    return ced::solve_rows(desc, n, target, t, init, max_iters, tol, x, step, evals, "field_move_inverse_newton",
+                           ced::launch_motion<ced::NewtonOp, 1>, stream);
 }
 
 extern "C" int ced_field_track_newton(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target,
                                       const float *times, const float *init, int32_t max_iters, float tol, float *x,
                                       float *step, int32_t *evals, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_track_newton");
-    if (rc) return rc;
-    CED_REQUIRE(n_points >= 0 && n_times >= 0, "field_track_newton: n_points=%lld n_times=%lld", (long long)n_points,
-                (long long)n_times);
-    CED_REQUIRE(n_points <= INT64_MAX / 3 / (n_times > 0 ? n_times : 1), "field_track_newton: n_points * n_times overflows");
-    rc = ced::validate_solve(max_iters, tol, "field_track_newton");
-    if (rc) return rc;
-    if (n_points == 0 || n_times == 0) return CED_OK;
-    CED_REQUIRE(target && times, "field_track_newton: null target/times");
-    CED_REQUIRE(x || step || evals, "field_track_newton: no output requested");
-    ced::TrackArgs A{};
-    A.n = n_points * n_times;
-    A.n_points = n_points;
-    A.bcast = 1;
-    A.target = target; A.t = times; A.init = init;
-    A.max_iters = max_iters; A.tol = tol;
-    A.x = x; A.step = step; A.evals = evals;
-    return ced::launch_newton(desc, A, "field_track_newton", stream);
+    return ced::solve_track(desc, n_points, n_times, target, times, init, max_iters, tol, x, step, evals, "field_track_newton",
+                            ced::launch_motion<ced::NewtonOp, 1>, stream);
 }

@@ -13,12 +13,13 @@
 // so a value computed here is the value the fused kernel computes internally, bit for bit.  Where the fused f16x2 kernel
 // runs its hidden layers on the K-doubled v_mfma_f32_16x16x32_f16 (half_kernel_k32; the blob then carries the K = 32
 // placements) these kernels evaluate that instruction's four blocks of eight products, in its order, on two
-// v_mfma_f32_16x16x16_f16 (mlp_layer_k32_blocks below): the K-doubled instruction stays confined to the two fused kernels
-// that hold their SIMDs alone, and these short kernels need no residency rule.
+// v_mfma_f32_16x16x16_f16 (mlp_layer_k32_blocks, field_move_device.hpp): the K-doubled instruction stays confined to the
+// two fused kernels that hold their SIMDs alone, and these short kernels need no residency rule.
 //
-// Shape: one network per 32-sample wave tile, workgroups persistent over tiles (wave w of workgroup b takes tiles
-// b * WAVES + w, + gridDim.x * WAVES, ...).  Only that network's layers are staged into LDS (motion: 44 KB fp32 or split
-// fp16, 22 KB fp16; head: 28 KB / 14 KB), not the fused kernel's 86 KB, so two 512-thread workgroups share a CU.
+// Shape: one network per 32-sample wave tile, workgroups persistent over tiles -- tile_kernel of field_move_device.hpp,
+// which every entry here instantiates with an op (MoveOp, TrackOp, RgbOp) and the weights of the descriptor's arithmetic.
+// Only that network's layers are staged into LDS (motion: 44 KB fp32 or split fp16, 22 KB fp16; head: 28 KB / 14 KB), not
+// the fused kernel's 86 KB, so two 512-thread workgroups share a CU.
 #include "ced_common.hpp"
 #include "field_device.hpp"
 #include "field_half_device.hpp"
@@ -75,23 +76,18 @@ template <int NT>
 __device__ __forceinline__ void load_samples(const MoveArgs &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[NT][3],
                                              float (&tq)[NT])
 {
+    if (!A.rays_mode) return load_points<NT>(A.pos, A.t, n_eff, tile_base, c, px, tq);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         int64_t s = tile_base + 16 * j + c;
         s = s < n_eff ? s : n_eff - 1;
-        if (A.rays_mode) {
-            const int64_t r_in = A.ray_idx[s];
-            const bool used = r_in >= 0;
-            const int64_t r = used ? r_in : 0;
-            const float tm2 = used ? A.t0[s] + A.t1[s] : 0.0f;
+        const int64_t r_in = A.ray_idx[s];
+        const bool used = r_in >= 0;
+        const int64_t r = used ? r_in : 0;
+        const float tm2 = used ? A.t0[s] + A.t1[s] : 0.0f;
 #pragma unroll
-            for (int a = 0; a < 3; ++a) px[j][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
-            tq[j] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
-        } else {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) px[j][a] = A.pos[3 * s + a];
-            tq[j] = A.t[s];
-        }
+        for (int a = 0; a < 3; ++a) px[j][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
+        tq[j] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
     }
 }
 
@@ -128,149 +124,77 @@ __device__ __forceinline__ void move_store(const MoveArgs &A, const float (&mv)[
     }
 }
 
-// ---- motion network, fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2) ------------------------------------------
-template <int NT, int THREADS>
-__global__ __launch_bounds__(THREADS) void move_kernel(MoveArgs A)
-{
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_eff = sample_count(A.n, A.n_dev);
-    const int64_t n_tiles = (n_eff + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+// ---- ced_field_move, ced_field_move_rays --------------------------------------------------------------------------------
+struct MoveOp : TileOp {
+    using Args = MoveArgs;
+    __device__ __forceinline__ static int64_t rows(const MoveArgs &A) { return sample_count(A.n, A.n_dev); }
 
-    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
-    __syncthreads();
-
-    // eval frames: one timestamp for every sample, its two Frequency features of this lane computed once (field_kernel.hpp)
-    const bool shared_time = A.rays_mode && !A.t_per_ray;
-    float t_feat[2] = { 0.0f, 0.0f };
-    if (shared_time) {
-        const float t_all = A.timestamps[0];
+    // eval frames: one timestamp for every sample, its two Frequency features of this lane computed once per workgroup
+    // (field_kernel.hpp); only the fp32 chain asks for features
+    struct Shared {
+        bool on;
+        float feat[2];
+    };
+    template <typename W> __device__ __forceinline__ static Shared prologue(const MoveArgs &A, int lane)
+    {
+        Shared sh{ A.rays_mode && !A.t_per_ray, { 0.0f, 0.0f } };
+        if constexpr (!W::kHalf) {
+            if (sh.on) {
+                const int g = lane >> 4;
+                const float t_all = A.timestamps[0];
 #pragma unroll
-        for (int S = 6; S < 8; ++S) t_feat[S - 6] = det_sinpi_phase(t_all * (float)(1 << (2 * (S & 1) + (g >> 1))), g & 1);
+                for (int S = 6; S < 8; ++S) sh.feat[S - 6] = det_sinpi_phase(t_all * (float)(1 << (2 * (S & 1) + (g >> 1))), g & 1);
+            }
+        }
+        return sh;
     }
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
-        int lds_off = 0;
-        asm volatile("" : "+v"(lds_off));
-        const float *const lw = lds + lds_off;
-        float px[NT][3], tq[NT], mv[NT][3];
-        load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
-        const auto time = [&](int j, float &f0, float &f1) {
-            if (shared_time) {
-                f0 = t_feat[0]; f1 = t_feat[1];
+    // RowTime, except that the shared timestamp's features are taken as they are: the shortcut stays a branch inside the
+    // encoding
+    template <int NT> struct Time {
+        const float (&tq)[NT];
+        const Shared &sh;
+        __device__ __forceinline__ float value(int j) const { return tq[j]; }
+        __device__ __forceinline__ void features(int j, int g, float &f0, float &f1) const
+        {
+            if (sh.on) {
+                f0 = sh.feat[0]; f1 = sh.feat[1];
             } else {
                 time_features(tq[j], g, f0, f1);
             }
-        };
-        motion_move<NT>(lw, lane, px, time, A.moving_step, A.use_div, mv);
-        move_store<NT>(A, mv, px, tile * TILE, n_eff, g, c);
-    }
-}
+        }
+    };
 
-// ---- motion network on fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2; K32: the blob has half_kernel_k32's placements) ----
-template <bool SPLIT, bool K32, int NT, int THREADS>
-__global__ __launch_bounds__(THREADS) void move_half_kernel(MoveArgs A)
-{
-    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_eff = sample_count(A.n, A.n_dev);
-    const int64_t n_tiles = (n_eff + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
-    if constexpr (SPLIT)
-        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        int lds_off = 0;
-        asm volatile("" : "+v"(lds_off));
-        const _Float16 *const whi = lds + lds_off;
-        const _Float16 *const wlo = whi + kMotionHalves;
+    template <typename W, int NT>
+    __device__ __forceinline__ static void tile(const MoveArgs &A, const Shared &sh, const typename W::Elem *w, int64_t tile_base,
+                                                int64_t n_eff, int lane)
+    {
+        const int g = lane >> 4, c = lane & 15;
         float px[NT][3], tq[NT], mv[NT][3];
-        load_samples<NT>(A, tile * TILE, n_eff, c, px, tq);
-        motion_move_half<SPLIT, K32, NT>(whi, wlo, lane, px, tq, A.moving_step, A.use_div, mv);
-        move_store<NT>(A, mv, px, tile * TILE, n_eff, g, c);
+        load_samples<NT>(A, tile_base, n_eff, c, px, tq);
+        motion_move<W, NT>(w, lane, px, Time<NT>{ tq, sh }, A.moving_step, A.use_div, mv);
+        move_store<NT>(A, mv, px, tile_base, n_eff, g, c);
     }
-}
+};
 
-template <int NT, int THREADS>
-__global__ __launch_bounds__(THREADS) void track_kernel(TrackArgs A)
-{
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    __shared__ __attribute__((aligned(16))) float lds[kMotionFloats];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionFloats / 4, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
+// ---- ced_field_move_inverse, ced_field_track: the fixed point on TrackRows (field_move_device.hpp) -----------------------
+struct TrackOp : TileOp {
+    using Args = TrackArgs;
+    template <typename W, int NT>
+    __device__ __forceinline__ static void tile(const TrackArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base,
+                                                int64_t, int lane)
+    {
+        const int g = lane >> 4, c = lane & 15;
         TrackRows<NT> R;
-        track_load<NT>(A, tile * TILE, c, R);
-        float tf[NT][2];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) time_features(R.tq[j], g, tf[j][0], tf[j][1]);   // the time does not move: once per tile
-        const auto time = [&](int j, float &f0, float &f1) { f0 = tf[j][0]; f1 = tf[j][1]; };
+        track_load<NT>(A, tile_base, c, R);
+        const HeldTime<NT> time = hold_time<W, NT>(R.tq, g);
         for (int it = 0; it < A.max_iters; ++it) {
-            // opaque LDS base per round: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
-            int lds_off = 0;
-            asm volatile("" : "+v"(lds_off));
             float mv[NT][3];
-            motion_move<NT>(lds + lds_off, lane, R.px, time, A.moving_step, A.use_div, mv);
+            motion_move<W, NT>(opaque(w), lane, R.px, time, A.moving_step, A.use_div, mv);
             if (__ballot(track_update<NT>(mv, A.tol, R)) == 0) break;    // wave-uniform
         }
-        track_store<NT>(A, R, tile * TILE, g, c);
+        track_store<NT>(A, R, tile_base, g, c);
     }
-}
-
-template <bool SPLIT, bool K32, int NT, int THREADS>
-__global__ __launch_bounds__(THREADS) void track_half_kernel(TrackArgs A)
-{
-    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[kMotionHalves * (SPLIT ? 2 : 1)];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kMotionHalves / 8, tid);
-    if constexpr (SPLIT)
-        stage<THREADS>(lds + kMotionHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kMotionHalves / 8, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        TrackRows<NT> R;
-        track_load<NT>(A, tile * TILE, c, R);
-        for (int it = 0; it < A.max_iters; ++it) {
-            int lds_off = 0;
-            asm volatile("" : "+v"(lds_off));
-            const _Float16 *const whi = lds + lds_off;
-            float mv[NT][3];
-            motion_move_half<SPLIT, K32, NT>(whi, whi + kMotionHalves, lane, R.px, R.tq, A.moving_step, A.use_div, mv);
-            if (__ballot(track_update<NT>(mv, A.tol, R)) == 0) break;    // wave-uniform
-        }
-        track_store<NT>(A, R, tile * TILE, g, c);
-    }
-}
+};
 
 // SH coefficient g of the head's input (model.py:447-459), as the fused kernels evaluate it: lane group g normalises
 // only the direction component it needs (Y00 const, Y1-1 ~ -y, Y10 ~ z, Y11 ~ -x; tcnn maps the unit vector to [0,1]
@@ -312,35 +236,23 @@ __device__ __forceinline__ void rgb_store(const RgbArgs &A, const f4 (&D)[NT][4]
     }
 }
 
-// ---- colour head, fp32 MFMA chain (CED_MLP_F32) --------------------------------------------------------------------
-template <int NT, int THREADS, bool BCAST = false>
-__global__ __launch_bounds__(THREADS) void rgb_kernel(RgbArgs A)
-{
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    constexpr int H0 = 0, H1 = H0 + layer_floats(4, 5), H2 = H1 + layer_floats(4, 16);
-    static_assert(H2 + layer_floats(1, 16) == kHeadFloats, "head layers");
-    __shared__ __attribute__((aligned(16))) float lds[kHeadFloats];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;
+// ---- ced_field_rgb, ced_field_rgb_bcast: the colour head on rows given one by one, or as embedding x direction -------------
+template <bool BCAST> struct RgbOp : TileOp {
+    using Args = RgbArgs;
 
-    stage<THREADS>(lds, A.weights, kHeadFloats / 4, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        int lds_off = 0;
-        asm volatile("" : "+v"(lds_off));
-        const float *const lw = lds + lds_off;
+    // fp32 MFMA chain (CED_MLP_F32)
+    template <int NT>
+    __device__ __forceinline__ static void head(const RgbArgs &A, const float *lw, int64_t tile_base, int lane, f4 (&D)[NT][4])
+    {
+        constexpr int H0 = 0, H1 = H0 + layer_floats(4, 5), H2 = H1 + layer_floats(4, 16);
+        static_assert(H2 + layer_floats(1, 16) == kHeadFloats, "head layers");
+        const int g = lane >> 4, c = lane & 15;
         float B[NT][16];
-        f4 D[NT][4];
         // head input [SH(4), geo(15)], k = 4S + g: k-step 0 is SH_g, k-steps 1..3 geometry feature 4S + g - 4, k-step 4
         // features 12 + g (g < 3) -- what the fused kernel's mlp_base leaves in those registers (base_out_neuron)
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            int64_t s = tile * TILE + 16 * j + c;
+            int64_t s = tile_base + 16 * j + c;
             s = s < A.n ? s : A.n - 1;
             int64_t sd, se;
             rgb_rows<BCAST>(A, s, sd, se);
@@ -355,42 +267,21 @@ __global__ __launch_bounds__(THREADS) void rgb_kernel(RgbArgs A)
         mlp_layer<16, 4, NT>(lw + H1, lane, B, D);
         to_operand<4, true, NT>(D, B);
         mlp_layer<16, 1, NT>(lw + H2, lane, B, D);
-        rgb_store<NT>(A, D, tile * TILE, g, c);
     }
-}
 
-// ---- colour head on fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2, CED_MLP_F32_HEAD16X2) -------------------------------------
-template <bool SPLIT, bool K32, int NT, int THREADS, bool BCAST = false>
-__global__ __launch_bounds__(THREADS) void rgb_half_kernel(RgbArgs A)
-{
-    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int TILE = 16 * NT;
-    using BL = Blob<false>;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[kHeadHalves * (SPLIT ? 2 : 1)];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t n_tiles = (A.n + TILE - 1) / TILE;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    stage<THREADS>(lds, A.weights, kHeadHalves / 8, tid);
-    if constexpr (SPLIT)
-        stage<THREADS>(lds + kHeadHalves, reinterpret_cast<const _Float16 *>(A.weights) + A.lo_halves, kHeadHalves / 8, tid);
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES) {
-        int lds_off = 0;
-        asm volatile("" : "+v"(lds_off));
-        const _Float16 *const whi = lds + lds_off;
-        const _Float16 *const wlo = whi + kHeadHalves;
+    // fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2, CED_MLP_F32_HEAD16X2)
+    template <bool SPLIT, bool K32, int NT>
+    __device__ __forceinline__ static void head_half(const RgbArgs &A, const _Float16 *whi, const _Float16 *wlo, int64_t tile_base,
+                                                     int lane, f4 (&D)[NT][4])
+    {
+        using BL = Blob<false>;
+        const int g = lane >> 4, c = lane & 15;
         h8 Bh[NT][2], Bl[NT][2];
-        f4 D[NT][4];
         // operand element 0 = SH_g, 1..4 = geometry features 4g .. 4g + 3 (feature 15 does not exist), saturated to the
         // fp16 range as the fused kernels saturate their mlp_base outputs
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            int64_t s = tile * TILE + 16 * j + c;
+            int64_t s = tile_base + 16 * j + c;
             s = s < A.n ? s : A.n - 1;
             int64_t sd, se;
             rgb_rows<BCAST>(A, s, sd, se);
@@ -410,72 +301,49 @@ __global__ __launch_bounds__(THREADS) void rgb_half_kernel(RgbArgs A)
         hidden_fed_layer<2, 4, NT, SPLIT, K32>(whi + BL::HF_H1 * kFragHalves, wlo + BL::HF_H1 * kFragHalves, lane, Bh, Bl, D);
         to_operand_h<NT, SPLIT>(D, Bh, Bl);
         hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::HF_H2 * kFragHalves, wlo + BL::HF_H2 * kFragHalves, lane, Bh, Bl, D);
-        rgb_store<NT>(A, D, tile * TILE, g, c);
     }
-}
+
+    template <typename W, int NT>
+    __device__ __forceinline__ static void tile(const RgbArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base, int64_t,
+                                                int lane)
+    {
+        f4 D[NT][4];
+        if constexpr (W::kHalf) head_half<W::kSplit, W::kK32, NT>(A, w, w + W::kPlane, tile_base, lane, D);
+        else head<NT>(A, w, tile_base, lane, D);
+        rgb_store<NT>(A, D, tile_base, lane >> 4, lane & 15);
+    }
+};
 
 static int launch_move(const ced_field_desc *d, MoveArgs &A, const char *who, void *stream)
 {
     for (int i = 0; i < 6; ++i) A.aabb[i] = d->aabb[i];
-    A.moving_step = d->moving_step;
-    A.use_div = d->use_div_offsets ? 1 : 0;
-    A.weights = d->packed_weights;                    // every blob starts with the motion network
-    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
-    const int mw = d->max_workgroups;
-    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
-        launch_tiles<2, 512>(move_kernel<2, 512>, A, A.n, 2, mw, stream);
-    else if (d->mlp_precision == CED_MLP_F16)
-        launch_tiles<2, 512>(move_half_kernel<false, false, 2, 512>, A, A.n, 2, mw, stream);
-    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
-        launch_tiles<2, 512>(move_half_kernel<true, true, 2, 512>, A, A.n, 2, mw, stream);
-    else
-        launch_tiles<2, 512>(move_half_kernel<true, false, 2, 512>, A, A.n, 2, mw, stream);
-    return check_launch(who);
+    return launch_motion<MoveOp, 2>(d, A, who, stream);
 }
 
-// the fixed-point kernel for the descriptor's arithmetic: launch_move's four variants, the same launch geometry
-static int launch_track(const ced_field_desc *d, TrackArgs &A, const char *who, void *stream)
-{
-    A.moving_step = d->moving_step;
-    A.use_div = d->use_div_offsets ? 1 : 0;
-    A.weights = d->packed_weights;
-    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
-    const int mw = d->max_workgroups;
-    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
-        launch_tiles<2, 512>(track_kernel<2, 512>, A, A.n, 2, mw, stream);
-    else if (d->mlp_precision == CED_MLP_F16)
-        launch_tiles<2, 512>(track_half_kernel<false, false, 2, 512>, A, A.n, 2, mw, stream);
-    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
-        launch_tiles<2, 512>(track_half_kernel<true, true, 2, 512>, A, A.n, 2, mw, stream);
-    else
-        launch_tiles<2, 512>(track_half_kernel<true, false, 2, 512>, A, A.n, 2, mw, stream);
-    return check_launch(who);
-}
-
-// the head's kernel for the descriptor's arithmetic, on rows given one by one (ced_field_rgb) or as embedding x direction
+// the head in the descriptor's arithmetic; its layers sit behind the other networks' at an offset the time encoding moves
 template <bool BCAST> static int launch_rgb(const ced_field_desc *desc, RgbArgs &A, const char *who, void *stream)
 {
-    const int64_t n = A.n;
+    using Op = RgbOp<BCAST>;
     const bool te = desc->time_mode != 0;
     const int mw = desc->max_workgroups;
     if (desc->mlp_precision == CED_MLP_F32) {
         A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
-        launch_tiles<2, 512>(rgb_kernel<2, 512, BCAST>, A, n, 2, mw, stream);
+        launch_tiles<Op, F32Weights<kHeadFloats>, 2>(A, mw, stream);
     } else if (desc->mlp_precision == CED_MLP_F32_HEAD16X2) {
         // the mixed blob: fp16 fragments in the fp32 head's region, high parts then remainders, pair-form placements
         A.weights = reinterpret_cast<const float *>(desc->packed_weights) + (te ? Blob<true>::H0 : Blob<false>::H0);
         A.lo_halves = kHeadHalves;
-        launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512, BCAST>, A, n, 2, mw, stream);
+        launch_tiles<Op, HalfWeights<kHeadHalves, true, false>, 2>(A, mw, stream);
     } else {
         A.weights = reinterpret_cast<const _Float16 *>(desc->packed_weights) +
                     (int64_t)(te ? HalfBlob<true>::H0 : HalfBlob<false>::H0) * kFragHalves;
         A.lo_halves = (int64_t)(te ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
         if (desc->mlp_precision == CED_MLP_F16)
-            launch_tiles<2, 512>(rgb_half_kernel<false, false, 2, 512, BCAST>, A, n, 2, mw, stream);
+            launch_tiles<Op, HalfWeights<kHeadHalves, false, false>, 2>(A, mw, stream);
         else if (half_layout_k32(desc->time_mode, desc->mlp_precision, desc->hash.temporal))
-            launch_tiles<2, 512>(rgb_half_kernel<true, true, 2, 512, BCAST>, A, n, 2, mw, stream);
+            launch_tiles<Op, HalfWeights<kHeadHalves, true, true>, 2>(A, mw, stream);
         else
-            launch_tiles<2, 512>(rgb_half_kernel<true, false, 2, 512, BCAST>, A, n, 2, mw, stream);
+            launch_tiles<Op, HalfWeights<kHeadHalves, true, false>, 2>(A, mw, stream);
     }
     return check_launch(who);
 }
@@ -523,44 +391,16 @@ extern "C" int ced_field_move_inverse(const ced_field_desc *desc, int64_t n, con
                                       const float *init, int32_t max_iters, float tol, float *x, float *step,
                                       int32_t *evals, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_move_inverse");
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "field_move_inverse: n < 0");
-    rc = ced::validate_solve(max_iters, tol, "field_move_inverse");
-    if (rc) return rc;
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(target && t, "field_move_inverse: null target/t");
-    CED_REQUIRE(x || step || evals, "field_move_inverse: no output requested");
-    ced::TrackArgs A{};
-    A.n = n;
-    A.target = target; A.t = t; A.init = init;
-    A.max_iters = max_iters; A.tol = tol;
-    A.x = x; A.step = step; A.evals = evals;
-    return ced::launch_track(desc, A, "field_move_inverse", stream);
+    return ced::solve_rows(desc, n, target, t, init, max_iters, tol, x, step, evals, "field_move_inverse",
+                           ced::launch_motion<ced::TrackOp, 2>, stream);
 }
 
 extern "C" int ced_field_track(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target,
                                const float *times, const float *init, int32_t max_iters, float tol, float *x,
                                float *step, int32_t *evals, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_track");
-    if (rc) return rc;
-    CED_REQUIRE(n_points >= 0 && n_times >= 0, "field_track: n_points=%lld n_times=%lld", (long long)n_points,
-                (long long)n_times);
-    CED_REQUIRE(n_points <= INT64_MAX / 3 / (n_times > 0 ? n_times : 1), "field_track: n_points * n_times overflows");
-    rc = ced::validate_solve(max_iters, tol, "field_track");
-    if (rc) return rc;
-    if (n_points == 0 || n_times == 0) return CED_OK;
-    CED_REQUIRE(target && times, "field_track: null target/times");
-    CED_REQUIRE(x || step || evals, "field_track: no output requested");
-    ced::TrackArgs A{};
-    A.n = n_points * n_times;
-    A.n_points = n_points;
-    A.bcast = 1;
-    A.target = target; A.t = times; A.init = init;
-    A.max_iters = max_iters; A.tol = tol;
-    A.x = x; A.step = step; A.evals = evals;
-    return ced::launch_track(desc, A, "field_track", stream);
+    return ced::solve_track(desc, n_points, n_times, target, times, init, max_iters, tol, x, step, evals, "field_track",
+                            ced::launch_motion<ced::TrackOp, 2>, stream);
 }
 
 extern "C" int ced_field_rgb(const ced_field_desc *desc, int64_t n, const float *dirs, const float *embedding,

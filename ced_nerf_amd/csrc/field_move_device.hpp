@@ -1,8 +1,18 @@
-// Device code of the motion network shared by field_move.hip (ced_field_move, ced_field_move_inverse, ced_field_track)
-// and field_jacobian.hip (ced_field_move_jacobian and the Newton inverse): weight staging, the encode -> four layers -> move
-// chain in the three arithmetics, the K = 32 blocks on the K = 16 instruction, the rows a solver keeps in registers, and
-// the launch / validation helpers of their entries.  One statement of the arithmetic, so every kernel built on it
-// computes ced_field_move's bits.
+// Device code of the motion network and of the colour head on their own, shared by field_move.hip (ced_field_move,
+// ced_field_move_inverse, ced_field_track, ced_field_rgb) and field_jacobian.hip (ced_field_move_jacobian and the Newton
+// inverse).
+//
+// Every kernel of the two files is tile_kernel<Op, W, NT, THREADS>.  The skeleton fixes, once: the wave's tiles of
+// 16 * NT rows (wave w of workgroup b takes tiles b * WAVES + w, + gridDim.x * WAVES, ...), the workgroup-uniform early
+// return, the staging of one network's layers into LDS and its barrier, and the opaque LDS base of each tile.
+//   W, the weights (F32Weights, HalfWeights): the LDS element type, the size of one plane, whether a plane of remainders
+//      follows it (in LDS directly behind, in the blob A.lo_halves after A.weights), whether the blob has the K = 32
+//      placements.  A tile body gets the base of the first plane.
+//   Op, what one tile does: its Args (the kernel's argument; n, weights and lo_halves are read here), tile(), and -- where
+//      TileOp's defaults do not fit -- the row count and a once-per-workgroup prologue whose result every tile receives.
+// Below them: the encode -> four layers -> move chain in the three arithmetics (motion_move), the K = 32 blocks on the
+// K = 16 instruction, the rows a solver keeps in registers, and the launch / validation helpers of the entries.  One
+// statement of the arithmetic, so every kernel built on it computes ced_field_move's bits.
 #pragma once
 #include "ced_common.hpp"
 #include "field_device.hpp"
@@ -40,9 +50,93 @@ template <int THREADS> __device__ __forceinline__ void stage(void *dst, const vo
     for (int i = tid; i < count; i += THREADS) d[i] = s[i];
 }
 
-// query_move's `move` (model.py:354-365) from the motion network's accumulators (rows natural: row a on lane group 0
-// register a; rows 3,4,5 on (g0,r3), (g1,r0), (g1,r1)), as the fused kernels state it.  Every lane gets all three
-// components of its column's samples.
+// ---- what a kernel stages ------------------------------------------------------------------------------------------
+template <int FLOATS> struct F32Weights {             // fp32 layers for the fp32 MFMA chain
+    using Elem = float;
+    static constexpr int kPlane = FLOATS;
+    static constexpr bool kHalf = false, kSplit = false, kK32 = false;
+};
+template <int HALVES, bool SPLIT, bool K32> struct HalfWeights {   // fp16 fragments; SPLIT: high parts, then remainders
+    static_assert(!K32 || SPLIT, "only the f16x2 blob has K = 32 placements");
+    using Elem = _Float16;
+    static constexpr int kPlane = HALVES;
+    static constexpr bool kHalf = true, kSplit = SPLIT, kK32 = K32;
+};
+
+// what an op leaves to the skeleton unless it says otherwise: A.n rows, nothing computed once per workgroup
+struct TileOp {
+    struct Shared {};
+    template <typename Args> __device__ __forceinline__ static int64_t rows(const Args &A) { return A.n; }
+    template <typename W, typename Args> __device__ __forceinline__ static Shared prologue(const Args &, int) { return {}; }
+};
+
+// An LDS base the compiler cannot see through: keeps the A-fragment reads inside the loop it is taken in (see
+// field_kernel.hpp).  The skeleton takes it per tile; a solver, which evaluates the network up to max_iters times per
+// tile, takes it again per round.
+template <typename T> __device__ __forceinline__ const T *opaque(const T *lds)
+{
+    int lds_off = 0;
+    asm volatile("" : "+v"(lds_off));
+    return lds + lds_off;
+}
+
+template <typename Op, typename W, int NT, int THREADS>
+__global__ __launch_bounds__(THREADS) void tile_kernel(typename Op::Args A)
+{
+    using Elem = typename W::Elem;
+    constexpr int WAVES = THREADS / kWave;
+    constexpr int TILE = 16 * NT;
+    constexpr int kPlaneWords = W::kPlane * (int)sizeof(Elem) / 16;
+    __shared__ __attribute__((aligned(16))) Elem lds[W::kPlane * (W::kSplit ? 2 : 1)];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int64_t n = Op::rows(A);
+    const int64_t n_tiles = (n + TILE - 1) / TILE;
+    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
+
+    const Elem *const blob = reinterpret_cast<const Elem *>(A.weights);
+    stage<THREADS>(lds, blob, kPlaneWords, tid);
+    if constexpr (W::kSplit) stage<THREADS>(lds + W::kPlane, blob + A.lo_halves, kPlaneWords, tid);
+    __syncthreads();
+
+    const typename Op::Shared shared = Op::template prologue<W>(A, lane);
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES)
+        Op::template tile<W, NT>(A, shared, opaque(lds), tile * TILE, n, lane);
+}
+
+// position and time of sample c of each 16-sample column tile, rows given one by one; a ragged last tile repeats the last
+// sample (never stored)
+template <int NT>
+__device__ __forceinline__ void load_points(const float *pos, const float *t, int64_t n, int64_t tile_base, int c,
+                                            float (&px)[NT][3], float (&tq)[NT])
+{
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        int64_t s = tile_base + 16 * j + c;
+        s = s < n ? s : n - 1;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) px[j][a] = pos[3 * s + a];
+        tq[j] = t[s];
+    }
+}
+
+// The last layer's accumulators hold the output rows naturally: offset a on (lane group 0, register a), fine offset a
+// (row 3 + a) on (g0,r3), (g1,r0), (g1,r1).  fine_row: that row's value of column c; fine_tanh: the tanh the fused
+// kernels take of it.
+__device__ __forceinline__ float fine_row(const f4 &D0, int a, int c)
+{
+    constexpr int kFineReg[3] = { 3, 0, 1 };
+    return __shfl(D0[kFineReg[a]], (a == 0) ? c : 16 + c, 64);
+}
+
+__device__ __forceinline__ float fine_tanh(float fine)
+{
+    const float e = det_expf(2.0f * fine);
+    return 1.0f - 2.0f / (e + 1.0f);
+}
+
+// query_move's `move` (model.py:354-365) from the motion network's accumulators, as the fused kernels state it.  Every
+// lane gets all three components of its column's samples.
 template <int NT>
 __device__ __forceinline__ void move_vector(const f4 (&D)[NT][4], float moving_step, int use_div, int c, float (&mv)[NT][3])
 {
@@ -52,13 +146,7 @@ __device__ __forceinline__ void move_vector(const f4 (&D)[NT][4], float moving_s
         for (int a = 0; a < 3; ++a) {
             const float off = __shfl(D[j][0][a], c, 64);
             float m = off * moving_step;
-            if (use_div) {
-                constexpr int kFineReg[3] = { 3, 0, 1 };
-                const float fine = __shfl(D[j][0][kFineReg[a]], (a == 0) ? c : 16 + c, 64);
-                const float e = det_expf(2.0f * fine);
-                const float th = 1.0f - 2.0f / (e + 1.0f);
-                m = m + th * moving_step;
-            }
+            if (use_div) m = m + fine_tanh(fine_row(D[j][0], a, c)) * moving_step;
             mv[j][a] = m;
         }
     }
@@ -150,9 +238,8 @@ __device__ __forceinline__ void hidden_fed_layer(const _Float16 *__restrict__ wh
 }
 
 // ---- the motion network on one wave tile: encode -> four layers -> move -------------------------------------------------
-// Shared by the kernels that hand `move` out once (move_kernel, move_half_kernel) and by the fixed-point loop that
-// evaluates it up to max_iters times on a position held in registers (track_kernel, track_half_kernel): one statement
-// of the arithmetic, so every evaluation has ced_field_move's bits.
+// Shared by the ops that hand `move` out once and by the solvers that evaluate it up to max_iters times on a position
+// held in registers: one statement of the arithmetic, so every evaluation has ced_field_move's bits.
 
 // fp32 chain: the two Frequency features of time tq that lane group g feeds (field_kernel.hpp: k = 4S + g, S = 6, 7)
 __device__ __forceinline__ void time_features(float tq, int g, float &f0, float &f1)
@@ -165,17 +252,37 @@ __device__ __forceinline__ void time_features(float tq, int g, float &f0, float 
     f0 = __uint_as_float(sw[0]); f1 = __uint_as_float(sw[1]);
 }
 
-// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): lw = the staged layers M0..M3; time(j, f0, f1) gives the two time
-// features of column tile j where the encoding wants them (time_features, or values the caller holds already)
-template <int NT, typename Time>
-__device__ __forceinline__ void motion_move(const float *lw, int lane, const float (&px)[NT][3], Time time, float moving_step,
-                                            int use_div, float (&mv)[NT][3])
+// Where a chain takes the time of column tile j from: the fp16 encodings ask for its value, the fp32 encoding for the two
+// features of it that the lane feeds.  RowTime: each row's own time, the features made where the encoding wants them, so
+// no feature array is live beside the operands.  HeldTime (hold_time): a solver's rows, whose time does not move -- the
+// features are made once per tile.
+template <int NT> struct RowTime {
+    const float (&tq)[NT];
+    __device__ __forceinline__ float value(int j) const { return tq[j]; }
+    __device__ __forceinline__ void features(int j, int g, float &f0, float &f1) const { time_features(tq[j], g, f0, f1); }
+};
+
+template <int NT> struct HeldTime {
+    const float (&tq)[NT];
+    float tf[NT][2];
+    __device__ __forceinline__ float value(int j) const { return tq[j]; }
+    __device__ __forceinline__ void features(int j, int, float &f0, float &f1) const { f0 = tf[j][0]; f1 = tf[j][1]; }
+};
+
+template <typename W, int NT> __device__ __forceinline__ HeldTime<NT> hold_time(const float (&tq)[NT], int g)
 {
-    using BL = Blob<false>;
-    const int g = lane >> 4, c = lane & 15;
-    float B[NT][16];
-    f4 D[NT][4];
-    // tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g)
+    HeldTime<NT> held{ tq, {} };
+    if constexpr (!W::kHalf) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) time_features(tq[j], g, held.tf[j][0], held.tf[j][1]);
+    }
+    return held;
+}
+
+// fp32 chain: tcnn Frequency(4) on (x,y,z,t) in the fused kernel's operand order (field_kernel.hpp: k = 4S + g): B[j][0 .. 7]
+template <int NT, typename Time>
+__device__ __forceinline__ void motion_encode(const float (&px)[NT][3], const Time &time, int g, float (&B)[NT][16])
+{
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const bool odd = (g & 1) != 0;
@@ -192,8 +299,31 @@ __device__ __forceinline__ void motion_move(const float *lw, int lane, const flo
         det_sinpi_both(px[j][2] * scz, p0, p1);
         sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(p0), __float_as_uint(p1), false, false);
         B[j][4] = __uint_as_float(sw[0]); B[j][5] = __uint_as_float(sw[1]);
-        time(j, B[j][6], B[j][7]);
+        time.features(j, g, B[j][6], B[j][7]);
     }
+}
+
+// fp16 operands: tcnn Frequency(4), lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
+__device__ __forceinline__ void motion_features_half(const float (&px)[3], float tq, int g, float (&f)[8])
+{
+    float v = tq;
+    v = (g == 0) ? px[0] : v;
+    v = (g == 1) ? px[1] : v;
+    v = (g == 2) ? px[2] : v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
+}
+
+// fp32 MFMA chain (CED_MLP_F32, CED_MLP_F32_HEAD16X2): lw = the staged layers M0..M3
+template <int NT, typename Time>
+__device__ __forceinline__ void motion_move_f32(const float *lw, int lane, const float (&px)[NT][3], const Time &time,
+                                                float moving_step, int use_div, float (&mv)[NT][3])
+{
+    using BL = Blob<false>;
+    const int g = lane >> 4, c = lane & 15;
+    float B[NT][16];
+    f4 D[NT][4];
+    motion_encode<NT>(px, time, g, B);
     mlp_layer<8, 4, NT>(lw + BL::M0, lane, B, D);
     to_operand<4, true, NT>(D, B);
     mlp_layer<16, 4, NT>(lw + BL::M1, lane, B, D);
@@ -205,24 +335,18 @@ __device__ __forceinline__ void motion_move(const float *lw, int lane, const flo
 }
 
 // fp16 MFMAs (CED_MLP_F16, CED_MLP_F16X2; K32: the blob has half_kernel_k32's placements): whi / wlo = the staged planes
-template <bool SPLIT, bool K32, int NT>
+template <bool SPLIT, bool K32, int NT, typename Time>
 __device__ __forceinline__ void motion_move_half(const _Float16 *whi, const _Float16 *wlo, int lane, const float (&px)[NT][3],
-                                                 const float (&tq)[NT], float moving_step, int use_div, float (&mv)[NT][3])
+                                                 const Time &time, float moving_step, int use_div, float (&mv)[NT][3])
 {
     using BL = HalfBlob<false>;
     const int g = lane >> 4, c = lane & 15;
     h8 Bh[NT][2], Bl[NT][2];
     f4 D[NT][4];
-    // tcnn Frequency(4): lane group g owns dimension g; e = 2 * freq + phase (field_half.hip)
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
-        float v = tq[j];
-        v = (g == 0) ? px[j][0] : v;
-        v = (g == 1) ? px[j][1] : v;
-        v = (g == 2) ? px[j][2] : v;
         float f[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = det_sinpi_phase(v * (float)(1 << (e >> 1)), e & 1);
+        motion_features_half(px[j], time.value(j), g, f);
         to_half8<SPLIT>(f, Bh[j][0], Bl[j][0]);
     }
     mlp_layer_h<1, 4, NT, SPLIT>(whi + BL::M0 * kFragHalves, wlo + BL::M0 * kFragHalves, lane, Bh, Bl, D);
@@ -233,6 +357,15 @@ __device__ __forceinline__ void motion_move_half(const _Float16 *whi, const _Flo
     to_operand_h<NT, SPLIT>(D, Bh, Bl);
     hidden_fed_layer<2, 1, NT, SPLIT, K32>(whi + BL::M3 * kFragHalves, wlo + BL::M3 * kFragHalves, lane, Bh, Bl, D);
     move_vector<NT>(D, moving_step, use_div, c, mv);
+}
+
+// the chain in the arithmetic of the staged weights W; w = the tile's LDS base
+template <typename W, int NT, typename Time>
+__device__ __forceinline__ void motion_move(const typename W::Elem *w, int lane, const float (&px)[NT][3], const Time &time,
+                                            float moving_step, int use_div, float (&mv)[NT][3])
+{
+    if constexpr (W::kHalf) motion_move_half<W::kSplit, W::kK32, NT>(w, w + W::kPlane, lane, px, time, moving_step, use_div, mv);
+    else motion_move_f32<NT>(w, lane, px, time, moving_step, use_div, mv);
 }
 
 // ---- the warp's inverse: x + move(x, t) = target by fixed-point iteration (include/cednerf_hip.h states it) -----------
@@ -316,16 +449,44 @@ __device__ __forceinline__ void track_store(const TrackArgs &A, const TrackRows<
     }
 }
 
-// Persistent launch: enough workgroups for the tiles, at most per_cu per CU (the descriptor's max_workgroups caps it).
-template <int NT, int THREADS, typename Kernel, typename Args>
-static void launch_tiles(Kernel kernel, const Args &A, int64_t n, int per_cu, int max_workgroups, void *stream)
+// Persistent launch of Op on the weights W, NT 16-row tiles per wave: workgroups of 512 threads, enough for the tiles, at
+// most two per CU (the descriptor's max_workgroups caps it).
+template <typename Op, typename W, int NT>
+static void launch_tiles(const typename Op::Args &A, int max_workgroups, void *stream)
 {
-    const int64_t n_tiles = (n + 16 * NT - 1) / (16 * NT);
+    constexpr int THREADS = 512, per_cu = 2;
+    const int64_t n_tiles = (A.n + 16 * NT - 1) / (16 * NT);
     constexpr int waves = THREADS / 64;
     int64_t blocks = (n_tiles + waves - 1) / waves;
     const int64_t cap = max_workgroups > 0 ? max_workgroups : (int64_t)kFieldBlocksDefault * per_cu;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL((tile_kernel<Op, W, NT, THREADS>), dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
+}
+
+// what every op on the motion network reads from the descriptor
+template <typename Args> static void motion_args(const ced_field_desc *d, Args &A)
+{
+    A.moving_step = d->moving_step;
+    A.use_div = d->use_div_offsets ? 1 : 0;
+    A.weights = d->packed_weights;                    // every blob starts with the motion network
+    A.lo_halves = (int64_t)(d->time_mode ? HalfBlob<true>::FRAGS : HalfBlob<false>::FRAGS) * kFragHalves;
+}
+
+// Op on the motion network in the descriptor's arithmetic: the fp32 chain, fp16 operands, or split fp16 on the blob's
+// K = 32 placements or on the pair form
+template <typename Op, int NT> static int launch_motion(const ced_field_desc *d, typename Op::Args &A, const char *who, void *stream)
+{
+    motion_args(d, A);
+    const int mw = d->max_workgroups;
+    if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
+        launch_tiles<Op, F32Weights<kMotionFloats>, NT>(A, mw, stream);
+    else if (d->mlp_precision == CED_MLP_F16)
+        launch_tiles<Op, HalfWeights<kMotionHalves, false, false>, NT>(A, mw, stream);
+    else if (half_layout_k32(d->time_mode, d->mlp_precision, d->hash.temporal))
+        launch_tiles<Op, HalfWeights<kMotionHalves, true, true>, NT>(A, mw, stream);
+    else
+        launch_tiles<Op, HalfWeights<kMotionHalves, true, false>, NT>(A, mw, stream);
+    return check_launch(who);
 }
 
 // the descriptor fields these entries read; the hash table is not touched, but its kind selects the blob's layout
@@ -348,6 +509,54 @@ static int validate_solve(int32_t max_iters, float tol, const char *who)
     CED_REQUIRE(max_iters >= 1 && max_iters <= 1024, "%s: max_iters=%d outside 1 .. 1024", who, max_iters);
     CED_REQUIRE(tol >= 0.0f, "%s: tol=%g must be >= 0 (and not a NaN)", who, (double)tol);
     return CED_OK;
+}
+
+// ---- the bodies of the solver entries: `launch` is the fixed-point or the Newton op on the motion network ------------------
+typedef int (*SolveLaunch)(const ced_field_desc *, TrackArgs &, const char *, void *);
+
+// ced_field_move_inverse, ced_field_move_inverse_newton: rows given one by one
+static int solve_rows(const ced_field_desc *desc, int64_t n, const float *target, const float *t, const float *init,
+                      int32_t max_iters, float tol, float *x, float *step, int32_t *evals, const char *who, SolveLaunch launch,
+                      void *stream)
+{
+    int rc = validate_desc(desc, who);
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "%s: n < 0", who);
+    rc = validate_solve(max_iters, tol, who);
+    if (rc) return rc;
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(target && t, "%s: null target/t", who);
+    CED_REQUIRE(x || step || evals, "%s: no output requested", who);
+    TrackArgs A{};
+    A.n = n;
+    A.target = target; A.t = t; A.init = init;
+    A.max_iters = max_iters; A.tol = tol;
+    A.x = x; A.step = step; A.evals = evals;
+    return launch(desc, A, who, stream);
+}
+
+// ced_field_track, ced_field_track_newton: every (time, point) pair
+static int solve_track(const ced_field_desc *desc, int64_t n_points, int64_t n_times, const float *target, const float *times,
+                       const float *init, int32_t max_iters, float tol, float *x, float *step, int32_t *evals, const char *who,
+                       SolveLaunch launch, void *stream)
+{
+    int rc = validate_desc(desc, who);
+    if (rc) return rc;
+    CED_REQUIRE(n_points >= 0 && n_times >= 0, "%s: n_points=%lld n_times=%lld", who, (long long)n_points, (long long)n_times);
+    CED_REQUIRE(n_points <= INT64_MAX / 3 / (n_times > 0 ? n_times : 1), "%s: n_points * n_times overflows", who);
+    rc = validate_solve(max_iters, tol, who);
+    if (rc) return rc;
+    if (n_points == 0 || n_times == 0) return CED_OK;
+    CED_REQUIRE(target && times, "%s: null target/times", who);
+    CED_REQUIRE(x || step || evals, "%s: no output requested", who);
+    TrackArgs A{};
+    A.n = n_points * n_times;
+    A.n_points = n_points;
+    A.bcast = 1;
+    A.target = target; A.t = times; A.init = init;
+    A.max_iters = max_iters; A.tol = tol;
+    A.x = x; A.step = step; A.evals = evals;
+    return launch(desc, A, who, stream);
 }
 
 }  // namespace ced
