@@ -300,7 +300,7 @@ std::atomic<int> g_field_spread_tiles{ 2 };     // field kernels: tile -> wave m
 std::atomic<int> g_march_two_pass{ -1 };        // frame renderer: first iteration as culling pass + marching of the rest (-1: when there are several grid levels)
 static std::atomic<int> g_hash_grad_blocks{ 0 }; // table-gradient workgroups per level (0: one per 64 samples)
 
-static int validate_hash(const ced_hash_desc *h, const char *who)
+int validate_hash(const ced_hash_desc *h, const char *who)
 {
     CED_REQUIRE(h != nullptr, "%s: null hash descriptor", who);
     CED_REQUIRE(h->n_levels >= 1 && h->n_levels <= CED_MAX_LEVELS, "%s: n_levels=%d out of range", who, h->n_levels);

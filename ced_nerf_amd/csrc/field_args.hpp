@@ -52,6 +52,8 @@ void launch_field_grid(Kernel kernel, const FieldArgs &A, void *stream)
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
 }
 
+// field.hip: what every entry that reads the hash table checks of its descriptor
+int validate_hash(const ced_hash_desc *h, const char *who);
 // Fills the field/hash parts of A from the descriptor, validates, and launches on `stream`.
 int launch_field(const ced_field_desc *d, FieldArgs &A, void *stream);
 // field_half.hip: the f16x2 / f16 MLP variants (A already filled by launch_field)

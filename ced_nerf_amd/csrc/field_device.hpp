@@ -253,6 +253,95 @@ __device__ __forceinline__ void hash_level(const LevelConst &L, const void *__re
     f1 = acc[1];
 }
 
+// hash_level with the derivative of both features with respect to the normalised position (field_density_gradient.hip).
+// The features are hash_level's bits: the same corner weights, the same eight fused multiply-adds in the same order, on
+// the same corner values (MODE 0 or 2; a dense level goes through MODE 0, which reads what MODE 1 and 3 read).  Inside
+// the cell the fp32 floor above selects, the fraction's derivative is the level's scale exactly, so with v[c] the
+// (time-interpolated) corner values and (wx, wy, wz)[0 / 1] = 1 - frac / frac per axis
+//     d f / d x_a = (scale * dscale) * sum over the four corner pairs along axis a of  (weight of the other two axes) * (v[upper] - v[lower])
+// each difference, weight product and fused multiply-add rounded once, pairs in ascending corner order.  dscale is an
+// exact power of two the caller carries its tangents by.
+template <bool F16, bool TEMPORAL, int MODE>
+__device__ __forceinline__ void hash_level_dx(const LevelConst &L, const void *__restrict__ table, const float (&x)[3],
+                                              int k_lo, float t_frac, float dscale, float &f0, float &f1, float (&d0)[3],
+                                              float (&d1)[3])
+{
+    static_assert(MODE == 0 || MODE == 2, "hash_level_dx: mixed (0) or hashed (2) index form");
+    uint32_t g[3];
+    float fr[3], om[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p = x[a] * L.scale + 0.5f;
+        g[a] = (uint32_t)p;
+        fr[a] = __builtin_amdgcn_fractf(p);
+        om[a] = 1.0f - fr[a];
+    }
+    constexpr uint32_t EB = EntryBytes<F16, TEMPORAL>::value;
+    const uint32_t x0 = g[0] * EB;
+    const uint32_t y0 = g[1] * L.syb;
+    const uint32_t z0 = g[2] * L.szb;
+    const uint32_t xs[2] = { x0, x0 + EB };
+    const uint32_t ys[2] = { y0, y0 + L.syb };
+    const uint32_t zs[2] = { z0, z0 + L.szb };
+    const bool hashed = L.hashed != 0;
+    const float wxy[4] = { om[0] * om[1], fr[0] * om[1], om[0] * fr[1], fr[0] * fr[1] };   // index cx + 2*cy
+    const char *tb = reinterpret_cast<const char *>(table);
+    const float omt = 1.0f - t_frac;
+    const f2 omt2 = { omt, omt }, tf2 = { t_frac, t_frac };
+    const uint32_t kb = TEMPORAL ? (uint32_t)k_lo * (F16 ? 4u : 8u) : 0u;
+    f2 v[8];
+    float w[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int cx = c & 1, cy = (c >> 1) & 1, cz = (c >> 2) & 1;
+        const uint32_t hb = (xs[cx] ^ (ys[cy] ^ zs[cz])) & L.maskb;
+        uint32_t idxb = hb;
+        if constexpr (MODE == 0) {
+            const uint32_t dx = xs[cx] + (ys[cy] + zs[cz]);
+            const uint32_t dw = dx - L.sizeb;
+            const uint32_t db = dx < dw ? dx : dw;
+            idxb = hashed ? hb : db;
+        }
+        const char *entry = tb + (L.offb + idxb) + kb;
+        w[c] = wxy[cx + 2 * cy] * (cz ? fr[2] : om[2]);
+        if constexpr (!TEMPORAL && !F16) {
+            v[c] = *reinterpret_cast<const f2 *>(entry);
+        } else if constexpr (!TEMPORAL) {
+            const uint32_t u = *reinterpret_cast<const uint32_t *>(entry);
+            v[c] = f2{ half_bits_to_float((uint16_t)(u & 0xffffu)), half_bits_to_float((uint16_t)(u >> 16)) };
+        } else if constexpr (!F16) {
+            const f4 pr = *reinterpret_cast<const f4 *>(entry);
+            const f2 lo = { pr[0], pr[1] }, hi = { pr[2], pr[3] };
+            v[c] = lo * omt2 + hi * tf2;
+        } else {
+            typedef uint32_t u2t __attribute__((ext_vector_type(2)));
+            const u2t pr = *reinterpret_cast<const u2t *>(entry);
+            const f2 a = { half_bits_to_float((uint16_t)(pr[0] & 0xffffu)), half_bits_to_float((uint16_t)(pr[0] >> 16)) };
+            const f2 b = { half_bits_to_float((uint16_t)(pr[1] & 0xffffu)), half_bits_to_float((uint16_t)(pr[1] >> 16)) };
+            v[c] = a * omt2 + b * tf2;
+        }
+    }
+    f2 acc = { 0.0f, 0.0f };
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc = __builtin_elementwise_fma(f2{ w[c], w[c] }, v[c], acc);
+    f0 = acc[0];
+    f1 = acc[1];
+
+    f2 gx = { 0.0f, 0.0f }, gy = { 0.0f, 0.0f }, gz = { 0.0f, 0.0f };
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int lo = q & 1, hi = q >> 1;
+        const float wyz = (lo ? fr[1] : om[1]) * (hi ? fr[2] : om[2]);       // x pairs: cy = lo, cz = hi
+        const float wxz = (lo ? fr[0] : om[0]) * (hi ? fr[2] : om[2]);       // y pairs: cx = lo, cz = hi
+        gx = __builtin_elementwise_fma(f2{ wyz, wyz }, v[1 + 2 * lo + 4 * hi] - v[2 * lo + 4 * hi], gx);
+        gy = __builtin_elementwise_fma(f2{ wxz, wxz }, v[lo + 2 + 4 * hi] - v[lo + 4 * hi], gy);
+        gz = __builtin_elementwise_fma(f2{ wxy[q], wxy[q] }, v[q + 4] - v[q], gz);
+    }
+    const float s = L.scale * dscale;
+    d0[0] = gx[0] * s; d0[1] = gy[0] * s; d0[2] = gz[0] * s;
+    d1[0] = gx[1] * s; d1[1] = gy[1] * s; d1[2] = gz[1] * s;
+}
+
 __device__ __forceinline__ void temporal_keyframe(float tq, int &k_lo, float &t_frac)
 {
     float ts = tq * 3.0f;

@@ -203,6 +203,14 @@ def nerfvis_eval_fn(field, t=0.0):
 
 # ---- meshes ----------------------------------------------------------------------------------------------------------
 MESH_MAX_RESO = 512                               # the dense density lattice is 4 * reso^3 bytes: 512 MiB
+MESH_NORMALS = ("lattice", "field")               # where a mesh's vertex normals come from
+
+
+def check_mesh_normals(normals) -> str:
+    """`normals` of the mesh extractors, or ValueError."""
+    if not isinstance(normals, str) or normals not in MESH_NORMALS:
+        raise ValueError(f"normals must be one of {MESH_NORMALS}, got {normals!r}")
+    return normals
 
 
 def _check_mesh_reso(reso):
@@ -210,7 +218,8 @@ def _check_mesh_reso(reso):
         raise ValueError(f"reso must be an int in 1 .. {MESH_MAX_RESO} for a mesh, got {reso!r}")
 
 
-def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max_rows: int, meta: Dict) -> Dict:
+def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max_rows: int, meta: Dict,
+          field_normals: bool = False) -> Dict:
     desc = field._descriptor()
     index, xyz = cand
     reso, dev = meta["reso"], xyz.device
@@ -226,6 +235,8 @@ def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max
     del lattice
     v = vertices.shape[0]
     res = field.query_density(vertices, torch.full((v, 1), t, device=dev, dtype=torch.float32), return_feat=True)
+    if field_normals:                                                            # the field's own slope at the vertices
+        normals = field.query_normals(vertices, torch.full((v,), t, device=dev, dtype=torch.float32))[0]
     out = dict(vertices=vertices, normals=normals, faces=faces, cube=cube, sigma=res["density"].reshape(v),
                embedding=res["base_mlp_out"])
     if isinstance(dirs, str):                                                    # "normal": head-on, one direction each
@@ -240,9 +251,10 @@ def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max
 @torch.no_grad()
 def extract_mesh_sequence(field, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None,
                           apply_act: bool = False, center=None, radius=None,
-                          max_cells_per_launch: int = 1 << 22) -> List[Dict]:
+                          max_cells_per_launch: int = 1 << 22, normals: str = "lattice") -> List[Dict]:
     """`extract_mesh` at every time of `times`: the candidate cells (the occupancy mask and the centres) are computed
     once and reused for every time."""
+    field_normals = check_mesh_normals(normals) == "field"
     _check_mesh_reso(reso)
     by_normal = isinstance(dirs, str)
     if by_normal and dirs != "normal":
@@ -255,15 +267,18 @@ def extract_mesh_sequence(field, times: Sequence, reso: int = 128, sigma_thresh:
         meta = dict(reso=int(reso), center=center, radius=radius, sigma_thresh=float(sigma_thresh),
                     apply_act=bool(apply_act))
         return [_mesh(field, cand, t, float(sigma_thresh), "normal" if by_normal else tensor_dirs, apply_act, max_cells,
-                      meta) for t in times]
+                      meta, field_normals) for t in times]
 
 
 def extract_mesh(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None, apply_act: bool = False,
-                 center=None, radius=None, max_cells_per_launch: int = 1 << 22) -> Dict:
+                 center=None, radius=None, max_cells_per_launch: int = 1 << 22, normals: str = "lattice") -> Dict:
     """The iso-surface density == sigma_thresh of `field` at time t as a triangle mesh: naive surface nets (the
     definition is in include/cednerf_hip.h) on the lattice of `voxel_centers`(reso, center, radius), reso <= 512, whose
     densities are query_density's bits (0 at the cells an `estimator` does not mark).  Returns
-        vertices [V,3], normals [V,3] (unit, towards lower density; zero where the density gradient vanishes),
+        vertices [V,3], normals [V,3] (unit, towards lower density; zero where the density gradient vanishes):
+        normals="lattice" (the default) central differences of the reso^3 lattice, normals="field" the field's analytic
+        gradient at the vertices, `DNGPradianceField.query_normals`(vertices, t)[0], which resolves what the hash grid's
+        fine levels hold; everything else is the same mesh; any other value raises ValueError,
         faces [F,3] int32 (counter-clockwise seen from outside), cube [V] int64 (the lattice cube of each vertex),
         sigma [V] and embedding [V,15] (query_density(vertices, t, return_feat=True)'s bits),
         rgb [V,D,3]: for dirs [D,3] _query_rgb on every pair; for dirs="normal" D = 1 and every vertex is viewed head-on,
@@ -272,7 +287,7 @@ def extract_mesh(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None
     The mesh is closed away from the lattice border and open on it; its vertex and face order do not depend on the run
     or on max_cells_per_launch."""
     return extract_mesh_sequence(field, [t], reso, sigma_thresh, dirs, estimator, apply_act, center, radius,
-                                 max_cells_per_launch)[0]
+                                 max_cells_per_launch, normals)[0]
 
 
 # ---- a mesh that moves -----------------------------------------------------------------------------------------------
@@ -289,7 +304,8 @@ def track_mesh(field, mesh: Dict, t_src, times: Sequence, max_iters: int = 32, t
         faces, cube, sigma, embedding, normals (and rgb if present): the reference mesh's own, valid at t_ref ONLY --
         faces are shared by all times; colours are not recomputed per time,
         reso, center, radius, sigma_thresh, apply_act,
-        normals=True (the mesh must have normals): normals_t [T,V,3], the reference normals carried along.  The surface
+        normals=True (the mesh must have normals): normals_t [T,V,3], the reference normals carried along, whichever the
+        mesh has (extract_mesh's normals="lattice" or "field").  The surface
         is a level set of the canonical density pulled back through the warp, whose gradient at (x, t) is
         (I + J_x(x, t))^T times the canonical gradient, so n_t is (I + J_t(x_t))^T (I + J_ref(x_ref))^-T n_ref, normalised,
         velocities=True: velocities_t [T,V,3] and det_t [T,V], `DNGPradianceField.query_velocity` at the tracked vertices.
@@ -333,13 +349,17 @@ def track_mesh(field, mesh: Dict, t_src, times: Sequence, max_iters: int = 32, t
 def extract_mesh_tracked(field, t_ref, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None,
                          estimator=None, apply_act: bool = False, center=None, radius=None,
                          max_cells_per_launch: int = 1 << 22, max_iters: int = 32, tol: float = 1e-6,
-                         method: str = "fixed_point", normals: bool = False, velocities: bool = False) -> Dict:
+                         method: str = "fixed_point", normals=False, velocities: bool = False) -> Dict:
     """`extract_mesh` at t_ref followed by `track_mesh` to `times`: one mesh with shared faces and per-time vertex
-    positions (see `track_mesh` for the result, `method`, `normals` and `velocities`)."""
+    positions (see `track_mesh` for the result, `method`, `normals` and `velocities`).  normals: False / True as
+    `track_mesh`'s, on the lattice normals; "lattice" or "field": the reference mesh takes those normals
+    (`extract_mesh`'s normals=) and they are carried along."""
     max_iters, tol = ops.check_solve(max_iters, tol)
     ops.check_method(method)
-    mesh = extract_mesh(field, t_ref, reso, sigma_thresh, dirs, estimator, apply_act, center, radius, max_cells_per_launch)
-    return track_mesh(field, mesh, t_ref, times, max_iters=max_iters, tol=tol, method=method, normals=normals,
+    kind = "lattice" if isinstance(normals, bool) else check_mesh_normals(normals)
+    mesh = extract_mesh(field, t_ref, reso, sigma_thresh, dirs, estimator, apply_act, center, radius, max_cells_per_launch,
+                        normals=kind)
+    return track_mesh(field, mesh, t_ref, times, max_iters=max_iters, tol=tol, method=method, normals=bool(normals),
                       velocities=velocities)
 
 
@@ -510,6 +530,9 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--mesh_dirs", type=parse_mesh_dirs, default="normal", metavar="normal|N",
                    help="view directions of the mesh colours: 'normal' (every vertex head-on) or N directions spread over "
                         "the sphere and averaged (0: no colour)")
+    p.add_argument("--mesh_normals", choices=MESH_NORMALS, default="lattice",
+                   help="vertex normals of the meshes: central differences of the density lattice, or the field's analytic "
+                        "gradient at the vertices")
     p.add_argument("--mesh_track", type=float, default=None, metavar="T_REF",
                    help="with --mesh: also write ONE mesh that moves -- the mesh of time T_REF, its vertices tracked to every "
                         "time of --times by inverting the warp: tracked_%%04d.ply per time and tracked.npz")
@@ -579,7 +602,7 @@ def main(argv=None) -> int:
         else:
             mesh_dirs = torch.from_numpy(fibonacci_dirs(a.mesh_dirs)).to(field.hash_table.device)
         meshes = extract_mesh_sequence(field, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh, dirs=mesh_dirs,
-                                       estimator=None if a.no_occupancy else estimator)
+                                       estimator=None if a.no_occupancy else estimator, normals=a.mesh_normals)
         for i, mesh in enumerate(meshes):
             stem = os.path.join(a.out, f"mesh_{i:04d}")
             save_mesh_npz(stem + ".npz", mesh)
@@ -587,10 +610,10 @@ def main(argv=None) -> int:
             print(f"t={mesh['t']:g}: {mesh['vertices'].shape[0]} vertices, {mesh['faces'].shape[0]} triangles -> "
                   f"{stem}.npz / .ply", flush=True)
         if a.mesh_track is not None:
-            tracked = extract_mesh_tracked(field, a.mesh_track, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh,
-                                           dirs=mesh_dirs, estimator=None if a.no_occupancy else estimator,
-                                           max_iters=a.track_iters, tol=a.track_tol, method=a.mesh_track_method,
-                                           normals=a.mesh_track_normals)
+            ref = extract_mesh(field, a.mesh_track, reso=a.reso, sigma_thresh=a.sigma_thresh, dirs=mesh_dirs,
+                               estimator=None if a.no_occupancy else estimator, normals=a.mesh_normals)
+            tracked = track_mesh(field, ref, a.mesh_track, a.times, max_iters=a.track_iters, tol=a.track_tol,
+                                 method=a.mesh_track_method, normals=a.mesh_track_normals)
             save_tracked_npz(os.path.join(a.out, "tracked.npz"), tracked)
             n_vertices = tracked["vertices_t"].shape[1]
             lost = (~tracked["converged"]).sum(dim=1).tolist()

@@ -255,6 +255,38 @@ class DNGPradianceField(torch.nn.Module):
         return -(inv @ jac[..., 3:]).squeeze(-1), det
 
     @torch.no_grad()
+    def query_density_gradient(self, x: torch.Tensor, t: torch.Tensor, canonical: bool = False):
+        """The density and its spatial gradient: (density [N,1], grad [N,3]) at (x, t), grad being what
+        torch.autograd.grad(density.sum(), x) returns on the reference's graph (cednerf/model.py:354-445) -- the time
+        encoding a constant, trunc_exp's clamped backward, the hash grid's slope inside the cell the encode selects, zero
+        outside the box -- by forward mode through the warp and mlp_base in this field's mlp_precision, from one launch
+        (ced_field_density_gradient; include/cednerf_hip.h states the operations).  `density` has `query_density`'s
+        bits.  canonical=True: the gradient with respect to the canonical point x + move(x, t) instead, i.e. without the
+        warp's (I + J_x)^T."""
+        density, grad = self._density_gradient(x, t, canonical, want_grad=True)
+        return density, grad
+
+    @torch.no_grad()
+    def query_normals(self, x: torch.Tensor, t: torch.Tensor, canonical: bool = False):
+        """(normals [N,3], density [N,1]): the unit vector towards lower density, -g / |g| with g the gradient of the
+        PRE-ACTIVATION density (`query_density_gradient`'s direction without sigma's twenty decades of range); 0 where g
+        is 0 or the point leaves the box.  canonical=True: in the canonical frame."""
+        density, dlog = self._density_gradient(x, t, canonical, want_grad=False)
+        return ops.unit_or_zero(-dlog), density
+
+    def _density_gradient(self, x, t, canonical, want_grad):
+        if not (x.is_cuda and t.is_cuda):
+            raise NotImplementedError("Only support cuda inputs: the density's gradient runs on the HIP kernel (no CPU fallback).")
+        sigma, grad, dlog, dlog_c = ops.field_density_gradient(
+            self._descriptor(), x.reshape(-1, 3).float().contiguous(), t.reshape(-1).float().contiguous(),
+            want=(True, want_grad and not canonical, not want_grad and not canonical, bool(canonical)))
+        if canonical:
+            out = sigma.clamp(max=ops.EXP15)[:, None] * dlog_c if want_grad else dlog_c
+        else:
+            out = grad if want_grad else dlog
+        return sigma[:, None], out
+
+    @torch.no_grad()
     def query_move_inverse(self, c: torch.Tensor, t: torch.Tensor, max_iters: int = 32, tol: float = 1e-6,
                            init: Optional[torch.Tensor] = None, method: str = "fixed_point"):
         """The inverse of the warp: per row the x with x + move(x, t) = c, `move` being `query_move`'s.  The density at
@@ -363,6 +395,15 @@ class DNGPradianceField(torch.nn.Module):
         return ops.field_move_rays(self._descriptor(), rays_o, rays_d, ray_indices, t_starts, t_ends, ts,
                                    bool(self.training), want_x_norm, n_dev=n_dev)
 
+
+    @torch.no_grad()
+    def query_density_gradient_rays(self, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps,
+                                    want=(True, True, True, True), n_dev: Optional[torch.Tensor] = None):
+        """`ops.field_density_gradient` at the samples `query_rays` evaluates (same positions, same per-ray / per-frame
+        timestamps): returns (sigma [S], grad [S,3], dlog [S,3], dlog_canonical [S,3]), None where want= is False."""
+        ts = timestamps.reshape(-1).float().contiguous()
+        return ops.field_density_gradient_rays(self._descriptor(), rays_o, rays_d, ray_indices, t_starts, t_ends, ts,
+                                               bool(self.training), want, n_dev=n_dev)
 
 def make_occ_eval_fn(radiance_field: "DNGPradianceField", timestamps: torch.Tensor, render_step_size: float):
     """The occ_eval_fn closure of train_real.py:324-328: a random training timestamp per point,

@@ -398,6 +398,71 @@ def field_move_jacobian(desc: _lib.FieldDesc, positions, t, want=(True, True)):
     return move, jac
 
 
+GRADIENT_OUTPUTS = ("sigma", "grad", "dlog", "dlog_canonical")   # ced_field_density_gradient's outputs, in `want=` order
+EXP15 = float(np.float32(np.exp(15.0)))                             # trunc_exp's backward clamps there (3269017.25)
+
+
+def _gradient_outputs(n, dev, want, who):
+    if len(want) != len(GRADIENT_OUTPUTS):
+        raise ValueError(f"{who}: want= takes one flag per output {GRADIENT_OUTPUTS}")
+    if not any(want):
+        raise ValueError(f"{who}: no output requested")
+    return [torch.empty((n,) if i == 0 else (n, 3), device=dev, dtype=torch.float32) if w else None
+            for i, w in enumerate(want)]
+
+
+def field_density_gradient(desc: _lib.FieldDesc, positions, t, want=(True, True, True, True)):
+    """ced_field_density_gradient: (sigma [n], grad [n,3], dlog [n,3], dlog_canonical [n,3]) at positions [n,3], t [n],
+    from one launch.  sigma has `field_forward`'s bits; dlog_canonical is the gradient of the pre-activation density with
+    respect to the canonical point x + move(x, t), dlog = (I + J_x)^T dlog_canonical with respect to x, grad =
+    min(sigma, e^15) * dlog; all zero outside the box (include/cednerf_hip.h states every operation).  want = which of
+    the four to compute; the others come back as None."""
+    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
+    n = positions.shape[0]
+    if positions.shape != (n, 3) or t.numel() != n:
+        raise ValueError(f"positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
+    outs = _gradient_outputs(n, positions.device, want, "field_density_gradient")
+    rc = _lib.lib().ced_field_density_gradient(C.byref(desc), n, _p(positions), _p(t), *[_p(o) for o in outs], _stream())
+    _lib.check(rc, "field_density_gradient")
+    return tuple(outs)
+
+
+def field_density_gradient_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps,
+                                t_per_ray: bool, want=(True, True, True, True), n_dev: Optional[torch.Tensor] = None,
+                                out=None):
+    """ced_field_density_gradient_rays: `field_density_gradient` at the sample positions of `field_forward_rays`.  n_dev
+    as there; out = the four buffers (or None each) to write into instead of fresh ones, which then decides what is
+    computed."""
+    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
+    _chk(ray_indices, torch.int64, "ray_indices")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
+    _chk(timestamps, torch.float32, "timestamps")
+    n = ray_indices.shape[0]
+    assert t_starts.shape == (n,) and t_ends.shape == (n,)
+    if t_per_ray:
+        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
+    if out is not None:
+        outs = list(out)
+        if len(outs) != len(GRADIENT_OUTPUTS) or all(o is None for o in outs):
+            raise ValueError("field_density_gradient_rays: no output requested")
+        for i, o in enumerate(outs):
+            _chk(o, torch.float32, f"out[{i}]", allow_none=True)
+            assert o is None or o.shape == ((n,) if i == 0 else (n, 3)), (i, o.shape)
+    else:
+        outs = _gradient_outputs(n, rays_o.device, want, "field_density_gradient_rays")
+    rc = _lib.lib().ced_field_density_gradient_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices),
+                                                    _p(t_starts), _p(t_ends), _p(timestamps), int(bool(t_per_ray)),
+                                                    *[_p(o) for o in outs], _stream())
+    _lib.check(rc, "field_density_gradient_rays")
+    return tuple(outs)
+
+
+def unit_or_zero(v: torch.Tensor) -> torch.Tensor:
+    """v / |v| along the last axis, 0 where v is 0 (a normal where the field has a slope, none where it has not)."""
+    length = v.norm(dim=-1, keepdim=True)
+    return torch.where(length > 0, v / length, torch.zeros_like(v))
+
+
 def field_move_inverse_newton(desc: _lib.FieldDesc, target, t, init=None, max_iters: int = 32, tol: float = 1e-6):
     """ced_field_move_inverse_newton: `field_move_inverse`'s arguments and outputs, solved by Newton's method on
     `field_move_jacobian` (include/cednerf_hip.h states the iteration).  `step` is the max-norm residual

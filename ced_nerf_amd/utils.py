@@ -195,6 +195,57 @@ def render_image(
             depths.view((*rays_shape[:-1], -1)), sum(n_rendering_samples), extra_info)
 
 
+def _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle, alpha_thre,
+                          test_chunk_size, timestamps, return_samples, who, key, values_fn):
+    """What `render_motion` and `render_normals` share: a per-sample [S,3] quantity composited with the volume-rendering
+    weights on exactly the samples `render_image` takes in eval mode.  values_fn(o, d, ray_indices, t_starts, t_ends, ts)
+    -> [S,3]; `key` names it in the per-chunk sample dicts."""
+    if timestamps is None:
+        raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:78-86)")
+    if radiance_field.training:
+        raise NotImplementedError(f"{who} renders eval frames (one time per frame)")
+    rays, rays_shape, num_rays = _flatten_rays(rays)
+    ts = timestamps
+    pass_rays = max(test_chunk_size, (_EVAL_PASS_RAYS // test_chunk_size) * test_chunk_size)
+    images, opacities, samples, n_samples = [], [], [], 0
+    for i in range(0, num_rays, pass_rays):
+        chunk_rays = namedtuple_map(lambda r: r[i:i + pass_rays].contiguous().float(), rays)
+        o, d = chunk_rays.origins, chunk_rays.viewdirs
+        n_pass = o.shape[0]
+
+        def sigma_fn(t_starts, t_ends, ray_indices):
+            return radiance_field.query_rays(o, d, ray_indices, t_starts, t_ends, ts, want_rgb=False)[1]
+
+        ray_indices, t_starts, t_ends = estimator.sampling(
+            o, d, sigma_fn=sigma_fn, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size,
+            stratified=False, cone_angle=cone_angle, alpha_thre=alpha_thre, sigma_field=(radiance_field, ts, False))
+        values = values_fn(o, d, ray_indices, t_starts, t_ends, ts)
+        sigmas = sigma_fn(t_starts, t_ends, ray_indices)
+        packed = _packed_info_from(ray_indices, n_pass)
+        weights, _, _ = render_weight_from_density(t_starts, t_ends, sigmas, packed_info=packed)
+        images.append(accumulate_along_rays(weights, values=values, packed_info=packed))
+        opacities.append(accumulate_along_rays(weights, values=None, packed_info=packed))
+        n_samples += int(t_starts.shape[0])
+        if not return_samples:
+            continue
+        extras = {"ray_indices": ray_indices, "t_starts": t_starts, "t_ends": t_ends, "weights": weights, key: values}
+        if n_pass <= test_chunk_size:
+            samples.append(extras)
+            continue
+        # the reference's chunks, as render_image cuts them: samples are sorted by ray
+        starts = list(range(0, n_pass, test_chunk_size)) + [n_pass]
+        bounds = packed[:, 0][torch.tensor(starts[:-1], device=o.device)].tolist() + [int(t_starts.shape[0])]
+        sizes = [bounds[c + 1] - bounds[c] for c in range(len(starts) - 1)]
+        extras["ray_indices"] = ray_indices % test_chunk_size
+        cut = {k: v.split(sizes) for k, v in extras.items()}
+        samples.extend([{k: cut[k][c] for k in cut} for c in range(len(sizes))])
+    image = torch.cat(images, dim=0).view((*rays_shape[:-1], 3))
+    opacity = torch.cat(opacities, dim=0).view((*rays_shape[:-1], 1))
+    if return_samples:
+        return image, opacity, n_samples, samples
+    return image, opacity, n_samples
+
+
 @torch.no_grad()
 def render_motion(
     radiance_field: torch.nn.Module,
@@ -217,50 +268,41 @@ def render_motion(
     `render_image`'s.  Rays that meet no sample have motion = 0 and opacity = 0.  With return_samples=True a fourth
     value is the list of per-chunk dicts `ray_indices` (relative to the chunk when the frame has several), `t_starts`,
     `t_ends`, `weights`, `move`.  rays: [H,W,3] or flat [N,3], as `render_image`."""
-    if timestamps is None:
-        raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:78-86)")
-    if radiance_field.training:
-        raise NotImplementedError("render_motion renders eval frames (one time per frame)")
-    rays, rays_shape, num_rays = _flatten_rays(rays)
-    ts = timestamps
-    pass_rays = max(test_chunk_size, (_EVAL_PASS_RAYS // test_chunk_size) * test_chunk_size)
-    motions, opacities, samples, n_samples = [], [], [], 0
-    for i in range(0, num_rays, pass_rays):
-        chunk_rays = namedtuple_map(lambda r: r[i:i + pass_rays].contiguous().float(), rays)
-        o, d = chunk_rays.origins, chunk_rays.viewdirs
-        n_pass = o.shape[0]
+    def move_fn(o, d, ray_indices, t_starts, t_ends, ts):
+        return radiance_field.query_move_rays(o, d, ray_indices, t_starts, t_ends, ts)[0]
 
-        def sigma_fn(t_starts, t_ends, ray_indices):
-            return radiance_field.query_rays(o, d, ray_indices, t_starts, t_ends, ts, want_rgb=False)[1]
+    return _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle,
+                                 alpha_thre, test_chunk_size, timestamps, return_samples, "render_motion", "move", move_fn)
 
-        ray_indices, t_starts, t_ends = estimator.sampling(
-            o, d, sigma_fn=sigma_fn, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size,
-            stratified=False, cone_angle=cone_angle, alpha_thre=alpha_thre, sigma_field=(radiance_field, ts, False))
-        move, _ = radiance_field.query_move_rays(o, d, ray_indices, t_starts, t_ends, ts)
-        sigmas = sigma_fn(t_starts, t_ends, ray_indices)
-        packed = _packed_info_from(ray_indices, n_pass)
-        weights, _, _ = render_weight_from_density(t_starts, t_ends, sigmas, packed_info=packed)
-        motions.append(accumulate_along_rays(weights, values=move, packed_info=packed))
-        opacities.append(accumulate_along_rays(weights, values=None, packed_info=packed))
-        n_samples += int(t_starts.shape[0])
-        if not return_samples:
-            continue
-        extras = {"ray_indices": ray_indices, "t_starts": t_starts, "t_ends": t_ends, "weights": weights, "move": move}
-        if n_pass <= test_chunk_size:
-            samples.append(extras)
-            continue
-        # the reference's chunks, as render_image cuts them: samples are sorted by ray
-        starts = list(range(0, n_pass, test_chunk_size)) + [n_pass]
-        bounds = packed[:, 0][torch.tensor(starts[:-1], device=o.device)].tolist() + [int(t_starts.shape[0])]
-        sizes = [bounds[c + 1] - bounds[c] for c in range(len(starts) - 1)]
-        extras["ray_indices"] = ray_indices % test_chunk_size
-        cut = {k: v.split(sizes) for k, v in extras.items()}
-        samples.extend([{k: cut[k][c] for k in cut} for c in range(len(sizes))])
-    motion = torch.cat(motions, dim=0).view((*rays_shape[:-1], 3))
-    opacity = torch.cat(opacities, dim=0).view((*rays_shape[:-1], 1))
-    if return_samples:
-        return motion, opacity, n_samples, samples
-    return motion, opacity, n_samples
+
+@torch.no_grad()
+def render_normals(
+    radiance_field: torch.nn.Module,
+    estimator: OccGridEstimator,
+    rays: Rays,
+    near_plane: float = 0.0,
+    far_plane: float = 1e10,
+    render_step_size: float = 1e-3,
+    cone_angle: float = 0.0,
+    alpha_thre: float = 0.0,
+    test_chunk_size: int = 8192,
+    timestamps: Optional[torch.Tensor] = None,
+    return_samples: bool = False,
+):
+    """Per-pixel normal map: the field's normals at the samples (`query_normals`: the unit vector towards lower density
+    from the density's analytic gradient with respect to the observed point, 0 outside the box) composited with the
+    volume-rendering weights, on exactly `render_motion`'s samples for the same arguments.
+    Returns (normals [H,W,3], opacity [H,W,1], n_samples): normals = sum_i w_i * n_i along each ray, NOT normalised -- its
+    length is at most the opacity, and the surface normal is normals / |normals| where that is > 0.  Rays that meet no
+    sample have normals = 0 and opacity = 0.  With return_samples=True a fourth value is the list of per-chunk dicts, as
+    `render_motion`'s with `normal` in place of `move`."""
+    def normal_fn(o, d, ray_indices, t_starts, t_ends, ts):
+        dlog = radiance_field.query_density_gradient_rays(o, d, ray_indices, t_starts, t_ends, ts,
+                                                          want=(False, False, True, False))[2]
+        return ops.unit_or_zero(-dlog)
+
+    return _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle,
+                                 alpha_thre, test_chunk_size, timestamps, return_samples, "render_normals", "normal", normal_fn)
 
 
 @torch.no_grad()

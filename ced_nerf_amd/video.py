@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .dist import PipelinedRenderer, ShardedRenderer
-from .utils import Rays, render_motion
+from .utils import Rays, render_motion, render_normals
 
 
 def frame_to_uint8(rgb: torch.Tensor, depth: torch.Tensor, flip_w: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -30,7 +30,7 @@ def frame_to_uint8(rgb: torch.Tensor, depth: torch.Tensor, flip_w: bool = True) 
 def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays], timestamps_of_frame: Callable[[int], torch.Tensor],
                  n_frames: int, max_samples: int = 1024, render_kwargs: Optional[Dict] = None, frames_in_flight: int = 3,
                  flip_w: bool = True, to_host: bool = False, keep_float: bool = False, frames_per_call: int = 1,
-                 motion: bool = False) -> List[Dict]:
+                 motion: bool = False, normals: bool = False) -> List[Dict]:
     """Render frames 0..n_frames-1 of a path.
 
     rays_of_frame(i) -> Rays with [H,W,3] device tensors (e.g. `cameras.pinhole_rays(K, c2w_i, W, H)`; it is called on
@@ -43,7 +43,8 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
     per call on its first frame's entry and the others carry None.
     motion=True: every frame's dict also carries `motion_f32` [H,W,3], the deformation field's motion map
     (`utils.render_motion`) rendered after the frame on the frame's rays and time with the march options of
-    render_kwargs; the frames themselves are rendered exactly as without it."""
+    render_kwargs; the frames themselves are rendered exactly as without it.
+    normals=True: likewise `normals_f32` [H,W,3], the frame's normal map (`utils.render_normals`)."""
     if n_frames <= 0:
         return []
     device = radiance_field.aabb.device if hasattr(radiance_field, "aabb") else torch.device("cuda")
@@ -79,10 +80,11 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
                 if keep_float:
                     f.update(rgb_f32=rgb, opacity_f32=out["opacity"][k], depth_f32=depth)
                 frames.append(f)
-    if motion:
-        kw = {k: v for k, v in (render_kwargs or {}).items()
-              if k in ("near_plane", "far_plane", "render_step_size", "cone_angle", "alpha_thre")}
+    kw = {k: v for k, v in (render_kwargs or {}).items()
+          if k in ("near_plane", "far_plane", "render_step_size", "cone_angle", "alpha_thre")}
+    for key, on, render in (("motion_f32", motion, render_motion), ("normals_f32", normals, render_normals)):
+        if not on:
+            continue
         for i, f in enumerate(frames):
-            f["motion_f32"] = render_motion(radiance_field, estimator, rays_of_frame(i), timestamps=timestamps_of_frame(i),
-                                            **kw)[0]
+            f[key] = render(radiance_field, estimator, rays_of_frame(i), timestamps=timestamps_of_frame(i), **kw)[0]
     return frames

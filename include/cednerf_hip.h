@@ -359,6 +359,49 @@ int ced_field_track_newton(const ced_field_desc *desc, int64_t n_points, int64_t
                            const float *times, const float *init, int32_t max_iters, float tol, float *x,
                            float *step, int32_t *evals, void *stream);
 
+/* ---- the derivative of the density ----
+ * sigma [n] and three gradients [n,3] per row (x, t), all in world units, from one launch; each output may be NULL, not
+ * all.  sigma is ced_field_forward's, bit for bit, in desc->mlp_precision.  `grad` is what torch.autograd.grad(
+ * density.sum(), x) returns on the reference's graph (cednerf/model.py:354-445), under four rules:
+ *   time encoding  a constant (model.py:386-396 runs it under no_grad), its attenuation by |move| included;
+ *   activation     trunc_exp's backward (cednerf/utils.py:27-43), exp(min(raw - 1, 15)): slope = fminf(s, kExp15) with s the
+ *                  forward's exp(raw - 1), its own bits, and kExp15 = 3269017.25f, the float32 nearest e^15;
+ *   hash grid      piecewise trilinear: inside the cell the encode's own fp32 floor selects, d frac / d x_norm = scale_l
+ *                  exactly; the temporal table's derivative is the same formula on the time-interpolated corner values;
+ *   outside        where the selector is false, sigma and every gradient output are 0.
+ * Forward mode: three tangent vectors per row (the axes of x_norm) through mlp_base beside the primal, as three more
+ * matrix-instruction columns on the same weights:
+ *   encoding   with v[c] corner c's two values (temporal table: v_k * (1 - t_frac) + v_(k+1) * t_frac, as the encode forms
+ *              them), frac / 1 - frac the encode's own fp32 fractions and K = ceil(log2(the largest level scale)):
+ *                  g_a = sum over the four corner pairs along axis a, ascending, of
+ *                        fma(w, v[upper] - v[lower], g_a),  w = the product of the other two axes' weights
+ *                  d feature / d x_norm[a] = g_a * (scale_l * 2^-K)
+ *              The tangents are carried scaled by the exact 2^-K so that they stay inside the fp16 range; f16 / f16x2:
+ *              clamped to +-65504, then rounded to fp16 / split into hi + lo like the primal features.  The tangents of
+ *              the nine time features are 0.
+ *   layers     mlp_base's two layers multiply the tangents in the mode's own layer arithmetic, exactly as the primal.
+ *   ReLU       the hidden tangent is set to 0 wherever the PRIMAL pre-activation is not > 0; f16 / f16x2: then clamped
+ *              to +-65504 and rounded / split like the primal activation.
+ * Then, with d[a] the raw density's three tangents, extent[a] = aabb[3 + a] - aabb[a] and J = ced_field_move_jacobian's
+ * jac of the row (its bits), every line in fp32, every product, sum and quotient rounded on its own (no fused
+ * multiply-add):
+ *     dlog_canonical[a] = (d[a] * 2^K) / extent[a]
+ *     dlog[b] = dlog_canonical[b] + ((J[0][b] * dlog_canonical[0] + J[1][b] * dlog_canonical[1]) + J[2][b] * dlog_canonical[2])
+ *     grad[b] = slope * dlog[b]
+ * dlog_canonical is the gradient of the pre-activation density with respect to the canonical point c = x + move(x, t)
+ * (the gradient of log sigma below the clamp), dlog = (I + J_x)^T dlog_canonical the same with respect to the observed
+ * point x.  A row's outputs do not depend on n or on the other rows. */
+int ced_field_density_gradient(const ced_field_desc *desc, int64_t n, const float *positions, const float *t,
+                               float *sigma, float *grad, float *dlog, float *dlog_canonical, void *stream);
+
+/* The same at the sample positions of the sigma_fn / rgb_sigma_fn closures: positions, timestamps, t_per_ray and n_dev
+ * as in ced_field_move_rays (rows past min(n, *n_dev) are left untouched). */
+int ced_field_density_gradient_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_dev,
+                                    const float *rays_o, const float *rays_d,
+                                    const int64_t *ray_indices, const float *t_starts, const float *t_ends,
+                                    const float *timestamps, int32_t t_per_ray, float *sigma, float *grad, float *dlog,
+                                    float *dlog_canonical, void *stream);
+
 /* DNGPradianceField._query_rgb(dir, embedding, apply_act) -- cednerf/model.py:447-466: dirs [n,3] are normalised,
  * mapped to [0,1], SH degree 2; mlp_head on [SH(4), embedding(15)]; the sigmoid iff apply_act.  embedding [n,15] is what
  * ced_field_forward writes to `geo`; rgb [n,3].  The head runs in the arithmetic of desc->mlp_precision. */
