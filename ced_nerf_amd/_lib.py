@@ -111,6 +111,8 @@ PROTOTYPES = {
     "ced_field_density_gradient": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ced_field_density_gradient_rays": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                                   _vp, _vp, _vp]),
+    "ced_field_velocity": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ced_field_velocity_rays": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ced_field_move_inverse_newton": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _i32, _f, _vp, _vp, _vp, _vp]),
     "ced_field_track_newton": (C.c_int, [C.POINTER(FieldDesc), _i64, _i64, _vp, _vp, _vp, _i32, _f, _vp, _vp, _vp, _vp]),
     "ced_field_rgb": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _i32, _vp, _vp]),
@@ -136,6 +138,7 @@ PROTOTYPES = {
                            C.c_double, _i32, C.POINTER(C.c_float), _i32, C.POINTER(C.c_float), _i32, _vp, _vp, _vp, _vp,
                            _vp, _vp]),
     "ced_frame_to_rgb8": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp]),
+    "ced_flow_to_rgb8": (C.c_int, [_i32, _i32, _vp, _f, _i32, _vp, _vp]),
     "ced_depth_to_u8": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ced_scatter_pixels": (C.c_int, [_i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "ced_linear": (C.c_int, [_i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -65,3 +65,42 @@ def hypercam_rays(orientation, position, focal_length: float, principal_point: S
                                                    _stream())
     _lib.check(rc, "generate_rays_hypercam")
     return Rays(origins=o, viewdirs=d)
+
+
+def pinhole_projector(K, c2w, opengl: bool = True, device="cuda"):
+    """The inverse of `pinhole_rays`: returns project(points [S,3]) -> (pixels [S,2], in_front [S] bool) for the camera
+    K [3,3], c2w [3,4] (or [4,4]).  Pixel units are continuous with the centre of pixel (x, y) AT (x, y): the point
+    o + s * d of `pinhole_rays`' ray through pixel (x, y), s > 0, projects to (x, y).  With p_cam = R^-1 (p - o), R and o
+    the rotation and translation of c2w:
+        opengl=True   the camera looks down -z with y up (`pinhole_rays`' camera direction ((x - cx + 0.5) / fx,
+                      -(y - cy + 0.5) / fy, -1)):  x = -fx * p_cam.x / p_cam.z + cx - 0.5,  y = fy * p_cam.y / p_cam.z + cy - 0.5,
+                      in_front = p_cam.z < 0;
+        opengl=False  OpenCV: down +z with y down (direction ((x - cx + 0.5) / fx, (y - cy + 0.5) / fy, 1)):
+                      x = fx * p_cam.x / p_cam.z + cx - 0.5,  y = fy * p_cam.y / p_cam.z + cy - 0.5,  in_front = p_cam.z > 0.
+    A point that is not in front still gets the formula's pixel (possibly infinite or NaN); mask with in_front.  Plain
+    torch in the points' own device and dtype (the camera is held in float64 and cast), so it runs on CPU tensors too;
+    `device` is where the camera's tensors are created first."""
+    K = np.asarray(K, np.float64)
+    c2w = np.asarray(c2w, np.float64)[:3, :4]
+    sign = -1.0 if opengl else 1.0
+    cam = {}
+
+    def held(like):
+        key = (like.device, like.dtype)
+        if key not in cam:
+            cam[key] = (torch.as_tensor(np.linalg.inv(c2w[:, :3]), dtype=like.dtype, device=like.device),
+                        torch.as_tensor(c2w[:, 3].copy(), dtype=like.dtype, device=like.device))
+        return cam[key]
+
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    if torch.device(device).type == "cuda" and torch.cuda.is_available():
+        held(torch.empty(0, dtype=torch.float32, device=device))
+
+    def project(points: torch.Tensor):
+        w2c, origin = held(points)
+        pc = ((points - origin)[:, None, :] * w2c[None, :, :]).sum(-1)  # rows p_cam = R^-1 (p - o), without a BLAS call
+        z = pc[:, 2]
+        pixels = torch.stack([(sign * fx) * (pc[:, 0] / z) + (cx - 0.5), fy * (pc[:, 1] / z) + (cy - 0.5)], dim=-1)
+        return pixels, (z * sign) > 0
+
+    return project

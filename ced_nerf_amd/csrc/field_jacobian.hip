@@ -1,6 +1,8 @@
 // The derivative of the motion network: ced_field_move_jacobian hands out move(x, t) and its 3 x 4 Jacobian with respect
 // to (x, y, z, t) from one launch, and ced_field_move_inverse_newton / ced_field_track_newton solve x + move(x, t) = c by
 // Newton's method on that Jacobian, the iterate held in registers (include/cednerf_hip.h states every operation).
+// ced_field_velocity / ced_field_velocity_rays turn the same Jacobian into the velocity of the material point that sits at
+// x, v = -(I + J_x)^-1 d move / dt, inside the launch: 17 bytes per row leave instead of the Jacobian's 60.
 //
 // Forward mode: the Jacobian of a sample is four tangent vectors pushed through the four layers beside the primal.  A
 // tangent is one more MFMA column, so the tangents of a 16-sample primal tile are four 16-column operand tiles that go
@@ -11,7 +13,7 @@
 // tangent is zeroed wherever the PRIMAL pre-activation is not > 0, and the output applies the tanh's derivative
 // 1 - th^2 to the fine offsets.
 //
-// Shape: field_move.hip's (tile_kernel of field_move_device.hpp with the ops JacobianOp and NewtonOp: persistent workgroups
+// Shape: field_move.hip's (tile_kernel of field_move_device.hpp with the ops JacobianOp, NewtonOp and VelocityOp: persistent workgroups
 // of 512 threads, the motion network's layers staged into LDS once), with ONE 16-sample primal tile per wave iteration
 // instead of two: primal + four tangents are five operand tiles and five
 // accumulator tiles (80 + 80 registers on the fp32 chain), which fit the 256 registers of a wave at two waves per SIMD
@@ -67,6 +69,35 @@ struct JacobianOp : TileOp {
     }
 };
 
+// ---- the 3 x 3 solve both the Newton step and the velocity take (include/cednerf_hip.h states it) ------------------------
+// A = I + J_x, its cofactors Cf (adj = Cf^T), det by the first row, d = adj r / det; every fp32 operation rounded on its own.
+__device__ __forceinline__ void adjugate_solve(const float (&J)[12], const float (&r)[3], float &det, float (&d)[3])
+{
+    float Am[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) Am[a][b] = (a == b) ? __fadd_rn(1.0f, J[4 * a + b]) : J[4 * a + b];
+    }
+    float Cf[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, b1 = (b + 1) % 3, b2 = (b + 2) % 3;
+            Cf[a][b] = __fsub_rn(__fmul_rn(Am[a1][b1], Am[a2][b2]), __fmul_rn(Am[a1][b2], Am[a2][b1]));
+        }
+    }
+    det = __fadd_rn(__fadd_rn(__fmul_rn(Am[0][0], Cf[0][0]), __fmul_rn(Am[0][1], Cf[0][1])), __fmul_rn(Am[0][2], Cf[0][2]));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float num = __fadd_rn(__fadd_rn(__fmul_rn(Cf[0][a], r[0]), __fmul_rn(Cf[1][a], r[1])), __fmul_rn(Cf[2][a], r[2]));
+        d[a] = __fdiv_rn(num, det);
+    }
+}
+
+constexpr float kDetFloor = 9.5367431640625e-07f;     // 2^-20: below it (in magnitude) neither op divides by the determinant
+
 // ---- the warp's inverse by Newton's method (include/cednerf_hip.h states it) ----------------------------------------------
 // The rows, their load and their store are the fixed-point kernels' (TrackRows: target, time and iterate of a wave tile
 // in registers, every lane group the same copy of column c's rows); `step` holds the residual.  One round on the rows
@@ -90,31 +121,11 @@ __device__ __forceinline__ bool newton_update(const float (&mv)[NT][3], const fl
         R.active[j] = on && !(res <= tol);                               // a NaN residual stays active
         any = any || R.active[j];
 
-        float Am[3][3];
+        float det, d[3];
+        adjugate_solve(J[j], r, det, d);
+        bool fine = __builtin_fabsf(det) >= kDetFloor;                   // false for a NaN
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) Am[a][b] = (a == b) ? __fadd_rn(1.0f, J[j][4 * a + b]) : J[j][4 * a + b];
-        }
-        // cofactors C[a][b] of A; adj = C^T
-        float Cf[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const int a1 = (a + 1) % 3, a2 = (a + 2) % 3, b1 = (b + 1) % 3, b2 = (b + 2) % 3;
-                Cf[a][b] = __fsub_rn(__fmul_rn(Am[a1][b1], Am[a2][b2]), __fmul_rn(Am[a1][b2], Am[a2][b1]));
-            }
-        }
-        const float det = __fadd_rn(__fadd_rn(__fmul_rn(Am[0][0], Cf[0][0]), __fmul_rn(Am[0][1], Cf[0][1])), __fmul_rn(Am[0][2], Cf[0][2]));
-        float d[3];
-        bool fine = __builtin_fabsf(det) >= 9.5367431640625e-07f;        // 2^-20; false for a NaN
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float num = __fadd_rn(__fadd_rn(__fmul_rn(Cf[0][a], r[0]), __fmul_rn(Cf[1][a], r[1])), __fmul_rn(Cf[2][a], r[2]));
-            d[a] = __fdiv_rn(num, det);
-            fine = fine && __builtin_fabsf(d[a]) < __builtin_inff();     // finite: false for an infinity and for a NaN
-        }
+        for (int a = 0; a < 3; ++a) fine = fine && __builtin_fabsf(d[a]) < __builtin_inff();   // finite: false for an infinity and for a NaN
         const bool go = R.active[j] && !last;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -141,6 +152,65 @@ struct NewtonOp : TileOp {
             if (__ballot(newton_update<NT>(mv, J, A.tol, it + 1 == A.max_iters, R)) == 0) break;   // wave-uniform
         }
         track_store<NT>(A, R, tile_base, g, c);
+    }
+};
+
+// ---- ced_field_velocity, ced_field_velocity_rays: v = -(I + J_x)^-1 d move / dt (include/cednerf_hip.h states it) ----------
+struct VelArgs {
+    int64_t n;
+    const int64_t *n_dev;                             // optional device-side sample count (<= n)
+    const float *pos, *t;                             // explicit mode
+    const float *rays_o, *rays_d;                     // rays mode: load_samples' fields
+    const int64_t *ray_idx;
+    const float *t0, *t1, *timestamps;
+    int rays_mode, t_per_ray;
+    float *velocity, *det;                            // [n,3], [n]; any may be null
+    uint8_t *valid;                                   // [n], may be null
+    float moving_step;
+    int use_div;
+    const void *weights;
+    int64_t lo_halves;
+};
+
+// The solve with r = the Jacobian's time column.  valid: the determinant at least 2^-20 -- a fold (det <= 0) and a NaN are
+// not -- and a finite quotient; a row that is not valid has velocity 0, so that it composites to nothing.  Lane group
+// a < 3 stores component a, lane group 3 det and valid.
+template <int NP>
+__device__ __forceinline__ void velocity_store(const VelArgs &A, const float (&J)[NP][12], int64_t tile_base, int64_t n_eff, int g, int c)
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const float r[3] = { J[j][3], J[j][7], J[j][11] };
+        float det, d[3];
+        adjugate_solve(J[j], r, det, d);
+        bool valid = det >= kDetFloor;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) valid = valid && __builtin_fabsf(d[a]) < __builtin_inff();
+        const float v0 = valid ? -d[0] : 0.0f, v1 = valid ? -d[1] : 0.0f, v2 = valid ? -d[2] : 0.0f;
+        const float o = (g == 0) ? v0 : (g == 1) ? v1 : v2;
+        const int64_t s = tile_base + 16 * j + c;
+        if (s >= n_eff) continue;
+        if (g == 3) {
+            if (A.det) A.det[s] = det;
+            if (A.valid) A.valid[s] = valid ? 1 : 0;
+            continue;
+        }
+        if (A.velocity) A.velocity[3 * s + g] = o;
+    }
+}
+
+struct VelocityOp : TileOp {
+    using Args = VelArgs;
+    __device__ __forceinline__ static int64_t rows(const VelArgs &A) { return sample_count(A.n, A.n_dev); }
+    template <typename W, int NP>
+    __device__ __forceinline__ static void tile(const VelArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base,
+                                                int64_t n_eff, int lane)
+    {
+        const int g = lane >> 4, c = lane & 15;
+        float px[NP][3], tq[NP], mv[NP][3], J[NP][12];
+        load_samples<NP>(A, tile_base, n_eff, c, px, tq);
+        motion_move_jacobian<W, NP>(w, lane, px, RowTime<NP>{ tq }, A.moving_step, A.use_div, mv, J);
+        velocity_store<NP>(A, J, tile_base, n_eff, g, c);
     }
 };
 
@@ -176,4 +246,41 @@ extern "C" int ced_field_track_newton(const ced_field_desc *desc, int64_t n_poin
 {
     return ced::solve_track(desc, n_points, n_times, target, times, init, max_iters, tol, x, step, evals, "field_track_newton",
                             ced::launch_motion<ced::NewtonOp, 1>, stream);
+}
+
+extern "C" int ced_field_velocity(const ced_field_desc *desc, int64_t n, const float *positions, const float *t, float *velocity,
+                                  float *det, uint8_t *valid, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_velocity");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_velocity: n < 0");
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(positions && t, "field_velocity: null positions/t");
+    CED_REQUIRE(velocity || det || valid, "field_velocity: no output requested");
+    ced::VelArgs A{};
+    A.n = n;
+    A.pos = positions; A.t = t;
+    A.velocity = velocity; A.det = det; A.valid = valid;
+    return ced::launch_motion<ced::VelocityOp, 1>(desc, A, "field_velocity", stream);
+}
+
+extern "C" int ced_field_velocity_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_dev, const float *rays_o,
+                                       const float *rays_d, const int64_t *ray_indices, const float *t_starts,
+                                       const float *t_ends, const float *timestamps, int32_t t_per_ray, float *velocity,
+                                       float *det, uint8_t *valid, void *stream)
+{
+    int rc = ced::validate_desc(desc, "field_velocity_rays");
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "field_velocity_rays: n < 0");
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && timestamps, "field_velocity_rays: null pointer");
+    CED_REQUIRE(velocity || det || valid, "field_velocity_rays: no output requested");
+    ced::VelArgs A{};
+    A.n = n;
+    A.n_dev = n_dev;
+    A.rays_o = rays_o; A.rays_d = rays_d; A.ray_idx = ray_indices;
+    A.t0 = t_starts; A.t1 = t_ends; A.timestamps = timestamps;
+    A.rays_mode = 1; A.t_per_ray = t_per_ray ? 1 : 0;
+    A.velocity = velocity; A.det = det; A.valid = valid;
+    return ced::launch_motion<ced::VelocityOp, 1>(desc, A, "field_velocity_rays", stream);
 }

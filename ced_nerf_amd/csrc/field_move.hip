@@ -62,35 +62,6 @@ static_assert(HalfBlob<false>::FRAGS - HalfBlob<false>::H0 == Blob<false>::HEAD_
               HalfBlob<false>::H2 - HalfBlob<false>::H0 == Blob<false>::HF_H2,
               "the head's fragments are laid out alike in the half blobs and in the mixed blob");
 
-__device__ __forceinline__ int64_t sample_count(int64_t n, const int64_t *n_dev)
-{
-    if (!n_dev) return n;
-    const int64_t nd = *n_dev;
-    return nd < n ? nd : n;
-}
-
-// Position and time of sample c of each 16-sample column tile: the expressions of field_kernel.hpp / field_half.hip
-// (rays mode: o + (d * (t0 + t1)) / 2 in fp32; a negative ray index is evaluated on ray 0 at distance 0).  A ragged last
-// tile repeats the last sample (never stored).
-template <int NT>
-__device__ __forceinline__ void load_samples(const MoveArgs &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[NT][3],
-                                             float (&tq)[NT])
-{
-    if (!A.rays_mode) return load_points<NT>(A.pos, A.t, n_eff, tile_base, c, px, tq);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        int64_t s = tile_base + 16 * j + c;
-        s = s < n_eff ? s : n_eff - 1;
-        const int64_t r_in = A.ray_idx[s];
-        const bool used = r_in >= 0;
-        const int64_t r = used ? r_in : 0;
-        const float tm2 = used ? A.t0[s] + A.t1[s] : 0.0f;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) px[j][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
-        tq[j] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
-    }
-}
-
 // x_move / normalise / selector (model.py:378-383) from `move` -- except that x_norm leaves unclamped, as the reference
 // returns it.  Lane group a < 3 stores component a, lane group 3 the selector.
 template <int NT>

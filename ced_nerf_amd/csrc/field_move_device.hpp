@@ -1,6 +1,6 @@
 // Device code of the motion network and of the colour head on their own, shared by field_move.hip (ced_field_move,
-// ced_field_move_inverse, ced_field_track, ced_field_rgb) and field_jacobian.hip (ced_field_move_jacobian and the Newton
-// inverse).
+// ced_field_move_inverse, ced_field_track, ced_field_rgb) and field_jacobian.hip (ced_field_move_jacobian, the Newton
+// inverse and ced_field_velocity, whose rays entry reads its samples through the loader of ced_field_move_rays below).
 //
 // Every kernel of the two files is tile_kernel<Op, W, NT, THREADS>.  The skeleton fixes, once: the wave's tiles of
 // 16 * NT rows (wave w of workgroup b takes tiles b * WAVES + w, + gridDim.x * WAVES, ...), the workgroup-uniform early
@@ -117,6 +117,37 @@ __device__ __forceinline__ void load_points(const float *pos, const float *t, in
 #pragma unroll
         for (int a = 0; a < 3; ++a) px[j][a] = pos[3 * s + a];
         tq[j] = t[s];
+    }
+}
+
+// the rows of a rays entry: n, or the device-side count where one is given and smaller
+__device__ __forceinline__ int64_t sample_count(int64_t n, const int64_t *n_dev)
+{
+    if (!n_dev) return n;
+    const int64_t nd = *n_dev;
+    return nd < n ? nd : n;
+}
+
+// Position and time of sample c of each 16-sample column tile of an op whose Args carry MoveArgs' sample fields (pos, t,
+// rays_o, rays_d, ray_idx, t0, t1, timestamps, rays_mode, t_per_ray): the expressions of field_kernel.hpp / field_half.hip
+// (rays mode: o + (d * (t0 + t1)) / 2 in fp32; a negative ray index is evaluated on ray 0 at distance 0).  A ragged last
+// tile repeats the last sample (never stored).
+template <int NT, typename Args>
+__device__ __forceinline__ void load_samples(const Args &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[NT][3],
+                                             float (&tq)[NT])
+{
+    if (!A.rays_mode) return load_points<NT>(A.pos, A.t, n_eff, tile_base, c, px, tq);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        int64_t s = tile_base + 16 * j + c;
+        s = s < n_eff ? s : n_eff - 1;
+        const int64_t r_in = A.ray_idx[s];
+        const bool used = r_in >= 0;
+        const int64_t r = used ? r_in : 0;
+        const float tm2 = used ? A.t0[s] + A.t1[s] : 0.0f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) px[j][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
+        tq[j] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
     }
 }
 

@@ -26,6 +26,34 @@ __global__ void frame_to_rgb8_kernel(int H, int W, const float *__restrict__ rgb
     for (int c = 0; c < 3; ++c) out[3 * i + c] = to_u8(rgb[3 * src + c] * 255.0f);
 }
 
+// Optical flow as colour (include/cednerf_hip.h states the formula): direction -> hue, magnitude / max_mag -> saturation,
+// value 1, on the HSV wheel in closed form.
+__device__ __forceinline__ float hsv_channel(float n, float h6, float sat)
+{
+    const float x = n + h6;
+    const float k = x >= 6.0f ? x - 6.0f : x;
+    const float m = fminf(fminf(k, 4.0f - k), 1.0f);
+    return 1.0f - sat * fmaxf(m, 0.0f);
+}
+
+__global__ void flow_to_rgb8_kernel(int H, int W, const float *__restrict__ flow, float max_mag, int flip_w, uint8_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;          // destination pixel
+    if (i >= (int64_t)H * W) return;
+    const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
+    const int64_t src = (int64_t)y * W + (flip_w ? W - 1 - x : x);
+    const float fx = flow[2 * src], fy = flow[2 * src + 1];
+    const bool finite = __builtin_fabsf(fx) < __builtin_inff() && __builtin_fabsf(fy) < __builtin_inff();
+    float h = atan2f(fy, fx) * 0.15915494309189535f;                           // 1 / (2 pi)
+    h = h < 0.0f ? h + 1.0f : h;
+    h = h >= 1.0f ? 0.0f : h;
+    const float h6 = h * 6.0f;
+    const float sat = fminf(__builtin_sqrtf(fx * fx + fy * fy) / max_mag, 1.0f);
+    const float nch[3] = { 5.0f, 3.0f, 1.0f };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * i + c] = finite ? to_u8(hsv_channel(nch[c], h6, sat) * 255.0f) : (uint8_t)0;
+}
+
 // Rendered pixels arrive in the order the rays were marched in (8x8-tile order; with several GPUs every rank's shard
 // of it, all-gathered): row i of the source goes to raster pixel dest[i] (rows with dest >= n_pixels are padding).
 // One pass writes the three raster images -- and, when asked, the 8-bit colour frame as well, so that a video frame
@@ -115,6 +143,19 @@ extern "C" int ced_frame_to_rgb8(int32_t height, int32_t width, const float *rgb
     hipLaunchKernelGGL(ced::frame_to_rgb8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (int)height, (int)width, rgb, (int)flip_w, out);
     return ced::check_launch("frame_to_rgb8");
+}
+
+extern "C" int ced_flow_to_rgb8(int32_t height, int32_t width, const float *flow, float max_mag, int32_t flip_w, uint8_t *out,
+                                void *stream)
+{
+    CED_REQUIRE(height >= 0 && width >= 0, "flow_to_rgb8: negative size");
+    CED_REQUIRE(max_mag > 0.0f, "flow_to_rgb8: max_mag=%g must be > 0 (and not a NaN)", (double)max_mag);
+    const int64_t n = (int64_t)height * width;
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(flow && out, "flow_to_rgb8: null pointer");
+    hipLaunchKernelGGL(ced::flow_to_rgb8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (int)height, (int)width, flow, max_mag, (int)flip_w, out);
+    return ced::check_launch("flow_to_rgb8");
 }
 
 extern "C" int ced_depth_to_u8(int32_t height, int32_t width, const float *depth, int32_t flip_w, uint8_t *out,

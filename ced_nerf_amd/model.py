@@ -249,10 +249,22 @@ class DNGPradianceField(torch.nn.Module):
     def query_velocity(self, x: torch.Tensor, t: torch.Tensor):
         """The velocity of the material point that sits at x at time t (the scene flow): its canonical coordinate
         c = x + move(x, t) does not change, so (I + J_x) v + d move / dt = 0 and v = -(I + J_x)^-1 d move / dt.
-        Returns (v [N,3], det [N]) with det = det(I + J_x); where det <= 0 the warp folds and v means little."""
+        Returns (v [N,3], det [N]) with det = det(I + J_x); where det <= 0 the warp folds and v means little.
+        `query_scene_flow` is the same quantity from one fused launch, guarded: 0 and flagged where the warp folds."""
         _, jac = self.query_move_jacobian(x, t)
         _, inv, det = ops.warp_gradient(jac)
         return -(inv @ jac[..., 3:]).squeeze(-1), det
+
+    @torch.no_grad()
+    def query_scene_flow(self, x: torch.Tensor, t: torch.Tensor):
+        """The scene flow at (x, t): `query_velocity`'s v = -(I + J_x)^-1 d move / dt from ONE launch that keeps the
+        Jacobian in registers (ced_field_velocity; include/cednerf_hip.h states every operation), with a guard.  Returns
+        (v [N,3], det [N], valid [N] bool): det = det(I + J_x) as computed; valid = det >= 2^-20 and v finite; where not
+        valid -- the warp folds there, or the Jacobian is not finite -- v is exactly 0 instead of an infinity, so that a
+        sum of w_i * v_i along a ray is not poisoned by one sample.  x is viewed as [-1, 3], t as [-1]."""
+        if not (x.is_cuda and t.is_cuda):
+            raise NotImplementedError("Only support cuda inputs: query_scene_flow runs on the HIP kernel (no CPU fallback).")
+        return ops.field_velocity(self._descriptor(), x.reshape(-1, 3).float().contiguous(), t.reshape(-1).float().contiguous())
 
     @torch.no_grad()
     def query_density_gradient(self, x: torch.Tensor, t: torch.Tensor, canonical: bool = False):
@@ -404,6 +416,18 @@ class DNGPradianceField(torch.nn.Module):
         ts = timestamps.reshape(-1).float().contiguous()
         return ops.field_density_gradient_rays(self._descriptor(), rays_o, rays_d, ray_indices, t_starts, t_ends, ts,
                                                bool(self.training), want, n_dev=n_dev)
+
+    @torch.no_grad()
+    def query_scene_flow_rays(self, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, want=(True, True, True),
+                              n_dev: Optional[torch.Tensor] = None):
+        """`query_scene_flow` at the samples `query_rays` evaluates (same positions, same per-ray / per-frame timestamps):
+        returns (v [S,3], det [S], valid [S] bool), None where want= is False."""
+        if not (rays_o.is_cuda and rays_d.is_cuda):
+            raise NotImplementedError("Only support cuda inputs: query_scene_flow_rays runs on the HIP kernel (no CPU fallback).")
+        ts = timestamps.reshape(-1).float().contiguous()
+        return ops.field_velocity_rays(self._descriptor(), rays_o, rays_d, ray_indices, t_starts, t_ends, ts,
+                                       bool(self.training), want, n_dev=n_dev)
+
 
 def make_occ_eval_fn(radiance_field: "DNGPradianceField", timestamps: torch.Tensor, render_step_size: float):
     """The occ_eval_fn closure of train_real.py:324-328: a random training timestamp per point,

@@ -398,6 +398,63 @@ def field_move_jacobian(desc: _lib.FieldDesc, positions, t, want=(True, True)):
     return move, jac
 
 
+VELOCITY_OUTPUTS = ("velocity", "det", "valid")   # ced_field_velocity's outputs, in `want=` order
+
+
+def _velocity_outputs(n, dev, want, who):
+    if len(want) != len(VELOCITY_OUTPUTS):
+        raise ValueError(f"{who}: want= takes one flag per output {VELOCITY_OUTPUTS}")
+    if not any(want):
+        raise ValueError(f"{who}: no output requested")
+    return [torch.empty((n, 3), device=dev, dtype=torch.float32) if want[0] else None,
+            torch.empty((n,), device=dev, dtype=torch.float32) if want[1] else None,
+            torch.empty((n,), device=dev, dtype=torch.bool) if want[2] else None]
+
+
+def field_velocity(desc: _lib.FieldDesc, positions, t, want=(True, True, True)):
+    """ced_field_velocity: (velocity [n,3], det [n], valid [n] bool) at positions [n,3], t [n], from one launch: the
+    velocity v = -(I + J_x)^-1 d move / dt of the material point that sits there, J being `field_move_jacobian`'s (its
+    bits), det = det(I + J_x), valid = det >= 2^-20 and v finite; v is 0 where not valid (include/cednerf_hip.h states every
+    operation).  want = which of the three to compute; the others come back as None."""
+    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
+    n = positions.shape[0]
+    if positions.shape != (n, 3) or t.numel() != n:
+        raise ValueError(f"positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
+    v, det, valid = _velocity_outputs(n, positions.device, want, "field_velocity")
+    rc = _lib.lib().ced_field_velocity(C.byref(desc), n, _p(positions), _p(t), _p(v), _p(det), _p(_as_u8(valid)), _stream())
+    _lib.check(rc, "field_velocity")
+    return v, det, valid
+
+
+def field_velocity_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray: bool,
+                        want=(True, True, True), n_dev: Optional[torch.Tensor] = None, out=None):
+    """ced_field_velocity_rays: `field_velocity` at the sample positions of `field_forward_rays`.  n_dev as there; out =
+    the three buffers (or None each) to write into instead of fresh ones, which then decides what is computed."""
+    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
+    _chk(ray_indices, torch.int64, "ray_indices")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
+    _chk(timestamps, torch.float32, "timestamps")
+    n = ray_indices.shape[0]
+    assert t_starts.shape == (n,) and t_ends.shape == (n,)
+    if t_per_ray:
+        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
+    if out is not None:
+        outs = list(out)
+        if len(outs) != len(VELOCITY_OUTPUTS) or all(o is None for o in outs):
+            raise ValueError("field_velocity_rays: no output requested")
+        for i, (o, dt, shape) in enumerate(zip(outs, (torch.float32, torch.float32, torch.bool), ((n, 3), (n,), (n,)))):
+            _chk(o, dt, f"out[{i}]", allow_none=True)
+            assert o is None or o.shape == shape, (i, o.shape)
+    else:
+        outs = _velocity_outputs(n, rays_o.device, want, "field_velocity_rays")
+    v, det, valid = outs
+    rc = _lib.lib().ced_field_velocity_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices),
+                                            _p(t_starts), _p(t_ends), _p(timestamps), int(bool(t_per_ray)), _p(v), _p(det),
+                                            _p(_as_u8(valid)), _stream())
+    _lib.check(rc, "field_velocity_rays")
+    return v, det, valid
+
+
 GRADIENT_OUTPUTS = ("sigma", "grad", "dlog", "dlog_canonical")   # ced_field_density_gradient's outputs, in `want=` order
 EXP15 = float(np.float32(np.exp(15.0)))                             # trunc_exp's backward clamps there (3269017.25)
 
@@ -791,6 +848,22 @@ def frame_to_rgb8(rgb, flip_w: bool = True):
     out = torch.empty(rgb.shape, device=rgb.device, dtype=torch.uint8)
     _lib.check(_lib.lib().ced_frame_to_rgb8(rgb.shape[0], rgb.shape[1], _p(rgb), int(bool(flip_w)), _p(out), _stream()),
                "frame_to_rgb8")
+    return out
+
+
+def flow_to_rgb8(flow, max_mag: float, flip_w: bool = True):
+    """ced_flow_to_rgb8: a flow image [H,W,2] as colour [H,W,3] uint8 on the HSV wheel: hue = the direction atan2(fy, fx),
+    saturation = min(|f| / max_mag, 1), value 1 -- no flow white, max_mag along +x pure red -- converted and flipped as
+    `frame_to_rgb8`; a pixel that is not finite is black (include/cednerf_hip.h states the formula)."""
+    _chk(flow, torch.float32, "flow")
+    if flow.dim() != 3 or flow.shape[2] != 2:
+        raise ValueError(f"flow_to_rgb8: flow [H,W,2], got {list(flow.shape)}")
+    max_mag = float(max_mag)
+    if not max_mag > 0.0:
+        raise ValueError(f"flow_to_rgb8: max_mag={max_mag!r} must be > 0")
+    out = torch.empty((flow.shape[0], flow.shape[1], 3), device=flow.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().ced_flow_to_rgb8(flow.shape[0], flow.shape[1], _p(flow), max_mag, int(bool(flip_w)), _p(out),
+                                           _stream()), "flow_to_rgb8")
     return out
 
 

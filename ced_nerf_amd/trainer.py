@@ -27,7 +27,7 @@ from . import synthetic
 from .metrics import evaluate_views
 from .nerfacc_api import OccGridEstimator
 from .train import TrainableField, next_num_rays, refresh_occupancy, train_step
-from .trainset import BKGD_MODES, VIEW_MODES, TrainViews
+from .trainset import BKGD_MODES, CAMERA_PINHOLE, VIEW_MODES, TrainViews
 
 
 def _preset(name: str, max_steps: int, init_batch_size: int, target_sample_batch_size: int, lr: float, milestones,
@@ -272,10 +272,16 @@ def dynerf_sampling(train: TrainViews, ist_from_step: Optional[int] = None, verb
 
 
 def write_video_frames(out_dir: str, inference, estimator, cfg: Dict, test: TrainViews, kind: str,
-                       n_frames: Optional[int] = None) -> int:
+                       n_frames: Optional[int] = None, flow: bool = False, flow_max: Optional[float] = None) -> int:
     """train_real.py:531-558 up to the encoder: renders DyNeRF's spiral path (`render_poses`) or, for the other two
     kinds, the test views' cameras at their times with `video.render_video` on black with 1024 samples per ray, and
-    writes `rgb_%04d.png` / `depth_%04d.png` (8-bit normalised depth) into `out_dir`.  Returns the frame count."""
+    writes `rgb_%04d.png` / `depth_%04d.png` (8-bit normalised depth) into `out_dir`.  Returns the frame count.
+    flow=True (pinhole paths only): also `flow_%04d.png`, the frame's optical flow into its own camera over one frame of
+    the path -- dt = 1 / frames for the spiral, the mean spacing of the views' times otherwise -- as the expected flow of
+    the visible surface (flow / coverage, nothing where coverage < 1e-3) on `ops.flow_to_rgb8`'s colour wheel, fully
+    saturated at flow_max pixels (default: the largest magnitude of the frames written).  The frames are mirrored along
+    the width like the rgb frames, and the flow's x component with them, so the hue is the direction seen in the PNG."""
+    from . import cameras, ops
     from .video import render_video
     try:
         from PIL import Image
@@ -286,19 +292,36 @@ def write_video_frames(out_dir: str, inference, estimator, cfg: Dict, test: Trai
         total = len(test.render_poses)
         rays_of = lambda i: test.render_path_rays(i)[0]
         time_of = lambda i: torch.full((1, 1), float(i) / total, device=dev, dtype=torch.float32)
+        projector_of = lambda i: cameras.pinhole_projector(test.K[0], test.render_poses[i], opengl=test.opengl, device=dev)
+        dt = 1.0 / total
     else:
         total = len(test)
         rays_of = test.view_rays
         time_of = lambda i: test.timestamps[i].reshape(1, 1)
+        projector_of = lambda i: cameras.pinhole_projector(test.K[i], test.c2w[i], opengl=test.opengl, device=dev)
+        dt = float(test.timestamps.max() - test.timestamps.min()) / max(total - 1, 1) if flow else 0.0
+    if flow and test.model != CAMERA_PINHOLE:
+        raise ValueError("flow=True needs pinhole cameras (D-NeRF test views, the DyNeRF spiral): these views have "
+                         "distorted HyperNeRF cameras, for which no projector is built")
     n = total if n_frames is None else max(0, min(int(n_frames), total))
     render = dict(near_plane=cfg["near_plane"], far_plane=cfg["far_plane"], render_step_size=cfg["render_step_size"],
                   cone_angle=cfg["cone_angle"], alpha_thre=cfg["alpha_thre"], render_bkgd=torch.zeros(3, device=dev))
     frames = render_video(inference, estimator, rays_of, time_of, n, max_samples=1024, render_kwargs=render,
-                          to_host=True)
+                          to_host=True, optical_flow=(projector_of, dt) if flow else None)
     os.makedirs(out_dir, exist_ok=True)
     for i, frame in enumerate(frames):
         Image.fromarray(frame["rgb"]).save(os.path.join(out_dir, f"rgb_{i:04d}.png"))
         Image.fromarray(frame["depth"]).save(os.path.join(out_dir, f"depth_{i:04d}.png"))
+    if flow and frames:
+        seen = [frame["flow_coverage_f32"] >= 1e-3 for frame in frames]
+        expected = [torch.where(s, frame["flow_f32"] / frame["flow_coverage_f32"].clamp_min(1e-3), torch.zeros((), device=dev))
+                    .contiguous() for s, frame in zip(seen, frames)]
+        if flow_max is None:
+            flow_max = max(float(e.norm(dim=-1).max()) for e in expected)
+        flow_max = flow_max if flow_max > 0 else 1.0
+        mirror = torch.tensor([-1.0, 1.0], device=dev)                   # render_video's frames are flipped along the width
+        for i, e in enumerate(expected):
+            Image.fromarray(ops.flow_to_rgb8(e * mirror, flow_max).cpu().numpy()).save(os.path.join(out_dir, f"flow_{i:04d}.png"))
     return len(frames)
 
 
@@ -321,6 +344,10 @@ def main(argv=None) -> int:
     p.add_argument("--assume_tcnn_layout", default=None, help="for a --load_model file written by the reference")
     p.add_argument("--render_video", default=None, metavar="DIR", help="write rgb_%%04d.png / depth_%%04d.png here")
     p.add_argument("--video_frames", type=int, default=None, help="render only the first N frames of the path")
+    p.add_argument("--video_flow", action="store_true",
+                   help="with --render_video: also write flow_%%04d.png, the optical flow over one frame of the path (pinhole cameras)")
+    p.add_argument("--video_flow_max", type=float, default=None, metavar="PX",
+                   help="flow magnitude in pixels at full saturation (default: the largest of the frames written)")
     p.add_argument("--ist_from_step", type=int, default=None, help="DyNeRF: sample by the IST map from this step on")
     p.add_argument("-df", "--use_div_offsets", action="store_true")
     p.add_argument("-f", "--use_feat_predict", action="store_true")
@@ -351,7 +378,12 @@ def main(argv=None) -> int:
     flags = dict(use_div_offsets=a.use_div_offsets, use_time_embedding=a.use_time_embedding,
                  use_time_attenuation=a.use_time_attenuation, use_feat_predict=a.use_feat_predict,
                  use_weight_predict=a.use_weight_predict)
+    if a.video_flow and not a.render_video:
+        p.error("--video_flow goes with --render_video DIR")
     test = load_scene(a.data_root, a.scene, kind, test_split, a.factor)
+    if a.video_flow and test.model != CAMERA_PINHOLE:
+        p.error("--video_flow needs pinhole cameras (D-NeRF test views, the DyNeRF spiral): these views have distorted "
+                "HyperNeRF cameras, for which no projector is built")
     if a.load_model:                             # train_real.py:189-190, 524-529: no training set, no loop
         cfg = resolve_config(kind, a.max_steps, **extra)
         ckpt = checkpoint.read_checkpoint(a.load_model)
@@ -369,8 +401,9 @@ def main(argv=None) -> int:
                   log_every=log_every, save_path=a.save_path, **flags, **sampling, **extra)
         inference, estimator, cfg = res["inference"], res["estimator"], res["config"]
     if a.render_video:
-        n = write_video_frames(a.render_video, inference.eval(), estimator.eval(), cfg, test, kind, a.video_frames)
-        print(f"wrote {n} rgb and depth frames to {a.render_video}", flush=True)
+        n = write_video_frames(a.render_video, inference.eval(), estimator.eval(), cfg, test, kind, a.video_frames,
+                               flow=a.video_flow, flow_max=a.video_flow_max)
+        print(f"wrote {n} rgb and depth{' and flow' if a.video_flow else ''} frames to {a.render_video}", flush=True)
     return 0
 
 

@@ -195,19 +195,27 @@ def render_image(
             depths.view((*rays_shape[:-1], -1)), sum(n_rendering_samples), extra_info)
 
 
-def _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle, alpha_thre,
-                          test_chunk_size, timestamps, return_samples, who, key, values_fn):
-    """What `render_motion` and `render_normals` share: a per-sample [S,3] quantity composited with the volume-rendering
-    weights on exactly the samples `render_image` takes in eval mode.  values_fn(o, d, ray_indices, t_starts, t_ends, ts)
-    -> [S,3]; `key` names it in the per-chunk sample dicts."""
+def _check_eval_frame(radiance_field, timestamps, who):
     if timestamps is None:
         raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:78-86)")
     if radiance_field.training:
         raise NotImplementedError(f"{who} renders eval frames (one time per frame)")
+
+
+def _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle, alpha_thre,
+                          test_chunk_size, timestamps, return_samples, who, key, values_fn):
+    """What `render_motion`, `render_normals` and the flow maps share: per-sample quantities composited with the
+    volume-rendering weights on exactly the samples `render_image` takes in eval mode.
+    values_fn(o, d, ray_indices, t_starts, t_ends, ts) -> [S,C], named `key` in the per-chunk sample dicts; or, with `key` a
+    tuple of names, a dict of per-sample tensors that holds at least those names: each named one ([S,C] float, or [S] bool
+    taken as 0 / 1) becomes an image, in that order, and every entry of the dict goes into the sample dicts.
+    Returns (image [H,W,C] per name, opacity [H,W,1], n_samples[, samples])."""
+    _check_eval_frame(radiance_field, timestamps, who)
     rays, rays_shape, num_rays = _flatten_rays(rays)
     ts = timestamps
     pass_rays = max(test_chunk_size, (_EVAL_PASS_RAYS // test_chunk_size) * test_chunk_size)
-    images, opacities, samples, n_samples = [], [], [], 0
+    keys = (key,) if isinstance(key, str) else tuple(key)
+    images, opacities, samples, n_samples = [[] for _ in keys], [], [], 0
     for i in range(0, num_rays, pass_rays):
         chunk_rays = namedtuple_map(lambda r: r[i:i + pass_rays].contiguous().float(), rays)
         o, d = chunk_rays.origins, chunk_rays.viewdirs
@@ -220,15 +228,19 @@ def _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane
             o, d, sigma_fn=sigma_fn, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size,
             stratified=False, cone_angle=cone_angle, alpha_thre=alpha_thre, sigma_field=(radiance_field, ts, False))
         values = values_fn(o, d, ray_indices, t_starts, t_ends, ts)
+        if isinstance(key, str):
+            values = {key: values}
         sigmas = sigma_fn(t_starts, t_ends, ray_indices)
         packed = _packed_info_from(ray_indices, n_pass)
         weights, _, _ = render_weight_from_density(t_starts, t_ends, sigmas, packed_info=packed)
-        images.append(accumulate_along_rays(weights, values=values, packed_info=packed))
+        for k, out in zip(keys, images):
+            v = values[k]
+            out.append(accumulate_along_rays(weights, values=v if v.dim() == 2 else v.float()[:, None], packed_info=packed))
         opacities.append(accumulate_along_rays(weights, values=None, packed_info=packed))
         n_samples += int(t_starts.shape[0])
         if not return_samples:
             continue
-        extras = {"ray_indices": ray_indices, "t_starts": t_starts, "t_ends": t_ends, "weights": weights, key: values}
+        extras = {"ray_indices": ray_indices, "t_starts": t_starts, "t_ends": t_ends, "weights": weights, **values}
         if n_pass <= test_chunk_size:
             samples.append(extras)
             continue
@@ -239,11 +251,12 @@ def _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane
         extras["ray_indices"] = ray_indices % test_chunk_size
         cut = {k: v.split(sizes) for k, v in extras.items()}
         samples.extend([{k: cut[k][c] for k in cut} for c in range(len(sizes))])
-    image = torch.cat(images, dim=0).view((*rays_shape[:-1], 3))
+    out = [torch.cat(parts, dim=0) for parts in images]
+    out = [im.view((*rays_shape[:-1], im.shape[-1])) for im in out]
     opacity = torch.cat(opacities, dim=0).view((*rays_shape[:-1], 1))
     if return_samples:
-        return image, opacity, n_samples, samples
-    return image, opacity, n_samples
+        return (*out, opacity, n_samples, samples)
+    return (*out, opacity, n_samples)
 
 
 @torch.no_grad()
@@ -303,6 +316,92 @@ def render_normals(
 
     return _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle,
                                  alpha_thre, test_chunk_size, timestamps, return_samples, "render_normals", "normal", normal_fn)
+
+
+@torch.no_grad()
+def render_scene_flow(
+    radiance_field: torch.nn.Module,
+    estimator: OccGridEstimator,
+    rays: Rays,
+    near_plane: float = 0.0,
+    far_plane: float = 1e10,
+    render_step_size: float = 1e-3,
+    cone_angle: float = 0.0,
+    alpha_thre: float = 0.0,
+    test_chunk_size: int = 8192,
+    timestamps: Optional[torch.Tensor] = None,
+    return_samples: bool = False,
+):
+    """Per-pixel scene flow: the velocity of the material point at every sample (`query_scene_flow`: v = -(I + J_x)^-1
+    d move / dt from one fused launch, 0 and flagged where the warp folds) composited with the volume-rendering weights,
+    on exactly `render_motion`'s samples for the same arguments.
+    Returns (flow3d [H,W,3], opacity [H,W,1], coverage [H,W,1], n_samples): flow3d = sum_i w_i * v_i in world units per
+    unit of time, coverage = sum_i w_i * valid_i <= opacity, neither normalised -- the expected velocity of the visible
+    surface is flow3d / coverage (where coverage > 0).  Rays that meet no sample have zeros.  With return_samples=True a
+    fifth value is the list of per-chunk dicts, as `render_motion`'s with `velocity` [S,3], `det` [S] and `valid` [S] bool
+    in place of `move`."""
+    _check_eval_frame(radiance_field, timestamps, "render_scene_flow")
+    if not rays.origins.is_cuda:
+        raise NotImplementedError("Only support cuda inputs: render_scene_flow runs on the HIP kernels (no CPU fallback).")
+
+    def flow_fn(o, d, ray_indices, t_starts, t_ends, ts):
+        v, det, valid = radiance_field.query_scene_flow_rays(o, d, ray_indices, t_starts, t_ends, ts)
+        return {"velocity": v, "det": det, "valid": valid}
+
+    flow3d, coverage, opacity, *rest = _render_sample_values(
+        radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle, alpha_thre, test_chunk_size,
+        timestamps, return_samples, "render_scene_flow", ("velocity", "valid"), flow_fn)
+    return (flow3d, opacity, coverage, *rest)
+
+
+def sample_positions(o, d, ray_indices, t_starts, t_ends):
+    """The sample positions the field kernels evaluate, in their own fp32 expression: o + (d * (t0 + t1)) / 2."""
+    return o[ray_indices] + (d[ray_indices] * (t_starts + t_ends)[:, None]) / 2.0
+
+
+@torch.no_grad()
+def render_optical_flow(
+    radiance_field: torch.nn.Module,
+    estimator: OccGridEstimator,
+    rays: Rays,
+    project,
+    dt: float,
+    near_plane: float = 0.0,
+    far_plane: float = 1e10,
+    render_step_size: float = 1e-3,
+    cone_angle: float = 0.0,
+    alpha_thre: float = 0.0,
+    test_chunk_size: int = 8192,
+    timestamps: Optional[torch.Tensor] = None,
+    return_samples: bool = False,
+):
+    """Per-pixel optical flow, in pixels per `dt`: every sample x_i is moved along its scene flow by dt, both points are
+    projected, and the image-plane displacements are composited on `render_scene_flow`'s samples:
+        flow2d = sum_i w_i * ok_i * (project(x_i + dt * v_i) - project(x_i)),   ok_i = valid_i and both points in front.
+    project(points [S,3]) -> (pixels [S,2], in_front [S] bool) is any callable of that shape, applied to device tensors
+    (`cameras.pinhole_projector` is the one shipped); it may project into another camera than the rays', e.g. the next
+    frame's, if it is given that camera.  dt is a time difference in the units of `timestamps` (one frame of a path).
+    Returns (flow2d [H,W,2], opacity [H,W,1], coverage [H,W,1], n_samples): coverage = sum_i w_i * ok_i <= opacity; the
+    expected flow of the visible surface is flow2d / coverage.  With return_samples=True a fifth value is the list of
+    per-chunk dicts, `render_scene_flow`'s plus `flow` [S,2] (the displacement, 0 where not ok) and `ok` [S] bool."""
+    _check_eval_frame(radiance_field, timestamps, "render_optical_flow")
+    if not rays.origins.is_cuda:
+        raise NotImplementedError("Only support cuda inputs: render_optical_flow runs on the HIP kernels (no CPU fallback).")
+    dt = float(dt)
+
+    def flow_fn(o, d, ray_indices, t_starts, t_ends, ts):
+        v, det, valid = radiance_field.query_scene_flow_rays(o, d, ray_indices, t_starts, t_ends, ts)
+        x = sample_positions(o, d, ray_indices, t_starts, t_ends)
+        p0, front0 = project(x)
+        p1, front1 = project(x + dt * v)
+        ok = valid & front0 & front1
+        flow = torch.where(ok[:, None], (p1 - p0).float(), torch.zeros((), device=x.device))
+        return {"flow": flow.contiguous(), "ok": ok, "velocity": v, "det": det, "valid": valid}
+
+    flow2d, coverage, opacity, *rest = _render_sample_values(
+        radiance_field, estimator, rays, near_plane, far_plane, render_step_size, cone_angle, alpha_thre, test_chunk_size,
+        timestamps, return_samples, "render_optical_flow", ("flow", "ok"), flow_fn)
+    return (flow2d, opacity, coverage, *rest)
 
 
 @torch.no_grad()

@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .dist import PipelinedRenderer, ShardedRenderer
-from .utils import Rays, render_motion, render_normals
+from .utils import Rays, render_motion, render_normals, render_optical_flow, render_scene_flow
 
 
 def frame_to_uint8(rgb: torch.Tensor, depth: torch.Tensor, flip_w: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -30,7 +30,8 @@ def frame_to_uint8(rgb: torch.Tensor, depth: torch.Tensor, flip_w: bool = True) 
 def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays], timestamps_of_frame: Callable[[int], torch.Tensor],
                  n_frames: int, max_samples: int = 1024, render_kwargs: Optional[Dict] = None, frames_in_flight: int = 3,
                  flip_w: bool = True, to_host: bool = False, keep_float: bool = False, frames_per_call: int = 1,
-                 motion: bool = False, normals: bool = False) -> List[Dict]:
+                 motion: bool = False, normals: bool = False, scene_flow: bool = False,
+                 optical_flow: Optional[Tuple[Callable[[int], Callable], float]] = None) -> List[Dict]:
     """Render frames 0..n_frames-1 of a path.
 
     rays_of_frame(i) -> Rays with [H,W,3] device tensors (e.g. `cameras.pinhole_rays(K, c2w_i, W, H)`; it is called on
@@ -44,7 +45,11 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
     motion=True: every frame's dict also carries `motion_f32` [H,W,3], the deformation field's motion map
     (`utils.render_motion`) rendered after the frame on the frame's rays and time with the march options of
     render_kwargs; the frames themselves are rendered exactly as without it.
-    normals=True: likewise `normals_f32` [H,W,3], the frame's normal map (`utils.render_normals`)."""
+    normals=True: likewise `normals_f32` [H,W,3], the frame's normal map (`utils.render_normals`).
+    scene_flow=True: likewise `scene_flow_f32` [H,W,3] (`utils.render_scene_flow`'s flow3d).
+    optical_flow=(projector_of_frame, dt): likewise `flow_f32` [H,W,2] and `flow_coverage_f32` [H,W,1],
+    `utils.render_optical_flow` with project = projector_of_frame(i) (e.g. `cameras.pinhole_projector(K, c2w_i)`) and the
+    time step dt; the expected flow of the visible surface, in pixels per dt, is flow_f32 / flow_coverage_f32."""
     if n_frames <= 0:
         return []
     device = radiance_field.aabb.device if hasattr(radiance_field, "aabb") else torch.device("cuda")
@@ -82,9 +87,16 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
                 frames.append(f)
     kw = {k: v for k, v in (render_kwargs or {}).items()
           if k in ("near_plane", "far_plane", "render_step_size", "cone_angle", "alpha_thre")}
-    for key, on, render in (("motion_f32", motion, render_motion), ("normals_f32", normals, render_normals)):
+    for key, on, render in (("motion_f32", motion, render_motion), ("normals_f32", normals, render_normals),
+                            ("scene_flow_f32", scene_flow, render_scene_flow)):
         if not on:
             continue
         for i, f in enumerate(frames):
             f[key] = render(radiance_field, estimator, rays_of_frame(i), timestamps=timestamps_of_frame(i), **kw)[0]
+    if optical_flow is not None:
+        projector_of_frame, dt = optical_flow
+        for i, f in enumerate(frames):
+            flow, _, coverage, _ = render_optical_flow(radiance_field, estimator, rays_of_frame(i), projector_of_frame(i), dt,
+                                                       timestamps=timestamps_of_frame(i), **kw)
+            f.update(flow_f32=flow, flow_coverage_f32=coverage)
     return frames

@@ -359,6 +359,35 @@ int ced_field_track_newton(const ced_field_desc *desc, int64_t n_points, int64_t
                            const float *times, const float *init, int32_t max_iters, float tol, float *x,
                            float *step, int32_t *evals, void *stream);
 
+/* ---- the velocity of the warp ----
+ * Where the material point that sits at x at time t is going: differentiating x(t) + move(x(t), t) = c in t gives
+ *     v = -(I + J_x)^-1 d move / dt
+ * with J = ced_field_move_jacobian's jac of the row (its bits, in desc->mlp_precision), from the same launch: the
+ * Jacobian is not written out.  Per row, r = J[:, 3] (the time column), every line in fp32, every product, sum, difference
+ * and quotient rounded on its own (no fused multiply-add) -- the Newton step's arithmetic on another right-hand side:
+ *     A = I + J[:, :3]                                          -- A[a][a] = 1.0f + J[a][a], A[a][b] = J[a][b]
+ *     C[a][b] = A[a+1][b+1] * A[a+2][b+2] - A[a+1][b+2] * A[a+2][b+1]      -- cofactors, indices mod 3
+ *     det = (A[0][0] * C[0][0] + A[0][1] * C[0][1]) + A[0][2] * C[0][2]
+ *     d[a] = ((C[0][a] * r[0] + C[1][a] * r[1]) + C[2][a] * r[2]) / det
+ *     valid = det >= 2^-20 and every |d[a]| < infinity           -- false for a NaN
+ *     v[a] = valid ? -d[a] : 0
+ * A determinant that is not positive is a fold of the warp (several material points share x, none has "the" velocity) and
+ * is not valid, unlike in the Newton step, which only asks for |det| >= 2^-20.  A row that is not valid has velocity 0
+ * exactly, so that a sum of w_i * v_i along a ray stays finite; `det` is stored as computed, whatever `valid` says.
+ * Outputs: velocity [n,3], det [n], valid [n] uint8 (1 / 0); each may be NULL, not all three.  A row's outputs do not
+ * depend on n or on the other rows. */
+int ced_field_velocity(const ced_field_desc *desc, int64_t n, const float *positions, const float *t,
+                       float *velocity, float *det, uint8_t *valid, void *stream);
+
+/* The same at the sample positions of the sigma_fn / rgb_sigma_fn closures: positions, timestamps, t_per_ray and n_dev
+ * as in ced_field_move_rays (rows past min(n, *n_dev) are left untouched; a negative ray index is evaluated on ray 0 at
+ * distance 0). */
+int ced_field_velocity_rays(const ced_field_desc *desc, int64_t n, const int64_t *n_dev,
+                            const float *rays_o, const float *rays_d,
+                            const int64_t *ray_indices, const float *t_starts, const float *t_ends,
+                            const float *timestamps, int32_t t_per_ray, float *velocity, float *det, uint8_t *valid,
+                            void *stream);
+
 /* ---- the derivative of the density ----
  * sigma [n] and three gradients [n,3] per row (x, t), all in world units, from one launch; each output may be NULL, not
  * all.  sigma is ced_field_forward's, bit for bit, in desc->mlp_precision.  `grad` is what torch.autograd.grad(
@@ -580,6 +609,19 @@ int ced_ssim(int64_t n, int64_t c, int64_t h, int64_t w, const float *x, const i
 int ced_frame_to_rgb8(int32_t height, int32_t width, const float *rgb, int32_t flip_w, uint8_t *out, void *stream);
 int ced_depth_to_u8(int32_t height, int32_t width, const float *depth, int32_t flip_w, uint8_t *out,
                     void *workspace, void *stream);
+
+/* A flow image as colour, on the device: flow [H,W,2] f32 (x, y components), max_mag > 0, out [H,W,3] u8, the flip of
+ * ced_frame_to_rgb8.  The HSV wheel in closed form, every line in fp32, no fused multiply-add:
+ *     h = atan2f(fy, fx) * fp32(1 / (2 pi));  if h < 0: h = h + 1;  if h >= 1: h = 0              -- hue in [0, 1)
+ *     s = fminf(sqrtf(fx * fx + fy * fy) / max_mag, 1)                                            -- saturation; value = 1
+ *     for (channel, n) in (R, 5), (G, 3), (B, 1):
+ *         k = n + h * 6;  if k >= 6: k = k - 6
+ *         channel = 1 - s * fmaxf(fminf(fminf(k, 4 - k), 1), 0)
+ *     out = uint8(channel * 255)                          -- ced_frame_to_rgb8's conversion: clamped, truncated toward zero
+ * so no flow is white, flow along +x pure red, +y (down the image) yellow-green, -x cyan, and a magnitude of max_mag or
+ * more is fully saturated.  A pixel either of whose components is not finite is black (0, 0, 0). */
+int ced_flow_to_rgb8(int32_t height, int32_t width, const float *flow, float max_mag, int32_t flip_w, uint8_t *out,
+                     void *stream);
 
 /* The exchange's consumer ("a local un-permute fused into the consumer"): rendered pixels arrive in marching
  * order (8x8-tile order; with several GPUs every rank's shard of it, all-gathered as [rows, 5] = rgb, opacity, depth);
