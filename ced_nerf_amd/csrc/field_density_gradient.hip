@@ -18,25 +18,19 @@
 //      the PRIMAL pre-activation is not > 0;
 //   5. the fp32 lines of the header: 1 / extent, (I + J_x)^T, the slope of trunc_exp.
 //
-// Shape: tile_kernel's (field_move_device.hpp: persistent workgroups of 512 threads, wave w of workgroup b takes tiles
-// b * WAVES + w, + gridDim.x * WAVES, ..., the weights staged into LDS once, an opaque LDS base per tile) with two
-// additions that skeleton has no place for: the staged plane is the motion network AND mlp_base (they are adjacent in
-// every blob: 64 KB fp32 or split fp16 with a time encoding), and the sixteen levels' constants sit in LDS beside it, as
-// in the fused kernels.  ONE 16-row primal tile per wave iteration: stage 1 holds five operand and five accumulator
-// tiles, stage 4 four and four beside J and the 32 gathered values; two waves per SIMD, no scratch.
+// Shape: tile_kernel<GradientOp, W, 1, 512> of field_move_device.hpp, one more op on that skeleton.  The staged plane W is
+// the motion network AND mlp_base (adjacent in every blob: 64 KB fp32 or split fp16 with a time encoding); the sixteen
+// levels' constants sit in LDS beside it, as in the fused kernels, filled by the op's hook before the skeleton's barrier;
+// one workgroup per CU.  The rows come from that header's SampleSrc, which the two entries fill through point_samples /
+// ray_samples.  ONE 16-row primal tile per wave iteration: stage 1 holds five operand and five accumulator tiles, stage 4
+// four and four beside J and the 32 gathered values; two waves per SIMD, no scratch.
 #include "field_args.hpp"
 #include "field_jacobian_device.hpp"
 
 namespace ced {
 
 struct GradArgs {
-    int64_t n;
-    const int64_t *n_dev;                             // optional device-side row count (<= n)
-    const float *pos, *t;                             // explicit mode
-    const float *rays_o, *rays_d;                     // rays mode
-    const int64_t *ray_idx;
-    const float *t0, *t1, *timestamps;
-    int rays_mode, t_per_ray;
+    SampleSrc src;
     float *sigma, *grad, *dlog, *dlog_canonical;      // [n], [n,3] x 3; any may be null
     float aabb[6];
     float moving_step;
@@ -53,22 +47,6 @@ struct GradArgs {
 
 constexpr float kExp15 = 3269017.25f;                 // the float32 nearest e^15: trunc_exp's backward clamps there
 constexpr int kGradDirs = 3;                          // tangent directions: x_norm's three axes
-
-// position and time of row c of the tile: load_points, or the fused rays kernels' expression (field_kernel.hpp)
-__device__ __forceinline__ void grad_load(const GradArgs &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[1][3],
-                                          float (&tq)[1])
-{
-    if (!A.rays_mode) return load_points<1>(A.pos, A.t, n_eff, tile_base, c, px, tq);
-    int64_t s = tile_base + c;
-    s = s < n_eff ? s : n_eff - 1;
-    const int64_t r_in = A.ray_idx[s];
-    const bool used = r_in >= 0;
-    const int64_t r = used ? r_in : 0;
-    const float tm2 = used ? A.t0[s] + A.t1[s] : 0.0f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) px[0][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
-    tq[0] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
-}
 
 // a hidden layer's tangents as the next layer's operand (tangent_operand / tangent_operand_h for kGradDirs tiles beside
 // one primal tile): zero wherever the primal pre-activation is not > 0
@@ -186,150 +164,132 @@ __device__ __forceinline__ void base_gradient_half(const GradArgs &A, const _Flo
     for (int b = 0; b < kGradDirs; ++b) draw[b] = Dt[b][0][3];
 }
 
-// one 16-row tile; w = the tile's LDS base of the staged layers, ltab = the levels' constants
-template <typename W, bool TE, bool F16, bool TEMPORAL>
-__device__ __forceinline__ void gradient_tile(const GradArgs &A, const typename W::Elem *w, const uint32_t *ltab, int64_t tile_base,
-                                              int64_t n_eff, int lane)
-{
-    const int g = lane >> 4, c = lane & 15;
-    float px[1][3], tq[1], mv[1][3], J[1][12];
-    grad_load(A, tile_base, n_eff, c, px, tq);
-    motion_move_jacobian<W, 1>(w, lane, px, RowTime<1>{ tq }, A.moving_step, A.use_div, mv, J);
+// ---- ced_field_density_gradient, ced_field_density_gradient_rays: one 16-row tile per wave iteration -----------------------
+template <bool TE, bool F16, bool TEMPORAL> struct GradientOp : SampleOp {
+    using Args = GradArgs;
+    static constexpr int kPerCu = 1;
 
-    // x_norm / selector / |move| (model.py:378-383), as the fused kernels form them
-    const float extent[3] = { A.aabb[3] - A.aabb[0], A.aabb[4] - A.aabb[1], A.aabb[5] - A.aabb[2] };
-    float xn[3];
-    bool sel = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float xm = px[0][a] + mv[0][a];
-        const float x = (xm - A.aabb[a]) / extent[a];
-        sel = sel && (x > 0.0f && x < 1.0f);
-        xn[a] = __builtin_fminf(__builtin_fmaxf(x, 0.0f), 1.0f);
+    // the sixteen levels' constants, in LDS beside the staged layers
+    __device__ __forceinline__ static uint32_t *levels()
+    {
+        __shared__ __attribute__((aligned(16))) uint32_t table[8 * CED_MAX_LEVELS];
+        return table;
     }
-    const float mnorm = TE ? __builtin_sqrtf((mv[0][0] * mv[0][0] + mv[0][1] * mv[0][1]) + mv[0][2] * mv[0][2]) : 0.0f;
+    __device__ __forceinline__ static void fill_lds(const GradArgs &A, int tid)
+    {
+        if (tid < CED_MAX_LEVELS)
+            store_level(levels() + tid * 8, make_level(A.scale[tid], A.res[tid], A.offset[tid], A.size[tid], A.hashed[tid],
+                                                       EntryBytes<F16, TEMPORAL>::value));
+    }
 
-    // the lane's four levels: features and x-tangents from the same corner loads
-    float R[8], dR[kGradDirs][8];
-    int k_lo = 0;
-    float t_frac = 0.0f;
-    if constexpr (TEMPORAL) temporal_keyframe(tq[0], k_lo, t_frac);
+    // w = the tile's LDS base of the staged layers
+    template <typename W, int NT>
+    __device__ __forceinline__ static void tile(const GradArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base,
+                                                int64_t n_eff, int lane)
+    {
+        static_assert(NT == 1, "one primal tile beside its three tangent tiles");
+        const int g = lane >> 4, c = lane & 15;
+        float px[1][3], tq[1], mv[1][3], J[1][12];
+        load_samples<1>(A.src, tile_base, n_eff, c, px, tq);
+        motion_move_jacobian<W, 1>(w, lane, px, RowTime<1>{ tq }, A.moving_step, A.use_div, mv, J);
+
+        // x_norm / selector / |move| (model.py:378-383), as the fused kernels form them
+        const float extent[3] = { A.aabb[3] - A.aabb[0], A.aabb[4] - A.aabb[1], A.aabb[5] - A.aabb[2] };
+        float xn[3];
+        bool sel = true;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int level = W::kHalf ? 4 * i + g : 4 * i + 2 * (g & 1) + (g >> 1);
-        const LevelConst L = load_level(ltab + level * 8);
-        float d0[3], d1[3];
-        if (((A.level_mode >> (2 * i)) & 3) == 2)
-            hash_level_dx<F16, TEMPORAL, 2>(L, A.table, xn, k_lo, t_frac, A.tangent_scale, R[2 * i], R[2 * i + 1], d0, d1);
-        else
-            hash_level_dx<F16, TEMPORAL, 0>(L, A.table, xn, k_lo, t_frac, A.tangent_scale, R[2 * i], R[2 * i + 1], d0, d1);
-#pragma unroll
-        for (int b = 0; b < kGradDirs; ++b) {
-            dR[b][2 * i] = d0[b];
-            dR[b][2 * i + 1] = d1[b];
+        for (int a = 0; a < 3; ++a) {
+            const float xm = px[0][a] + mv[0][a];
+            const float x = (xm - A.aabb[a]) / extent[a];
+            sel = sel && (x > 0.0f && x < 1.0f);
+            xn[a] = __builtin_fminf(__builtin_fmaxf(x, 0.0f), 1.0f);
         }
-    }
+        const float mnorm = TE ? __builtin_sqrtf((mv[0][0] * mv[0][0] + mv[0][1] * mv[0][1]) + mv[0][2] * mv[0][2]) : 0.0f;
 
-    float raw_own, draw_own[kGradDirs];
-    if constexpr (W::kHalf)
-        base_gradient_half<TE, W::kSplit, W::kK32>(A, w, w + W::kPlane, lane, R, dR, tq[0], mnorm, raw_own, draw_own);
-    else
-        base_gradient_f32<TE>(A, w, lane, R, dR, tq[0], mnorm, raw_own, draw_own);
-
-    // lane group 3 holds row c's raw density and its tangents: every lane group takes them, then the header's fp32 lines
-    const float raw = __shfl(raw_own, 48 + c, 64);
-    float dc[3], dl[3], gr[3];
+        // the lane's four levels: features and x-tangents from the same corner loads
+        float R[8], dR[kGradDirs][8];
+        int k_lo = 0;
+        float t_frac = 0.0f;
+        if constexpr (TEMPORAL) temporal_keyframe(tq[0], k_lo, t_frac);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float dn = __fmul_rn(__shfl(draw_own[a], 48 + c, 64), A.tangent_unscale);
-        dc[a] = sel ? __fdiv_rn(dn, extent[a]) : 0.0f;
-    }
-    const float sg = det_expf(raw - 1.0f);
-    const float slope = __builtin_fminf(sg, kExp15);
+        for (int i = 0; i < 4; ++i) {
+            const int level = W::kHalf ? 4 * i + g : 4 * i + 2 * (g & 1) + (g >> 1);
+            const LevelConst L = load_level(levels() + level * 8);
+            float d0[3], d1[3];
+            if (((A.level_mode >> (2 * i)) & 3) == 2)
+                hash_level_dx<F16, TEMPORAL, 2>(L, A.table, xn, k_lo, t_frac, A.tangent_scale, R[2 * i], R[2 * i + 1], d0, d1);
+            else
+                hash_level_dx<F16, TEMPORAL, 0>(L, A.table, xn, k_lo, t_frac, A.tangent_scale, R[2 * i], R[2 * i + 1], d0, d1);
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        const float jt = __fadd_rn(__fadd_rn(__fmul_rn(J[0][b], dc[0]), __fmul_rn(J[0][4 + b], dc[1])), __fmul_rn(J[0][8 + b], dc[2]));
-        dl[b] = sel ? __fadd_rn(dc[b], jt) : 0.0f;
-        gr[b] = sel ? __fmul_rn(slope, dl[b]) : 0.0f;
+            for (int b = 0; b < kGradDirs; ++b) {
+                dR[b][2 * i] = d0[b];
+                dR[b][2 * i + 1] = d1[b];
+            }
+        }
+
+        float raw_own, draw_own[kGradDirs];
+        if constexpr (W::kHalf)
+            base_gradient_half<TE, W::kSplit, W::kK32>(A, w, w + W::kPlane, lane, R, dR, tq[0], mnorm, raw_own, draw_own);
+        else
+            base_gradient_f32<TE>(A, w, lane, R, dR, tq[0], mnorm, raw_own, draw_own);
+
+        // lane group 3 holds row c's raw density and its tangents: every lane group takes them, then the header's fp32 lines
+        const float raw = __shfl(raw_own, 48 + c, 64);
+        float dc[3], dl[3], gr[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float dn = __fmul_rn(__shfl(draw_own[a], 48 + c, 64), A.tangent_unscale);
+            dc[a] = sel ? __fdiv_rn(dn, extent[a]) : 0.0f;
+        }
+        const float sg = det_expf(raw - 1.0f);
+        const float slope = __builtin_fminf(sg, kExp15);
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const float jt = __fadd_rn(__fadd_rn(__fmul_rn(J[0][b], dc[0]), __fmul_rn(J[0][4 + b], dc[1])), __fmul_rn(J[0][8 + b], dc[2]));
+            dl[b] = sel ? __fadd_rn(dc[b], jt) : 0.0f;
+            gr[b] = sel ? __fmul_rn(slope, dl[b]) : 0.0f;
+        }
+
+        // lane group a < 3 stores component a, lane group 3 the density
+        const int64_t s = tile_base + c;
+        if (s >= n_eff) return;
+        if (g == 3) {
+            if (A.sigma) A.sigma[s] = sel ? sg : 0.0f;
+            return;
+        }
+        const float o_dc = (g == 0) ? dc[0] : (g == 1) ? dc[1] : dc[2];
+        const float o_dl = (g == 0) ? dl[0] : (g == 1) ? dl[1] : dl[2];
+        const float o_gr = (g == 0) ? gr[0] : (g == 1) ? gr[1] : gr[2];
+        if (A.dlog_canonical) A.dlog_canonical[3 * s + g] = o_dc;
+        if (A.dlog) A.dlog[3 * s + g] = o_dl;
+        if (A.grad) A.grad[3 * s + g] = o_gr;
     }
-
-    // lane group a < 3 stores component a, lane group 3 the density
-    const int64_t s = tile_base + c;
-    if (s >= n_eff) return;
-    if (g == 3) {
-        if (A.sigma) A.sigma[s] = sel ? sg : 0.0f;
-        return;
-    }
-    const float o_dc = (g == 0) ? dc[0] : (g == 1) ? dc[1] : dc[2];
-    const float o_dl = (g == 0) ? dl[0] : (g == 1) ? dl[1] : dl[2];
-    const float o_gr = (g == 0) ? gr[0] : (g == 1) ? gr[1] : gr[2];
-    if (A.dlog_canonical) A.dlog_canonical[3 * s + g] = o_dc;
-    if (A.dlog) A.dlog[3 * s + g] = o_dl;
-    if (A.grad) A.grad[3 * s + g] = o_gr;
-}
-
-template <typename W, bool TE, bool F16, bool TEMPORAL, int THREADS>
-__global__ __launch_bounds__(THREADS) void density_gradient_kernel(GradArgs A)
-{
-    using Elem = typename W::Elem;
-    constexpr int WAVES = THREADS / kWave;
-    constexpr int kPlaneWords = W::kPlane * (int)sizeof(Elem) / 16;
-    __shared__ __attribute__((aligned(16))) Elem lds[W::kPlane * (W::kSplit ? 2 : 1)];
-    __shared__ __attribute__((aligned(16))) uint32_t levels[8 * CED_MAX_LEVELS];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    int64_t n = A.n;
-    if (A.n_dev) {
-        const int64_t nd = *A.n_dev;
-        n = nd < n ? nd : n;
-    }
-    const int64_t n_tiles = (n + 15) / 16;
-    if ((int64_t)blockIdx.x * WAVES >= n_tiles) return;                 // workgroup-uniform
-
-    const Elem *const blob = reinterpret_cast<const Elem *>(A.weights);
-    stage<THREADS>(lds, blob, kPlaneWords, tid);
-    if constexpr (W::kSplit) stage<THREADS>(lds + W::kPlane, blob + A.lo_halves, kPlaneWords, tid);
-    if (tid < CED_MAX_LEVELS)
-        store_level(levels + tid * 8, make_level(A.scale[tid], A.res[tid], A.offset[tid], A.size[tid], A.hashed[tid],
-                                                 EntryBytes<F16, TEMPORAL>::value));
-    __syncthreads();
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + (tid >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * WAVES)
-        gradient_tile<W, TE, F16, TEMPORAL>(A, opaque(lds), levels, tile * 16, n, lane);
-}
+};
 
 // the motion network and mlp_base, adjacent at the start of every blob
 template <bool TE> using GradF32 = F32Weights<Blob<TE>::H0>;
 template <bool TE, bool SPLIT, bool K32> using GradHalf = HalfWeights<HalfBlob<TE>::H0 * kFragHalves, SPLIT, K32>;
 
-template <typename W, bool TE, bool F16, bool TEMPORAL> static void launch_gradient_kernel(const GradArgs &A, int max_workgroups, void *stream)
-{
-    constexpr int THREADS = 512, waves = THREADS / 64;
-    const int64_t n_tiles = (A.n + 15) / 16;
-    int64_t blocks = (n_tiles + waves - 1) / waves;
-    const int64_t cap = max_workgroups > 0 ? max_workgroups : (int64_t)kFieldBlocksDefault;   // one resident workgroup per CU
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((density_gradient_kernel<W, TE, F16, TEMPORAL, THREADS>), dim3((unsigned)blocks), dim3(THREADS), 0,
-                       (hipStream_t)stream, A);
-}
-
 template <bool TE, bool F16, bool TEMPORAL> static void launch_gradient_table(const ced_field_desc *d, const GradArgs &A, void *stream)
 {
+    using Op = GradientOp<TE, F16, TEMPORAL>;
     const int mw = d->max_workgroups;
     if (d->mlp_precision == CED_MLP_F32 || d->mlp_precision == CED_MLP_F32_HEAD16X2)
-        launch_gradient_kernel<GradF32<TE>, TE, F16, TEMPORAL>(A, mw, stream);
+        launch_tiles<Op, GradF32<TE>, 1>(A, mw, stream);
     else if (d->mlp_precision == CED_MLP_F16)
-        launch_gradient_kernel<GradHalf<TE, false, false>, TE, F16, TEMPORAL>(A, mw, stream);
+        launch_tiles<Op, GradHalf<TE, false, false>, 1>(A, mw, stream);
     else if constexpr (!TE && !TEMPORAL)                                 // half_layout_k32: the blob has the K = 32 placements
-        launch_gradient_kernel<GradHalf<TE, true, true>, TE, F16, TEMPORAL>(A, mw, stream);
+        launch_tiles<Op, GradHalf<TE, true, true>, 1>(A, mw, stream);
     else
-        launch_gradient_kernel<GradHalf<TE, true, false>, TE, F16, TEMPORAL>(A, mw, stream);
+        launch_tiles<Op, GradHalf<TE, true, false>, 1>(A, mw, stream);
 }
 
-// validates the descriptor, fills A from it and launches
+// validates the hash table, fills A from the descriptor and launches
 static int launch_gradient(const ced_field_desc *d, GradArgs &A, const char *who, void *stream)
 {
     const ced_hash_desc &h = d->hash;
+    const int rc = validate_hash(&h, who);
+    if (rc) return rc;
     CED_REQUIRE(h.n_levels == CED_MAX_LEVELS, "%s: the kernel needs n_levels == 16 (got %d)", who, h.n_levels);
     CED_REQUIRE(h.total_entries * (uint64_t)((h.table_dtype ? 4 : 8) * (h.temporal ? 4 : 1)) < (1ull << 32),
                 "%s: hash table larger than 4 GiB", who);
@@ -374,30 +334,15 @@ static int launch_gradient(const ced_field_desc *d, GradArgs &A, const char *who
     return check_launch(who);
 }
 
-static int validate_gradient(const ced_field_desc *desc, int64_t n, const char *who)
-{
-    int rc = validate_desc(desc, who);
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "%s: n < 0", who);
-    return CED_OK;
-}
-
 }  // namespace ced
 
 extern "C" int ced_field_density_gradient(const ced_field_desc *desc, int64_t n, const float *positions, const float *t,
                                           float *sigma, float *grad, float *dlog, float *dlog_canonical, void *stream)
 {
     const char *who = "field_density_gradient";
-    int rc = ced::validate_gradient(desc, n, who);
-    if (rc) return rc;
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(positions && t, "%s: null positions/t", who);
-    CED_REQUIRE(sigma || grad || dlog || dlog_canonical, "%s: no output requested", who);
-    rc = ced::validate_hash(&desc->hash, who);
-    if (rc) return rc;
     ced::GradArgs A{};
-    A.n = n;
-    A.pos = positions; A.t = t;
+    const int rc = ced::point_samples(desc, n, positions, t, sigma || grad || dlog || dlog_canonical, who, A.src);
+    if (rc || n == 0) return rc;
     A.sigma = sigma; A.grad = grad; A.dlog = dlog; A.dlog_canonical = dlog_canonical;
     return ced::launch_gradient(desc, A, who, stream);
 }
@@ -408,19 +353,10 @@ extern "C" int ced_field_density_gradient_rays(const ced_field_desc *desc, int64
                                                float *grad, float *dlog, float *dlog_canonical, void *stream)
 {
     const char *who = "field_density_gradient_rays";
-    int rc = ced::validate_gradient(desc, n, who);
-    if (rc) return rc;
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && timestamps, "%s: null pointer", who);
-    CED_REQUIRE(sigma || grad || dlog || dlog_canonical, "%s: no output requested", who);
-    rc = ced::validate_hash(&desc->hash, who);
-    if (rc) return rc;
     ced::GradArgs A{};
-    A.n = n;
-    A.n_dev = n_dev;
-    A.rays_o = rays_o; A.rays_d = rays_d; A.ray_idx = ray_indices;
-    A.t0 = t_starts; A.t1 = t_ends; A.timestamps = timestamps;
-    A.rays_mode = 1; A.t_per_ray = t_per_ray ? 1 : 0;
+    const int rc = ced::ray_samples(desc, n, n_dev, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray,
+                                    sigma || grad || dlog || dlog_canonical, who, A.src);
+    if (rc || n == 0) return rc;
     A.sigma = sigma; A.grad = grad; A.dlog = dlog; A.dlog_canonical = dlog_canonical;
     return ced::launch_gradient(desc, A, who, stream);
 }

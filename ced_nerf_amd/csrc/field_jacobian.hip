@@ -13,11 +13,12 @@
 // tangent is zeroed wherever the PRIMAL pre-activation is not > 0, and the output applies the tanh's derivative
 // 1 - th^2 to the fine offsets.
 //
-// Shape: field_move.hip's (tile_kernel of field_move_device.hpp with the ops JacobianOp, NewtonOp and VelocityOp: persistent workgroups
-// of 512 threads, the motion network's layers staged into LDS once), with ONE 16-sample primal tile per wave iteration
-// instead of two: primal + four tangents are five operand tiles and five
-// accumulator tiles (80 + 80 registers on the fp32 chain), which fit the 256 registers of a wave at two waves per SIMD
-// without scratch; two primal tiles would not.
+// Shape: field_move.hip's (tile_kernel of field_move_device.hpp with the ops JacobianOp, NewtonOp and VelocityOp:
+// persistent workgroups of 512 threads, the motion network's layers staged into LDS once), with ONE 16-sample primal tile
+// per wave iteration instead of two: primal + four tangents are five operand tiles and five accumulator tiles (80 + 80
+// registers on the fp32 chain), which fit the 256 registers of a wave at two waves per SIMD without scratch; two primal
+// tiles would not.  VelocityOp reads its rows from that header's SampleSrc, as MoveOp does; the two velocity entries fill it
+// through point_samples / ray_samples.
 #include "field_jacobian_device.hpp"
 
 namespace ced {
@@ -157,13 +158,7 @@ struct NewtonOp : TileOp {
 
 // ---- ced_field_velocity, ced_field_velocity_rays: v = -(I + J_x)^-1 d move / dt (include/cednerf_hip.h states it) ----------
 struct VelArgs {
-    int64_t n;
-    const int64_t *n_dev;                             // optional device-side sample count (<= n)
-    const float *pos, *t;                             // explicit mode
-    const float *rays_o, *rays_d;                     // rays mode: load_samples' fields
-    const int64_t *ray_idx;
-    const float *t0, *t1, *timestamps;
-    int rays_mode, t_per_ray;
+    SampleSrc src;
     float *velocity, *det;                            // [n,3], [n]; any may be null
     uint8_t *valid;                                   // [n], may be null
     float moving_step;
@@ -199,16 +194,15 @@ __device__ __forceinline__ void velocity_store(const VelArgs &A, const float (&J
     }
 }
 
-struct VelocityOp : TileOp {
+struct VelocityOp : SampleOp {
     using Args = VelArgs;
-    __device__ __forceinline__ static int64_t rows(const VelArgs &A) { return sample_count(A.n, A.n_dev); }
     template <typename W, int NP>
     __device__ __forceinline__ static void tile(const VelArgs &A, const Shared &, const typename W::Elem *w, int64_t tile_base,
                                                 int64_t n_eff, int lane)
     {
         const int g = lane >> 4, c = lane & 15;
         float px[NP][3], tq[NP], mv[NP][3], J[NP][12];
-        load_samples<NP>(A, tile_base, n_eff, c, px, tq);
+        load_samples<NP>(A.src, tile_base, n_eff, c, px, tq);
         motion_move_jacobian<W, NP>(w, lane, px, RowTime<NP>{ tq }, A.moving_step, A.use_div, mv, J);
         velocity_store<NP>(A, J, tile_base, n_eff, g, c);
     }
@@ -251,15 +245,9 @@ extern "C" int ced_field_track_newton(const ced_field_desc *desc, int64_t n_poin
 extern "C" int ced_field_velocity(const ced_field_desc *desc, int64_t n, const float *positions, const float *t, float *velocity,
                                   float *det, uint8_t *valid, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_velocity");
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "field_velocity: n < 0");
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(positions && t, "field_velocity: null positions/t");
-    CED_REQUIRE(velocity || det || valid, "field_velocity: no output requested");
     ced::VelArgs A{};
-    A.n = n;
-    A.pos = positions; A.t = t;
+    const int rc = ced::point_samples(desc, n, positions, t, velocity || det || valid, "field_velocity", A.src);
+    if (rc || n == 0) return rc;
     A.velocity = velocity; A.det = det; A.valid = valid;
     return ced::launch_motion<ced::VelocityOp, 1>(desc, A, "field_velocity", stream);
 }
@@ -269,18 +257,10 @@ extern "C" int ced_field_velocity_rays(const ced_field_desc *desc, int64_t n, co
                                        const float *t_ends, const float *timestamps, int32_t t_per_ray, float *velocity,
                                        float *det, uint8_t *valid, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_velocity_rays");
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "field_velocity_rays: n < 0");
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && timestamps, "field_velocity_rays: null pointer");
-    CED_REQUIRE(velocity || det || valid, "field_velocity_rays: no output requested");
     ced::VelArgs A{};
-    A.n = n;
-    A.n_dev = n_dev;
-    A.rays_o = rays_o; A.rays_d = rays_d; A.ray_idx = ray_indices;
-    A.t0 = t_starts; A.t1 = t_ends; A.timestamps = timestamps;
-    A.rays_mode = 1; A.t_per_ray = t_per_ray ? 1 : 0;
+    const int rc = ced::ray_samples(desc, n, n_dev, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray,
+                                    velocity || det || valid, "field_velocity_rays", A.src);
+    if (rc || n == 0) return rc;
     A.velocity = velocity; A.det = det; A.valid = valid;
     return ced::launch_motion<ced::VelocityOp, 1>(desc, A, "field_velocity_rays", stream);
 }

@@ -18,6 +18,8 @@
 //
 // Shape: one network per 32-sample wave tile, workgroups persistent over tiles -- tile_kernel of field_move_device.hpp,
 // which every entry here instantiates with an op (MoveOp, TrackOp, RgbOp) and the weights of the descriptor's arithmetic.
+// MoveOp reads its rows from the SampleSrc of that header, which the two move entries fill through point_samples /
+// ray_samples, the argument checks every per-sample entry makes.
 // Only that network's layers are staged into LDS (motion: 44 KB fp32 or split fp16, 22 KB fp16; head: 28 KB / 14 KB), not
 // the fused kernel's 86 KB, so two 512-thread workgroups share a CU.
 #include "ced_common.hpp"
@@ -29,13 +31,7 @@
 namespace ced {
 
 struct MoveArgs {
-    int64_t n;
-    const int64_t *n_dev;                             // optional device-side sample count (<= n)
-    const float *pos, *t;                             // explicit mode
-    const float *rays_o, *rays_d;                     // rays mode
-    const int64_t *ray_idx;
-    const float *t0, *t1, *timestamps;
-    int rays_mode, t_per_ray;
+    SampleSrc src;
     float *x_move, *move, *x_norm;                    // [n,3] each, any may be null
     uint8_t *selector;                                // [n], may be null
     float aabb[6];
@@ -96,9 +92,8 @@ __device__ __forceinline__ void move_store(const MoveArgs &A, const float (&mv)[
 }
 
 // ---- ced_field_move, ced_field_move_rays --------------------------------------------------------------------------------
-struct MoveOp : TileOp {
+struct MoveOp : SampleOp {
     using Args = MoveArgs;
-    __device__ __forceinline__ static int64_t rows(const MoveArgs &A) { return sample_count(A.n, A.n_dev); }
 
     // eval frames: one timestamp for every sample, its two Frequency features of this lane computed once per workgroup
     // (field_kernel.hpp); only the fp32 chain asks for features
@@ -108,11 +103,11 @@ struct MoveOp : TileOp {
     };
     template <typename W> __device__ __forceinline__ static Shared prologue(const MoveArgs &A, int lane)
     {
-        Shared sh{ A.rays_mode && !A.t_per_ray, { 0.0f, 0.0f } };
+        Shared sh{ A.src.rays_mode && !A.src.t_per_ray, { 0.0f, 0.0f } };
         if constexpr (!W::kHalf) {
             if (sh.on) {
                 const int g = lane >> 4;
-                const float t_all = A.timestamps[0];
+                const float t_all = A.src.timestamps[0];
 #pragma unroll
                 for (int S = 6; S < 8; ++S) sh.feat[S - 6] = det_sinpi_phase(t_all * (float)(1 << (2 * (S & 1) + (g >> 1))), g & 1);
             }
@@ -141,7 +136,7 @@ struct MoveOp : TileOp {
     {
         const int g = lane >> 4, c = lane & 15;
         float px[NT][3], tq[NT], mv[NT][3];
-        load_samples<NT>(A, tile_base, n_eff, c, px, tq);
+        load_samples<NT>(A.src, tile_base, n_eff, c, px, tq);
         motion_move<W, NT>(w, lane, px, Time<NT>{ tq, sh }, A.moving_step, A.use_div, mv);
         move_store<NT>(A, mv, px, tile_base, n_eff, g, c);
     }
@@ -324,15 +319,9 @@ template <bool BCAST> static int launch_rgb(const ced_field_desc *desc, RgbArgs 
 extern "C" int ced_field_move(const ced_field_desc *desc, int64_t n, const float *positions, const float *t, float *x_move,
                               float *move, float *x_norm, uint8_t *selector, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_move");
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "field_move: n < 0");
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(positions && t, "field_move: null positions/t");
-    CED_REQUIRE(x_move || move || x_norm || selector, "field_move: no output requested");
     ced::MoveArgs A{};
-    A.n = n;
-    A.pos = positions; A.t = t;
+    const int rc = ced::point_samples(desc, n, positions, t, x_move || move || x_norm || selector, "field_move", A.src);
+    if (rc || n == 0) return rc;
     A.x_move = x_move; A.move = move; A.x_norm = x_norm; A.selector = selector;
     return ced::launch_move(desc, A, "field_move", stream);
 }
@@ -342,18 +331,10 @@ extern "C" int ced_field_move_rays(const ced_field_desc *desc, int64_t n, const 
                                    const float *t_ends, const float *timestamps, int32_t t_per_ray, float *move,
                                    float *x_norm, void *stream)
 {
-    int rc = ced::validate_desc(desc, "field_move_rays");
-    if (rc) return rc;
-    CED_REQUIRE(n >= 0, "field_move_rays: n < 0");
-    if (n == 0) return CED_OK;
-    CED_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && timestamps, "field_move_rays: null pointer");
-    CED_REQUIRE(move || x_norm, "field_move_rays: no output requested");
     ced::MoveArgs A{};
-    A.n = n;
-    A.n_dev = n_dev;
-    A.rays_o = rays_o; A.rays_d = rays_d; A.ray_idx = ray_indices;
-    A.t0 = t_starts; A.t1 = t_ends; A.timestamps = timestamps;
-    A.rays_mode = 1; A.t_per_ray = t_per_ray ? 1 : 0;
+    const int rc = ced::ray_samples(desc, n, n_dev, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray,
+                                    move || x_norm, "field_move_rays", A.src);
+    if (rc || n == 0) return rc;
     A.move = move; A.x_norm = x_norm;
     return ced::launch_move(desc, A, "field_move_rays", stream);
 }

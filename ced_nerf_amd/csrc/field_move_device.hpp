@@ -1,15 +1,19 @@
 // Device code of the motion network and of the colour head on their own, shared by field_move.hip (ced_field_move,
-// ced_field_move_inverse, ced_field_track, ced_field_rgb) and field_jacobian.hip (ced_field_move_jacobian, the Newton
-// inverse and ced_field_velocity, whose rays entry reads its samples through the loader of ced_field_move_rays below).
+// ced_field_move_inverse, ced_field_track, ced_field_rgb), field_jacobian.hip (ced_field_move_jacobian, the Newton
+// inverse, ced_field_velocity) and field_density_gradient.hip (ced_field_density_gradient).
 //
-// Every kernel of the two files is tile_kernel<Op, W, NT, THREADS>.  The skeleton fixes, once: the wave's tiles of
+// Every kernel of the three files is tile_kernel<Op, W, NT, THREADS>.  The skeleton fixes, once: the wave's tiles of
 // 16 * NT rows (wave w of workgroup b takes tiles b * WAVES + w, + gridDim.x * WAVES, ...), the workgroup-uniform early
-// return, the staging of one network's layers into LDS and its barrier, and the opaque LDS base of each tile.
+// return, the staging of the layers into LDS and its barrier, and the opaque LDS base of each tile.
 //   W, the weights (F32Weights, HalfWeights): the LDS element type, the size of one plane, whether a plane of remainders
 //      follows it (in LDS directly behind, in the blob A.lo_halves after A.weights), whether the blob has the K = 32
 //      placements.  A tile body gets the base of the first plane.
-//   Op, what one tile does: its Args (the kernel's argument; n, weights and lo_halves are read here), tile(), and -- where
-//      TileOp's defaults do not fit -- the row count and a once-per-workgroup prologue whose result every tile receives.
+//   Op, what one tile does: its Args (the kernel's argument; weights and lo_halves are read here), tile(), and -- where
+//      TileOp's defaults do not fit -- the row count, what else the workgroup puts into LDS before the barrier, a
+//      once-per-workgroup prologue whose result every tile receives, and how many workgroups share a CU.
+// The per-sample entries (move, velocity, density gradient; each with a rays twin) read their rows from one SampleSrc, the
+// first member of their Args: sample_count / load_samples on the device, point_samples / ray_samples -- the entries'
+// argument checks, stated once -- on the host.
 // Below them: the encode -> four layers -> move chain in the three arithmetics (motion_move), the K = 32 blocks on the
 // K = 16 instruction, the rows a solver keeps in registers, and the launch / validation helpers of the entries.  One
 // statement of the arithmetic, so every kernel built on it computes ced_field_move's bits.
@@ -20,6 +24,18 @@
 #include "field_kernel.hpp"
 
 namespace ced {
+
+// Where a per-sample entry takes its rows from: positions and times given one by one, or the samples of a ray batch as
+// ced_field_forward_rays reads them.  The first member of MoveArgs, VelArgs and GradArgs.
+struct SampleSrc {
+    int64_t n;
+    const int64_t *n_dev;                             // optional device-side sample count (<= n)
+    const float *pos, *t;                             // explicit mode
+    const float *rays_o, *rays_d;                     // rays mode
+    const int64_t *ray_idx;
+    const float *t0, *t1, *timestamps;
+    int rays_mode, t_per_ray;
+};
 
 // the inverse of the warp by fixed-point iteration (ced_field_move_inverse, ced_field_track)
 struct TrackArgs {
@@ -63,10 +79,14 @@ template <int HALVES, bool SPLIT, bool K32> struct HalfWeights {   // fp16 fragm
     static constexpr bool kHalf = true, kSplit = SPLIT, kK32 = K32;
 };
 
-// what an op leaves to the skeleton unless it says otherwise: A.n rows, nothing computed once per workgroup
+// what an op leaves to the skeleton unless it says otherwise: A.n rows, nothing but the weights in LDS, nothing computed
+// once per workgroup, two workgroups per CU
 struct TileOp {
     struct Shared {};
+    static constexpr int kPerCu = 2;
+    template <typename Args> static int64_t capacity(const Args &A) { return A.n; }       // the rows the grid is sized for
     template <typename Args> __device__ __forceinline__ static int64_t rows(const Args &A) { return A.n; }
+    template <typename Args> __device__ __forceinline__ static void fill_lds(const Args &, int) {}    // before the barrier
     template <typename W, typename Args> __device__ __forceinline__ static Shared prologue(const Args &, int) { return {}; }
 };
 
@@ -97,6 +117,7 @@ __global__ __launch_bounds__(THREADS) void tile_kernel(typename Op::Args A)
     const Elem *const blob = reinterpret_cast<const Elem *>(A.weights);
     stage<THREADS>(lds, blob, kPlaneWords, tid);
     if constexpr (W::kSplit) stage<THREADS>(lds + W::kPlane, blob + A.lo_halves, kPlaneWords, tid);
+    Op::fill_lds(A, tid);
     __syncthreads();
 
     const typename Op::Shared shared = Op::template prologue<W>(A, lane);
@@ -120,20 +141,25 @@ __device__ __forceinline__ void load_points(const float *pos, const float *t, in
     }
 }
 
-// the rows of a rays entry: n, or the device-side count where one is given and smaller
-__device__ __forceinline__ int64_t sample_count(int64_t n, const int64_t *n_dev)
+// the rows of a per-sample entry: n, or the device-side count where one is given and smaller
+__device__ __forceinline__ int64_t sample_count(const SampleSrc &A)
 {
-    if (!n_dev) return n;
-    const int64_t nd = *n_dev;
-    return nd < n ? nd : n;
+    if (!A.n_dev) return A.n;
+    const int64_t nd = *A.n_dev;
+    return nd < A.n ? nd : A.n;
 }
 
-// Position and time of sample c of each 16-sample column tile of an op whose Args carry MoveArgs' sample fields (pos, t,
-// rays_o, rays_d, ray_idx, t0, t1, timestamps, rays_mode, t_per_ray): the expressions of field_kernel.hpp / field_half.hip
-// (rays mode: o + (d * (t0 + t1)) / 2 in fp32; a negative ray index is evaluated on ray 0 at distance 0).  A ragged last
-// tile repeats the last sample (never stored).
-template <int NT, typename Args>
-__device__ __forceinline__ void load_samples(const Args &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[NT][3],
+// an op on the rows of a SampleSrc, the member `src` of its Args
+struct SampleOp : TileOp {
+    template <typename Args> static int64_t capacity(const Args &A) { return A.src.n; }
+    template <typename Args> __device__ __forceinline__ static int64_t rows(const Args &A) { return sample_count(A.src); }
+};
+
+// Position and time of sample c of each 16-sample column tile: load_points, or the expressions of field_kernel.hpp /
+// field_half.hip (rays mode: o + (d * (t0 + t1)) / 2 in fp32; a negative ray index is evaluated on ray 0 at distance 0).
+// A ragged last tile repeats the last sample (never stored).
+template <int NT>
+__device__ __forceinline__ void load_samples(const SampleSrc &A, int64_t tile_base, int64_t n_eff, int c, float (&px)[NT][3],
                                              float (&tq)[NT])
 {
     if (!A.rays_mode) return load_points<NT>(A.pos, A.t, n_eff, tile_base, c, px, tq);
@@ -481,15 +507,15 @@ __device__ __forceinline__ void track_store(const TrackArgs &A, const TrackRows<
 }
 
 // Persistent launch of Op on the weights W, NT 16-row tiles per wave: workgroups of 512 threads, enough for the tiles, at
-// most two per CU (the descriptor's max_workgroups caps it).
+// most Op::kPerCu per CU (the descriptor's max_workgroups caps it).
 template <typename Op, typename W, int NT>
 static void launch_tiles(const typename Op::Args &A, int max_workgroups, void *stream)
 {
-    constexpr int THREADS = 512, per_cu = 2;
-    const int64_t n_tiles = (A.n + 16 * NT - 1) / (16 * NT);
+    constexpr int THREADS = 512;
+    const int64_t n_tiles = (Op::capacity(A) + 16 * NT - 1) / (16 * NT);
     constexpr int waves = THREADS / 64;
     int64_t blocks = (n_tiles + waves - 1) / waves;
-    const int64_t cap = max_workgroups > 0 ? max_workgroups : (int64_t)kFieldBlocksDefault * per_cu;
+    const int64_t cap = max_workgroups > 0 ? max_workgroups : (int64_t)kFieldBlocksDefault * Op::kPerCu;
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL((tile_kernel<Op, W, NT, THREADS>), dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
 }
@@ -532,6 +558,40 @@ static int validate_desc(const ced_field_desc *d, const char *who)
                 "%s: packed_floats=%llu does not match this configuration (mlp_precision %d)", who,
                 (unsigned long long)d->packed_floats, d->mlp_precision);
     CED_REQUIRE(d->max_workgroups >= 0 && d->max_workgroups <= 65536, "%s: max_workgroups=%d", who, d->max_workgroups);
+    return CED_OK;
+}
+
+// What the per-sample entries check before they look at their outputs, in this order: the descriptor, n < 0, n == 0 -- the
+// caller returns CED_OK on it before any pointer is looked at --, null inputs, no output requested.  They fill S.
+static int point_samples(const ced_field_desc *d, int64_t n, const float *positions, const float *t, bool any_output,
+                         const char *who, SampleSrc &S)
+{
+    int rc = validate_desc(d, who);
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "%s: n < 0", who);
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(positions && t, "%s: null positions/t", who);
+    CED_REQUIRE(any_output, "%s: no output requested", who);
+    S.n = n;
+    S.pos = positions; S.t = t;
+    return CED_OK;
+}
+
+static int ray_samples(const ced_field_desc *d, int64_t n, const int64_t *n_dev, const float *rays_o, const float *rays_d,
+                       const int64_t *ray_indices, const float *t_starts, const float *t_ends, const float *timestamps,
+                       int32_t t_per_ray, bool any_output, const char *who, SampleSrc &S)
+{
+    int rc = validate_desc(d, who);
+    if (rc) return rc;
+    CED_REQUIRE(n >= 0, "%s: n < 0", who);
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(rays_o && rays_d && ray_indices && t_starts && t_ends && timestamps, "%s: null pointer", who);
+    CED_REQUIRE(any_output, "%s: no output requested", who);
+    S.n = n;
+    S.n_dev = n_dev;
+    S.rays_o = rays_o; S.rays_d = rays_d; S.ray_idx = ray_indices;
+    S.t0 = t_starts; S.t1 = t_ends; S.timestamps = timestamps;
+    S.rays_mode = 1; S.t_per_ray = t_per_ray ? 1 : 0;
     return CED_OK;
 }
 

@@ -222,18 +222,58 @@ def hash_encode_backward_temporal(desc: _lib.HashDesc, x: torch.Tensor, t: torch
     return grad_table
 
 
-def field_forward(desc: _lib.FieldDesc, positions, t, directions=None, want_geo=False):
+def _points(positions, t, who) -> int:
+    """The rows of an op on positions [n,3] and t [n] (any shape of n elements), checked -> n."""
     _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
     n = positions.shape[0]
-    assert positions.shape == (n, 3) and t.numel() == n
-    dev = positions.device
-    rgb = None
+    if positions.shape != (n, 3) or t.numel() != n:
+        raise ValueError(f"{who}: positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
+    return n
+
+
+def _ray_samples(rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray):
+    """The samples of a ray batch, checked -> (n, their ctypes arguments in the C order: rays_o .. t_per_ray)."""
+    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
+    _chk(ray_indices, torch.int64, "ray_indices")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
+    _chk(timestamps, torch.float32, "timestamps")
+    n = ray_indices.shape[0]
+    if t_starts.shape != (n,) or t_ends.shape != (n,):
+        raise ValueError(f"t_starts [n], t_ends [n] for ray_indices [n]: got {list(t_starts.shape)}, {list(t_ends.shape)}, "
+                         f"{list(ray_indices.shape)}")
+    if t_per_ray and timestamps.numel() != rays_o.shape[0]:
+        raise ValueError("per-ray timestamps must have one entry per ray")
+    return n, (_p(rays_o), _p(rays_d), _p(ray_indices), _p(t_starts), _p(t_ends), _p(timestamps), int(bool(t_per_ray)))
+
+
+def _outputs(spec, n, dev, want, out, who):
+    """The output buffers of an op, one per (name, trailing shape, dtype) of spec, None where not computed: fresh ones where
+    `want` says so, or the given `out` buffers, checked."""
+    if out is None and len(want) != len(spec):
+        raise ValueError(f"{who}: want= takes one flag per output {tuple(name for name, _, _ in spec)}")
+    outs = list(out) if out is not None else [torch.empty((n,) + shape, device=dev, dtype=dtype) if w else None
+                                              for (_, shape, dtype), w in zip(spec, want)]
+    if len(outs) != len(spec) or all(o is None for o in outs):
+        raise ValueError(f"{who}: no output requested")
+    if out is not None:
+        for i, (o, (_, shape, dtype)) in enumerate(zip(outs, spec)):
+            _chk(o, dtype, f"out[{i}]", allow_none=True)
+            if o is not None and o.shape != (n,) + shape:
+                raise ValueError(f"{who}: out[{i}] must be {[n, *shape]}, got {list(o.shape)}")
+    return outs
+
+
+_F32_3, _F32_1 = ((3,), torch.float32), ((), torch.float32)
+_FORWARD = (("rgb", *_F32_3), ("sigma", *_F32_1), ("geo", (15,), torch.float32))
+_MOVE = (("x_move", *_F32_3), ("move", *_F32_3), ("x_norm", *_F32_3), ("selector", (), torch.bool))
+
+
+def field_forward(desc: _lib.FieldDesc, positions, t, directions=None, want_geo=False):
+    n = _points(positions, t, "field_forward")
     if directions is not None:
         _chk(directions, torch.float32, "directions")
         assert directions.shape == positions.shape, f"{positions.shape} v.s. {directions.shape}"
-        rgb = torch.empty((n, 3), device=dev, dtype=torch.float32)
-    sigma = torch.empty((n,), device=dev, dtype=torch.float32)
-    geo = torch.empty((n, 15), device=dev, dtype=torch.float32) if want_geo else None
+    rgb, sigma, geo = _outputs(_FORWARD, n, positions.device, (directions is not None, True, want_geo), None, "field_forward")
     rc = _lib.lib().ced_field_forward(C.byref(desc), n, _p(positions), _p(t), _p(directions), _p(rgb), _p(sigma),
                                       _p(geo), _stream())
     _lib.check(rc, "field_forward")
@@ -243,21 +283,11 @@ def field_forward(desc: _lib.FieldDesc, positions, t, directions=None, want_geo=
 def field_forward_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps,
                        t_per_ray: bool, want_rgb: bool, n_dev: Optional[torch.Tensor] = None):
     """n_dev: optional device int64 scalar; the kernel evaluates min(len(ray_indices), n_dev) samples."""
-    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
-    _chk(ray_indices, torch.int64, "ray_indices")
-    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
-    _chk(timestamps, torch.float32, "timestamps")
-    n = ray_indices.shape[0]
-    assert t_starts.shape == (n,) and t_ends.shape == (n,)
-    if t_per_ray:
-        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
-    dev = rays_o.device
-    rgb = torch.empty((n, 3), device=dev, dtype=torch.float32) if want_rgb else None
-    sigma = torch.empty((n,), device=dev, dtype=torch.float32)
+    n, rays = _ray_samples(rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray)
+    rgb, sigma = _outputs(_FORWARD[:2], n, rays_o.device, (want_rgb, True), None, "field_forward_rays")
     with profiling.span("field", n):
-        rc = _lib.lib().ced_field_forward_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices),
-                                               _p(t_starts), _p(t_ends), _p(timestamps), int(bool(t_per_ray)),
-                                               int(bool(want_rgb)), _p(rgb), _p(sigma), _stream())
+        rc = _lib.lib().ced_field_forward_rays(C.byref(desc), n, _p(n_dev), *rays, int(bool(want_rgb)), _p(rgb), _p(sigma),
+                                               _stream())
     _lib.check(rc, "field_forward_rays")
     return rgb, sigma
 
@@ -265,42 +295,21 @@ def field_forward_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_star
 def field_move(desc: _lib.FieldDesc, positions, t, want=(True, True, True, True)):
     """ced_field_move: query_move plus the normalisation that follows it.  want = which of (x_move [n,3], move [n,3],
     x_norm [n,3], selector [n] bool) to compute; the others come back as None."""
-    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
-    n = positions.shape[0]
-    assert positions.shape == (n, 3) and t.numel() == n
-    if not any(want):
-        raise ValueError("field_move: no output requested")
-    dev = positions.device
-    outs = [torch.empty((n, 3), device=dev, dtype=torch.float32) if w else None for w in want[:3]]
-    sel = torch.empty((n,), device=dev, dtype=torch.bool) if want[3] else None
-    rc = _lib.lib().ced_field_move(C.byref(desc), n, _p(positions), _p(t), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+    n = _points(positions, t, "field_move")
+    x_move, move, x_norm, sel = _outputs(_MOVE, n, positions.device, want, None, "field_move")
+    rc = _lib.lib().ced_field_move(C.byref(desc), n, _p(positions), _p(t), _p(x_move), _p(move), _p(x_norm),
                                    _p(_as_u8(sel)), _stream())
     _lib.check(rc, "field_move")
-    return outs[0], outs[1], outs[2], sel
+    return x_move, move, x_norm, sel
 
 
 def field_move_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray: bool,
                     want_x_norm: bool = False, n_dev: Optional[torch.Tensor] = None, out=None):
     """ced_field_move_rays: (move [n,3], x_norm [n,3] or None) at the sample positions of `field_forward_rays`.
     n_dev as there; out = (move, x_norm) buffers to write into instead of fresh ones."""
-    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
-    _chk(ray_indices, torch.int64, "ray_indices")
-    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
-    _chk(timestamps, torch.float32, "timestamps")
-    n = ray_indices.shape[0]
-    assert t_starts.shape == (n,) and t_ends.shape == (n,)
-    if t_per_ray:
-        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
-    dev = rays_o.device
-    if out is not None:
-        move, x_norm = out
-        _chk(move, torch.float32, "out[0]"); _chk(x_norm, torch.float32, "out[1]", allow_none=True)
-        assert move.shape == (n, 3) and (x_norm is None or x_norm.shape == (n, 3))
-    else:
-        move = torch.empty((n, 3), device=dev, dtype=torch.float32)
-        x_norm = torch.empty((n, 3), device=dev, dtype=torch.float32) if want_x_norm else None
-    rc = _lib.lib().ced_field_move_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices), _p(t_starts),
-                                        _p(t_ends), _p(timestamps), int(bool(t_per_ray)), _p(move), _p(x_norm), _stream())
+    n, rays = _ray_samples(rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray)
+    move, x_norm = _outputs(_MOVE[1:3], n, rays_o.device, (True, want_x_norm), out, "field_move_rays")
+    rc = _lib.lib().ced_field_move_rays(C.byref(desc), n, _p(n_dev), *rays, _p(move), _p(x_norm), _stream())
     _lib.check(rc, "field_move_rays")
     return move, x_norm
 
@@ -384,31 +393,15 @@ def field_move_jacobian(desc: _lib.FieldDesc, positions, t, want=(True, True)):
     """ced_field_move_jacobian: (move [n,3], jac [n,3,4]) at positions [n,3], t [n], from one launch.  jac[r, a, b] =
     d move_a / d (x, y, z, t)_b by forward mode through the motion network in desc's mlp_precision; `move` has
     `field_move`'s bits.  want = which of the two to compute; the other comes back as None."""
-    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
-    n = positions.shape[0]
-    if positions.shape != (n, 3) or t.numel() != n:
-        raise ValueError(f"positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
-    if not any(want):
-        raise ValueError("field_move_jacobian: no output requested")
-    dev = positions.device
-    move = torch.empty((n, 3), device=dev, dtype=torch.float32) if want[0] else None
-    jac = torch.empty((n, 3, 4), device=dev, dtype=torch.float32) if want[1] else None
+    n = _points(positions, t, "field_move_jacobian")
+    move, jac = _outputs((_MOVE[1], ("jac", (3, 4), torch.float32)), n, positions.device, want, None, "field_move_jacobian")
     rc = _lib.lib().ced_field_move_jacobian(C.byref(desc), n, _p(positions), _p(t), _p(move), _p(jac), _stream())
     _lib.check(rc, "field_move_jacobian")
     return move, jac
 
 
 VELOCITY_OUTPUTS = ("velocity", "det", "valid")   # ced_field_velocity's outputs, in `want=` order
-
-
-def _velocity_outputs(n, dev, want, who):
-    if len(want) != len(VELOCITY_OUTPUTS):
-        raise ValueError(f"{who}: want= takes one flag per output {VELOCITY_OUTPUTS}")
-    if not any(want):
-        raise ValueError(f"{who}: no output requested")
-    return [torch.empty((n, 3), device=dev, dtype=torch.float32) if want[0] else None,
-            torch.empty((n,), device=dev, dtype=torch.float32) if want[1] else None,
-            torch.empty((n,), device=dev, dtype=torch.bool) if want[2] else None]
+_VELOCITY = (("velocity", *_F32_3), ("det", *_F32_1), ("valid", (), torch.bool))
 
 
 def field_velocity(desc: _lib.FieldDesc, positions, t, want=(True, True, True)):
@@ -416,11 +409,8 @@ def field_velocity(desc: _lib.FieldDesc, positions, t, want=(True, True, True)):
     velocity v = -(I + J_x)^-1 d move / dt of the material point that sits there, J being `field_move_jacobian`'s (its
     bits), det = det(I + J_x), valid = det >= 2^-20 and v finite; v is 0 where not valid (include/cednerf_hip.h states every
     operation).  want = which of the three to compute; the others come back as None."""
-    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
-    n = positions.shape[0]
-    if positions.shape != (n, 3) or t.numel() != n:
-        raise ValueError(f"positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
-    v, det, valid = _velocity_outputs(n, positions.device, want, "field_velocity")
+    n = _points(positions, t, "field_velocity")
+    v, det, valid = _outputs(_VELOCITY, n, positions.device, want, None, "field_velocity")
     rc = _lib.lib().ced_field_velocity(C.byref(desc), n, _p(positions), _p(t), _p(v), _p(det), _p(_as_u8(valid)), _stream())
     _lib.check(rc, "field_velocity")
     return v, det, valid
@@ -430,42 +420,16 @@ def field_velocity_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indices, t_sta
                         want=(True, True, True), n_dev: Optional[torch.Tensor] = None, out=None):
     """ced_field_velocity_rays: `field_velocity` at the sample positions of `field_forward_rays`.  n_dev as there; out =
     the three buffers (or None each) to write into instead of fresh ones, which then decides what is computed."""
-    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
-    _chk(ray_indices, torch.int64, "ray_indices")
-    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
-    _chk(timestamps, torch.float32, "timestamps")
-    n = ray_indices.shape[0]
-    assert t_starts.shape == (n,) and t_ends.shape == (n,)
-    if t_per_ray:
-        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
-    if out is not None:
-        outs = list(out)
-        if len(outs) != len(VELOCITY_OUTPUTS) or all(o is None for o in outs):
-            raise ValueError("field_velocity_rays: no output requested")
-        for i, (o, dt, shape) in enumerate(zip(outs, (torch.float32, torch.float32, torch.bool), ((n, 3), (n,), (n,)))):
-            _chk(o, dt, f"out[{i}]", allow_none=True)
-            assert o is None or o.shape == shape, (i, o.shape)
-    else:
-        outs = _velocity_outputs(n, rays_o.device, want, "field_velocity_rays")
-    v, det, valid = outs
-    rc = _lib.lib().ced_field_velocity_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices),
-                                            _p(t_starts), _p(t_ends), _p(timestamps), int(bool(t_per_ray)), _p(v), _p(det),
-                                            _p(_as_u8(valid)), _stream())
+    n, rays = _ray_samples(rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray)
+    v, det, valid = _outputs(_VELOCITY, n, rays_o.device, want, out, "field_velocity_rays")
+    rc = _lib.lib().ced_field_velocity_rays(C.byref(desc), n, _p(n_dev), *rays, _p(v), _p(det), _p(_as_u8(valid)), _stream())
     _lib.check(rc, "field_velocity_rays")
     return v, det, valid
 
 
 GRADIENT_OUTPUTS = ("sigma", "grad", "dlog", "dlog_canonical")   # ced_field_density_gradient's outputs, in `want=` order
+_GRADIENT = (("sigma", *_F32_1), ("grad", *_F32_3), ("dlog", *_F32_3), ("dlog_canonical", *_F32_3))
 EXP15 = float(np.float32(np.exp(15.0)))                             # trunc_exp's backward clamps there (3269017.25)
-
-
-def _gradient_outputs(n, dev, want, who):
-    if len(want) != len(GRADIENT_OUTPUTS):
-        raise ValueError(f"{who}: want= takes one flag per output {GRADIENT_OUTPUTS}")
-    if not any(want):
-        raise ValueError(f"{who}: no output requested")
-    return [torch.empty((n,) if i == 0 else (n, 3), device=dev, dtype=torch.float32) if w else None
-            for i, w in enumerate(want)]
 
 
 def field_density_gradient(desc: _lib.FieldDesc, positions, t, want=(True, True, True, True)):
@@ -474,11 +438,8 @@ def field_density_gradient(desc: _lib.FieldDesc, positions, t, want=(True, True,
     respect to the canonical point x + move(x, t), dlog = (I + J_x)^T dlog_canonical with respect to x, grad =
     min(sigma, e^15) * dlog; all zero outside the box (include/cednerf_hip.h states every operation).  want = which of
     the four to compute; the others come back as None."""
-    _chk(positions, torch.float32, "positions"); _chk(t, torch.float32, "t")
-    n = positions.shape[0]
-    if positions.shape != (n, 3) or t.numel() != n:
-        raise ValueError(f"positions [n,3], t [n]: got {list(positions.shape)}, {list(t.shape)}")
-    outs = _gradient_outputs(n, positions.device, want, "field_density_gradient")
+    n = _points(positions, t, "field_density_gradient")
+    outs = _outputs(_GRADIENT, n, positions.device, want, None, "field_density_gradient")
     rc = _lib.lib().ced_field_density_gradient(C.byref(desc), n, _p(positions), _p(t), *[_p(o) for o in outs], _stream())
     _lib.check(rc, "field_density_gradient")
     return tuple(outs)
@@ -490,26 +451,9 @@ def field_density_gradient_rays(desc: _lib.FieldDesc, rays_o, rays_d, ray_indice
     """ced_field_density_gradient_rays: `field_density_gradient` at the sample positions of `field_forward_rays`.  n_dev
     as there; out = the four buffers (or None each) to write into instead of fresh ones, which then decides what is
     computed."""
-    _chk(rays_o, torch.float32, "rays_o"); _chk(rays_d, torch.float32, "rays_d")
-    _chk(ray_indices, torch.int64, "ray_indices")
-    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends")
-    _chk(timestamps, torch.float32, "timestamps")
-    n = ray_indices.shape[0]
-    assert t_starts.shape == (n,) and t_ends.shape == (n,)
-    if t_per_ray:
-        assert timestamps.numel() == rays_o.shape[0], "per-ray timestamps must have one entry per ray"
-    if out is not None:
-        outs = list(out)
-        if len(outs) != len(GRADIENT_OUTPUTS) or all(o is None for o in outs):
-            raise ValueError("field_density_gradient_rays: no output requested")
-        for i, o in enumerate(outs):
-            _chk(o, torch.float32, f"out[{i}]", allow_none=True)
-            assert o is None or o.shape == ((n,) if i == 0 else (n, 3)), (i, o.shape)
-    else:
-        outs = _gradient_outputs(n, rays_o.device, want, "field_density_gradient_rays")
-    rc = _lib.lib().ced_field_density_gradient_rays(C.byref(desc), n, _p(n_dev), _p(rays_o), _p(rays_d), _p(ray_indices),
-                                                    _p(t_starts), _p(t_ends), _p(timestamps), int(bool(t_per_ray)),
-                                                    *[_p(o) for o in outs], _stream())
+    n, rays = _ray_samples(rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, t_per_ray)
+    outs = _outputs(_GRADIENT, n, rays_o.device, want, out, "field_density_gradient_rays")
+    rc = _lib.lib().ced_field_density_gradient_rays(C.byref(desc), n, _p(n_dev), *rays, *[_p(o) for o in outs], _stream())
     _lib.check(rc, "field_density_gradient_rays")
     return tuple(outs)
 

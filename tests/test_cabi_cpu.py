@@ -107,6 +107,44 @@ def test_argument_errors_are_reported_not_thrown():
         assert L.ced_set_option(key, default) == 0, key
 
 
+def test_per_sample_entries_report_the_same_argument_errors():
+    """The six per-sample entries on the motion network (move, velocity, density gradient and their rays twins) make the
+    same checks in the same order: descriptor, n < 0, n == 0 (success before any pointer is looked at), null inputs, no
+    output requested; the gradient pair then asks for sixteen levels.  Return codes and error strings as literals; every
+    case returns before a launch, so host pointers stand in for device memory."""
+    from ced_nerf_amd import _lib
+    L = _lib.lib()
+    buf = (C.c_float * 64)()
+    ptr = C.cast(buf, C.c_void_p)
+    d = _lib.FieldDesc()
+    d.packed_weights = ptr
+    d.packed_floats = L.ced_packed_weight_words(0, 0, 0)
+    d.hash.n_levels = 12                                  # a table validate_hash accepts: twelve hashed levels of 8 entries
+    d.hash.table = ptr
+    d.hash.total_entries = 8 * 12
+    for l in range(12):
+        d.hash.scale[l], d.hash.res[l], d.hash.offset[l], d.hash.size[l], d.hash.hashed[l] = 1.0, 2, 8 * l, 8, 1
+    # entry -> (rays entry?, number of outputs)
+    entries = {"field_move": (False, 4), "field_move_rays": (True, 2), "field_velocity": (False, 3),
+               "field_velocity_rays": (True, 3), "field_density_gradient": (False, 4), "field_density_gradient_rays": (True, 4)}
+
+    def call(name, desc, n, inputs, outputs):
+        rays, n_out = entries[name]
+        i, o = (ptr if inputs else None), (ptr if outputs else None)
+        args = [None, i, i, i, i, i, i, 1] if rays else [i, i]        # rays: n_dev (optional), six pointers, t_per_ray
+        rc = getattr(L, "ced_" + name)(desc, n, *args, *([o] * n_out), None)
+        return rc, L.ced_last_error_string().decode()
+
+    for name, (rays, _) in entries.items():
+        assert call(name, None, 4, True, True) == (-1, f"{name}: null descriptor"), name
+        assert call(name, C.byref(d), -1, True, True) == (-1, f"{name}: n < 0"), name
+        assert call(name, C.byref(d), 0, False, False)[0] == 0, name
+        assert call(name, C.byref(d), 4, False, True) == (-1, f"{name}: null pointer" if rays else f"{name}: null positions/t"), name
+        assert call(name, C.byref(d), 4, True, False) == (-1, f"{name}: no output requested"), name
+        if "gradient" in name:
+            assert call(name, C.byref(d), 4, True, True) == (-1, f"{name}: the kernel needs n_levels == 16 (got 12)"), name
+
+
 def test_closed_form_skip_matches_sequential_recurrence(oracle):
     """ced_host_skip_march runs the kernels' skip code on the host: the O(#binades) closed form for
     cone_angle == 0 must land on exactly the float the oracle's step-by-step loop reaches."""

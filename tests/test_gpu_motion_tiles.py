@@ -1,11 +1,14 @@
-"""GPU suite: the entries of csrc/field_move.hip and csrc/field_jacobian.hip do not depend on the launch grid.
+"""GPU suite: the entries of csrc/field_move.hip, csrc/field_jacobian.hip and csrc/field_density_gradient.hip do not depend
+on the launch grid.
 
 Their kernels are persistent: wave w of workgroup b takes tiles b * WAVES + w, + gridDim.x * WAVES, ...  With the default cap
-of 512 workgroups of 8 waves every wave of the other suites' largest input (4 099 rows) takes one tile, so the stride of
-that loop is exercised here: `max_workgroups` 1 and 3 at n = 257 and 4 099.  One workgroup at 4 099 rows is 129 tiles of 32
-rows (257 of 16 for the Jacobian and Newton kernels) over 8 waves -- many rounds, a ragged last tile, waves that run out
-at different rounds; three workgroups give a stride that does not divide the tile count.  Every output must be
-`torch.equal` to the same call on the default descriptor, whose outputs the neighbouring suites pin to the oracle.
+of 512 workgroups of 8 waves (256 for the density gradient) every wave of the other suites' largest input (4 099 rows) takes
+one tile, so the stride of that loop is exercised here: `max_workgroups` 1 and 3 at n = 257 and 4 099.  One workgroup at
+4 099 rows is 129 tiles of 32 rows (257 of 16 for the Jacobian, Newton, velocity and density-gradient kernels) over 8 waves
+-- many rounds, a ragged last tile, waves that run out at different rounds; three workgroups give a stride that does not
+divide the tile count.  Every output must be `torch.equal` to the same call on the default descriptor, whose outputs the
+neighbouring suites pin to the oracle.  The rays entries run with per-ray and with shared timestamps, and with a
+device-side count below n into prefilled `out=` buffers: the rows past the count must stay as they were on every grid.
 
 Fields: synthetic.init_field_params("trained"), fine offsets on, time_mode 0 and 2, moving step 1/32, in the four
 precisions: the fp32 chain, fp16 operands, split fp16 on the K = 32 placements (time_mode 0) and on the pair form
@@ -80,12 +83,29 @@ def _calls(n):
                                        n_dev=torch.tensor([keep], device=DEV, dtype=torch.int64), out=out)
         return fn
 
+    def rays_of(op, fills):
+        """op_rays with per-ray and shared timestamps, and shared with a device-side count below n into prefilled buffers"""
+        def call(ts, per_ray, keep=None):
+            def fn(d):
+                if keep is None:
+                    return op(d, I["rays_o"], I["rays_d"], ri, t0, t1, ts, per_ray)
+                out = tuple(torch.full((n,) + shape, fill, device=DEV) for shape, fill in fills)
+                return op(d, I["rays_o"], I["rays_d"], ri, t0, t1, ts, per_ray,
+                          n_dev=torch.tensor([keep], device=DEV, dtype=torch.int64), out=out)
+            return fn
+        return [(f"{op.__name__} per-ray", call(I["ts_rays"], True)), (f"{op.__name__} shared", call(I["ts_one"], False)),
+                (f"{op.__name__} shared n_dev", call(I["ts_one"], False, keep=n - 60))]
+
     calls = [("field_move", lambda d: ops.field_move(d, pos, t)),
              ("field_move_rays per-ray", rays(I["ts_rays"], True)),
              ("field_move_rays shared", rays(I["ts_one"], False)),
              ("field_move_rays per-ray n_dev", rays(I["ts_rays"], True, keep=n - 60)),
              ("field_move_rays shared n_dev", rays(I["ts_one"], False, keep=n - 60)),
              ("field_move_jacobian", lambda d: ops.field_move_jacobian(d, pos, t)),
+             ("field_velocity", lambda d: ops.field_velocity(d, pos, t)),
+             *rays_of(ops.field_velocity_rays, (((3,), 7.0), ((), 7.0), ((), True))),
+             ("field_density_gradient", lambda d: ops.field_density_gradient(d, pos, t)),
+             *rays_of(ops.field_density_gradient_rays, (((), 7.0), ((3,), 7.0), ((3,), 7.0), ((3,), 7.0))),
              ("field_rgb", lambda d: (ops.field_rgb(d, I["dirs"][:n], I["geo"][:n]),)),
              ("field_rgb_bcast", lambda d: (ops.field_rgb_bcast(d, I["dirs"][:N_DIRS], I["geo"][:n]),))]
     for K in (4, 32):
