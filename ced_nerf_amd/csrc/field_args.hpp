@@ -1,12 +1,57 @@
-// Kernel-argument block of the fused field kernel (field.hip), shared with the frame renderer.
+// Kernel-argument block of the fused field kernel (field_kernel.hpp; launched by field.hip), shared with the frame
+// renderer, and the per-level table of the hash grid as every kernel that reads the grid receives it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdint>
 
 #include "../../include/cednerf_hip.h"
+#include "ced_common.hpp"
 
 namespace ced {
+
+// The per-level table of a ced_hash_desc, by value inside a kernel's argument block (hash_device.hpp: make_level).
+struct HashLevels {
+    float scale[CED_MAX_LEVELS];
+    uint32_t res[CED_MAX_LEVELS], offset[CED_MAX_LEVELS], size[CED_MAX_LEVELS], hashed[CED_MAX_LEVELS];
+};
+
+inline void fill_levels(HashLevels &lv, const ced_hash_desc &h)
+{
+    for (int l = 0; l < CED_MAX_LEVELS; ++l) {
+        lv.scale[l] = h.scale[l]; lv.res[l] = h.res[l]; lv.offset[l] = h.offset[l];
+        lv.size[l] = h.size[l]; lv.hashed[l] = h.hashed[l];
+    }
+}
+
+// the fused kernels address the table by 32-bit byte offsets
+inline int require_32bit_byte_offsets(const ced_hash_desc &h, const char *who)
+{
+    CED_REQUIRE(h.total_entries * (uint64_t)((h.table_dtype ? 4 : 8) * (h.temporal ? 4 : 1)) < (1ull << 32),
+                "%s: hash table larger than 4 GiB", who);
+    return CED_OK;
+}
+
+// The level_mode word of a sixteen-level table, 2 bits per gather slot i = levels 4i..4i+3: 2 = all hashed, 0 = mixed.
+// With dense_modes a slot of four dense levels is 1, or 3 = all dense with the x-corner pairs as one load (hash_level
+// MODE 3): non-temporal tables, and every level of the slot followed by another level of the table -- the pair load of
+// a level's last entry reads one entry past the level.  Without it such a slot is 0.
+inline int hash_level_modes(const ced_hash_desc &h, bool dense_modes)
+{
+    int word = 0;
+    for (int i = 0; i < 4; ++i) {
+        int n_hashed = 0;
+        bool pairs = !h.temporal;
+        for (int g = 0; g < 4; ++g) {
+            const int l = 4 * i + g;
+            n_hashed += h.hashed[l] ? 1 : 0;
+            pairs = pairs && l + 1 < h.n_levels && (uint64_t)h.offset[l] + h.size[l] < h.total_entries;
+        }
+        const int dense = dense_modes ? (pairs ? 3 : 1) : 0;
+        word |= (n_hashed == 0 ? dense : (n_hashed == 4 ? 2 : 0)) << (2 * i);
+    }
+    return word;
+}
 
 struct FieldArgs {
     int64_t n;
@@ -27,16 +72,17 @@ struct FieldArgs {
     int use_div, time_mode;
     const void *weights;                              // packed blob of the descriptor's mlp_precision
     int table_dtype, temporal;
-    int spread_tiles;                                 // tile -> wave mapping (field.hip); ced_set_option("field_spread_tiles")
+    int spread_tiles;                                 // tile -> wave mapping (field_device.hpp); ced_set_option("field_spread_tiles")
     int level_mode;                                   // 2 bits per gather slot: 0 mixed, 1 all dense, 2 all hashed, 3 all dense and cannot wrap
     int max_blocks;                                   // workgroups of the launch (ced_field_desc.max_workgroups; <= 0: one per CU)
     const void *table;
-    float scale[CED_MAX_LEVELS];
-    uint32_t res[CED_MAX_LEVELS], offset[CED_MAX_LEVELS], size[CED_MAX_LEVELS], hashed[CED_MAX_LEVELS];
+    HashLevels levels;
 };
 
+// options of ced_set_option (field.hip)
 extern std::atomic<int> g_march_two_pass;
 extern std::atomic<int> g_field_spread_tiles;
+extern std::atomic<int> g_hash_grad_blocks;           // hash.hip
 constexpr int kFieldBlocksDefault = 256;      // one persistent workgroup per CU
 
 // Launches a persistent field kernel of NT 16-sample tiles per wave and THREADS threads per workgroup: enough
@@ -52,7 +98,7 @@ void launch_field_grid(Kernel kernel, const FieldArgs &A, void *stream)
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, A);
 }
 
-// field.hip: what every entry that reads the hash table checks of its descriptor
+// hash.hip: what every entry that reads the hash table checks of its descriptor
 int validate_hash(const ced_hash_desc *h, const char *who);
 // Fills the field/hash parts of A from the descriptor, validates, and launches on `stream`.
 int launch_field(const ced_field_desc *d, FieldArgs &A, void *stream);

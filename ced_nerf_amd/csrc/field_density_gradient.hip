@@ -26,6 +26,7 @@
 // four and four beside J and the 32 gathered values; two waves per SIMD, no scratch.
 #include "field_args.hpp"
 #include "field_jacobian_device.hpp"
+#include "hash_device.hpp"
 
 namespace ced {
 
@@ -41,8 +42,7 @@ struct GradArgs {
     int64_t lo_halves;
     int level_mode;                                   // 2 bits per gather slot: 2 = all four levels hashed, else 0
     const void *table;
-    float scale[CED_MAX_LEVELS];
-    uint32_t res[CED_MAX_LEVELS], offset[CED_MAX_LEVELS], size[CED_MAX_LEVELS], hashed[CED_MAX_LEVELS];
+    HashLevels levels;
 };
 
 constexpr float kExp15 = 3269017.25f;                 // the float32 nearest e^15: trunc_exp's backward clamps there
@@ -178,8 +178,7 @@ template <bool TE, bool F16, bool TEMPORAL> struct GradientOp : SampleOp {
     __device__ __forceinline__ static void fill_lds(const GradArgs &A, int tid)
     {
         if (tid < CED_MAX_LEVELS)
-            store_level(levels() + tid * 8, make_level(A.scale[tid], A.res[tid], A.offset[tid], A.size[tid], A.hashed[tid],
-                                                       EntryBytes<F16, TEMPORAL>::value));
+            store_level(levels() + tid * 8, make_level(A.levels, tid, EntryBytes<F16, TEMPORAL>::value));
     }
 
     // w = the tile's LDS base of the staged layers
@@ -288,11 +287,11 @@ template <bool TE, bool F16, bool TEMPORAL> static void launch_gradient_table(co
 static int launch_gradient(const ced_field_desc *d, GradArgs &A, const char *who, void *stream)
 {
     const ced_hash_desc &h = d->hash;
-    const int rc = validate_hash(&h, who);
+    int rc = validate_hash(&h, who);
     if (rc) return rc;
     CED_REQUIRE(h.n_levels == CED_MAX_LEVELS, "%s: the kernel needs n_levels == 16 (got %d)", who, h.n_levels);
-    CED_REQUIRE(h.total_entries * (uint64_t)((h.table_dtype ? 4 : 8) * (h.temporal ? 4 : 1)) < (1ull << 32),
-                "%s: hash table larger than 4 GiB", who);
+    rc = require_32bit_byte_offsets(h, who);
+    if (rc) return rc;
     static_assert(half_kernel_k32(false, false, true, 1024) && !half_kernel_k32(true, false, true, 1024) &&
                   !half_kernel_k32(false, true, true, 1024), "launch_gradient_table restates half_layout_k32");
     for (int i = 0; i < 6; ++i) A.aabb[i] = d->aabb[i];
@@ -303,24 +302,15 @@ static int launch_gradient(const ced_field_desc *d, GradArgs &A, const char *who
     float finest = 1.0f;
     for (int l = 0; l < CED_MAX_LEVELS; ++l) {
         CED_REQUIRE(h.scale[l] > 0.0f && h.scale[l] <= 1073741824.0f, "%s: level %d has scale %g", who, l, (double)h.scale[l]);
-        A.scale[l] = h.scale[l];
-        A.res[l] = h.res[l];
-        A.offset[l] = h.offset[l];
-        A.size[l] = h.size[l];
-        A.hashed[l] = h.hashed[l];
         finest = h.scale[l] > finest ? h.scale[l] : finest;
     }
+    fill_levels(A.levels, h);
     int e = 0;
     const float m = frexpf(finest, &e);                                  // finest = m * 2^e, 0.5 <= m < 1
     const int K = m == 0.5f ? e - 1 : e;                                 // ceil(log2(finest)), 0 .. 30
     A.tangent_scale = ldexpf(1.0f, -K);
     A.tangent_unscale = ldexpf(1.0f, K);
-    A.level_mode = 0;
-    for (int i = 0; i < 4; ++i) {
-        int n_hashed = 0;
-        for (int g = 0; g < 4; ++g) n_hashed += h.hashed[4 * i + g] ? 1 : 0;
-        A.level_mode |= (n_hashed == 4 ? 2 : 0) << (2 * i);
-    }
+    A.level_mode = hash_level_modes(h, false);
     switch ((d->time_mode ? 1 : 0) | (h.table_dtype ? 2 : 0) | (h.temporal ? 4 : 0)) {
     case 0: launch_gradient_table<false, false, false>(d, A, stream); break;
     case 1: launch_gradient_table<true, false, false>(d, A, stream); break;

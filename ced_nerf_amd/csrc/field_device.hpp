@@ -1,4 +1,4 @@
-// Device-side pieces shared by the fp32 (field.hip) and half-precision (field_half.hip) fused field
+// Device-side pieces shared by the fp32 (field_kernel.hpp) and half-precision (field_half.hip) fused field
 // kernels: per-level hash-grid constants, the trilinear gather of one level, the temporal key-frame
 // split and the 9-wide time encoding.  Everything here computes in fp32 with the deterministic
 // transcendentals of ced_common.hpp, whatever precision the MLPs run in.
@@ -89,14 +89,17 @@ struct LevelConst {
 
 template <bool F16, bool TEMPORAL> struct EntryBytes { static constexpr uint32_t value = (F16 ? 4u : 8u) * (TEMPORAL ? 4u : 1u); };
 
+// the spatial hash of a hashed level: x ^ y * kHashPrimeY ^ z * kHashPrimeZ (hash_encoder_half.py:112-161)
+constexpr uint32_t kHashPrimeY = 2654435761u, kHashPrimeZ = 805459861u;
+
 __device__ __forceinline__ LevelConst make_level(float scale, uint32_t res, uint32_t offset, uint32_t size, uint32_t hashed,
                                                  uint32_t eb)
 {
     LevelConst L;
     L.scale = scale;
     L.sxb = eb;
-    L.syb = (hashed ? 2654435761u : res) * eb;
-    L.szb = (hashed ? 805459861u : res * res) * eb;
+    L.syb = (hashed ? kHashPrimeY : res) * eb;
+    L.szb = (hashed ? kHashPrimeZ : res * res) * eb;
     L.offb = offset * eb;
     L.sizeb = size * eb;
     L.maskb = (size - 1u) * eb;
@@ -192,7 +195,7 @@ __device__ __forceinline__ void hash_level(const LevelConst &L, const void *__re
     f2 v[8];
     if constexpr (!TEMPORAL) {
         if constexpr (MODE == 3) {
-            // dense level (not the table's last: field.hip): the two x corners of a (y, z) corner are adjacent entries -- ONE
+            // dense level (not the table's last: field_args.hpp, hash_level_modes): the two x corners of a (y, z) corner are adjacent entries -- ONE
             // 16-byte (fp16 table: 8-byte) load instead of two on the same cache line.  The one exception is the reference's
             // `% size` acting between the two (the +x corner is the level's entry 0): that lane re-reads its second corner.
             constexpr uint32_t EBp = EntryBytes<F16, TEMPORAL>::value;

@@ -1,5 +1,5 @@
 // Half-precision-MFMA variants of the fused dynamic-NGP field (same fusion and same interface as
-// field.hip; selected by ced_field_desc.mlp_precision):
+// field_kernel.hpp; selected by ced_field_desc.mlp_precision):
 //
 //   CED_MLP_F16X2 (1): every MLP operand is split into two fp16 numbers, x = hi + lo (22 significant
 //       bits), and each product block is three fp16 MFMA blocks (hi*hi + hi*lo + lo*hi) with
@@ -14,7 +14,7 @@
 // (oracle/mfma_f16_model.h: two blocks of eight products per v_mfma_f32_16x16x16_f16, each cut below
 // 2^(Emax - 24) and rounded once) every output of these kernels is reproducible on the CPU bit for bit.
 //
-// Geometry: D^T = W * X^T as in field.hip, but K = 32 per product block (mfma_k32, field_half_device.hpp): lane (g = lane>>4, c = lane&15) supplies
+// Geometry: D^T = W * X^T as in field_kernel.hpp, but K = 32 per product block (mfma_k32, field_half_device.hpp): lane (g = lane>>4, c = lane&15) supplies
 // inputs 32ks + 8g + e (e = 0..7, four packed VGPRs) of sample c, and receives accumulator rows 4g + r.
 // The host packs the weight rows of every 64-wide hidden layer so that accumulator row 16nb + 4g + r
 // holds neuron 32(nb>>1) + 8g + 4(nb&1) + r: the eight values a lane needs as operand of k-step ks are
@@ -28,6 +28,7 @@
 #include "field_args.hpp"
 #include "field_device.hpp"
 #include "field_half_device.hpp"
+#include "hash_device.hpp"
 
 namespace ced {
 
@@ -82,7 +83,9 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
         for (int i = tid; i < WHALVES / 8; i += THREADS) dst[i] = src[i];
         if (tid < CED_MAX_LEVELS) {
             uint32_t *lt = reinterpret_cast<uint32_t *>(lds + WHALVES);
-            const LevelConst L = make_level(A.scale[tid], A.res[tid], A.offset[tid], A.size[tid], A.hashed[tid],
+            // the five reads spelled out: A is this kernel's by-value argument block (hash_device.hpp: make_level)
+            const HashLevels &lv = A.levels;
+            const LevelConst L = make_level(lv.scale[tid], lv.res[tid], lv.offset[tid], lv.size[tid], lv.hashed[tid],
                                             EntryBytes<F16, TEMPORAL>::value);
             store_level(lt + tid * 8, L);
         }
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
         }
     };
     for (int64_t tile = tiles.first; tile < tiles.end; tile = next_tile(tile)) {
-        // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field.hip)
+        // opaque LDS base per tile: keeps the A-fragment reads inside the loop (see field_kernel.hpp)
         int lds_off = 0;
         asm volatile("" : "+v"(lds_off));
         const _Float16 *const whi = lds + lds_off;
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
             sofs[j] = 16 * j + c < in_tile ? 16 * j + c : in_tile - 1;
             const int64_t s = tile_base + sofs[j];
             if (A.rays_mode) {
-                // negative ray index = unused sample slot (see field.hip)
+                // negative ray index = unused sample slot (see field_kernel.hpp)
                 const int64_t r_in = A.ray_idx32 ? (int64_t)A.ray_idx32[sbase + s] : A.ray_idx[sbase + s];
                 const bool used = r_in >= 0;
                 const int64_t r = used ? r_in : 0;

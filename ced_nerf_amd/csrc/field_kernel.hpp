@@ -1,10 +1,32 @@
 // The fused field kernel (template) and its packed-weight layout: included by field.hip (exact fp32 head) and
-// field_mixed.hip (exact sigma chain, split-fp16 colour head).  See field.hip for the description of the kernel.
+// field_mixed.hip (exact sigma chain, split-fp16 colour head).
+// Fused dynamic-NGP radiance field for gfx950: Frequency encoding -> motion MLP -> normalise /
+// selector -> multi-resolution hash gather -> [time encoding] -> mlp_base -> trunc_exp ->
+// SH(2) -> mlp_head -> sigmoid, one kernel, nothing but the inputs and (rgb, sigma) touch HBM.
+// Replaces DNGPradianceField.forward (cednerf/model.py:468-488; query_move :354-365,
+// query_density :367-445, _query_rgb :447-466), i.e. five tiny-cuda-nn launches plus ~12 torch
+// glue kernels per call, and the sigma_fn / rgb_sigma_fn closures of cednerf/utils.py:74-104,181-195.
+//
+// Execution shape (CDNA4): one 1024-thread workgroup per CU (4 waves per SIMD; 512 threads for temporal tables),
+// persistent over 32-sample wave tiles.  All nine weight matrices (~86 KB fp32, pre-swizzled by the host into
+// MFMA A-fragment order) are staged into LDS once per workgroup and read with conflict-free
+// ds_read_b128.  The GEMMs run on v_mfma_f32_16x16x4_f32 with D^T = W * X^T (neurons on the
+// accumulator rows, samples on lanes): exact fp32, an ascending-k fused-multiply-add chain,
+// which is what makes sample counts downstream bit-exact against the CPU oracle.  Activations
+// never leave registers, and they never move between lanes either: output rows are independent
+// dot products, so the host packs every hidden layer's weight rows such that accumulator row
+// 16nb + 4g + r (lane group g, register r) holds neuron 16nb + 4r + g -- which is exactly the element
+// lane group g must supply as B operand of k-step 4nb + r of the next layer.  A layer's accumulator
+// registers ARE the next layer's B operand (after a one-instruction ReLU), with the ascending-k
+// summation order intact.  The hash gather lives in the same geometry: lane group g owns levels
+// 4i + 2(g&1) + (g>>1), i = 0..3, of its 16 samples (128 gathers per sample spread over 4 lanes) and one
+// v_permlane16_swap per level pair puts the features in operand order.
 #pragma once
 #include "ced_common.hpp"
 #include "field_args.hpp"
 #include "field_device.hpp"
 #include "field_half_device.hpp"
+#include "hash_device.hpp"
 
 namespace ced {
 
@@ -152,7 +174,9 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
         for (int i = tid; i < BL::TOTAL / 4; i += FIELD_THREADS) dst[i] = src[i];
         if (tid < CED_MAX_LEVELS) {
             uint32_t *lt = reinterpret_cast<uint32_t *>(lds + BL::TOTAL);
-            const LevelConst L = make_level(A.scale[tid], A.res[tid], A.offset[tid], A.size[tid], A.hashed[tid],
+            // the five reads spelled out: A is this kernel's by-value argument block (hash_device.hpp: make_level)
+            const HashLevels &lv = A.levels;
+            const LevelConst L = make_level(lv.scale[tid], lv.res[tid], lv.offset[tid], lv.size[tid], lv.hashed[tid],
                                             EntryBytes<F16, TEMPORAL>::value);
             store_level(lt + tid * 8, L);
         }

@@ -2,7 +2,7 @@
 //
 // What a sample COUNT, an opacity or a depth depends on is sigma and t alone: Frequency encoding -> motion MLP ->
 // normalise / selector -> hash gather -> [time encoding] -> mlp_base -> trunc_exp (cednerf/model.py:354-445).  Those
-// stay the ascending-k fp32 FMA chains of field.hip (v_mfma_f32_16x16x4_f32), bit-identical to the CPU oracle -- so the
+// stay the ascending-k fp32 FMA chains of field_kernel.hpp (v_mfma_f32_16x16x4_f32), bit-identical to the CPU oracle -- so the
 // image-global N_samples schedule of render_image_test, every ray's sample set, its termination plane, opacity and
 // depth are those of the exact mode, bit for bit.  mlp_head (cednerf/model.py:447-466: [SH(4), geometry(15)] -> 64 -> 64
 // -> 3 -> sigmoid) only feeds rgb, where the north-star allows 1e-4: its 100 of the kernel's 324 fp32 MFMAs per

@@ -1,7 +1,7 @@
 """Time ("temporal") encoders with the interface of cednerf/encoder.py.
 
 Inside the renderer these 9-wide encodings are evaluated by the fused HIP field kernel
-(`time_feature` in csrc/field.hip); the modules below give callers of the reference API the same
+(`time_feature` in csrc/field_device.hpp); the modules below give callers of the reference API the same
 objects (`latent_dim`, `forward`) for use outside the hot path.  Output layouts (x_dim = 1):
   SinusoidalEncoder        [x, sin(2^k x) for k, sin(2^k x + pi/2) for k]         (encoder.py:36-44)
   SinusoidalEncoderWithExp [x, (sin(2^k x), sin(2^k x + pi/2)) * exp(-k 2^k v) per k] (encoder.py:75-90)

@@ -145,6 +145,72 @@ def test_per_sample_entries_report_the_same_argument_errors():
             assert call(name, C.byref(d), 4, True, True) == (-1, f"{name}: the kernel needs n_levels == 16 (got 12)"), name
 
 
+def test_hash_entries_report_descriptor_errors():
+    """What validate_hash and the three ced_hash_encode* entries refuse, and the 32-bit byte-offset limit of the two fused
+    entries that read the table: return codes and error strings as literals.  Every case returns before a launch, so host
+    pointers stand in for device memory."""
+    from ced_nerf_amd import _lib
+    assert "hash.hip" in _lib.SOURCES
+    L = _lib.lib()
+    buf = (C.c_float * 64)()
+    ptr = C.cast(buf, C.c_void_p)
+
+    def table(n_levels=4, temporal=0):
+        h = _lib.HashDesc()
+        h.n_levels, h.table_dtype, h.temporal, h.table, h.total_entries = n_levels, 0, temporal, ptr, 8 * 16
+        for l in range(16):
+            h.scale[l], h.res[l], h.offset[l], h.size[l], h.hashed[l] = 1.0, 2, 8 * l, 8, 1
+        return h
+
+    entries = {"hash_encode": lambda h, n: L.ced_hash_encode(h, n, ptr, ptr, ptr, None),
+               "hash_encode_backward": lambda h, n: L.ced_hash_encode_backward(h, n, ptr, ptr, ptr, ptr, 0, None),
+               "hash_encode_backward_temporal": lambda h, n: L.ced_hash_encode_backward_temporal(h, n, ptr, ptr, ptr, ptr, None)}
+
+    def call(name, h, n=4):
+        rc = entries[name](None if h is None else C.byref(h), n)
+        return rc, L.ced_last_error_string().decode()
+
+    for name in entries:
+        temporal = int(name.endswith("temporal"))
+        assert call(name, None) == (-1, f"{name}: null hash descriptor"), name
+        for n_levels in (0, 17):
+            assert call(name, table(n_levels, temporal)) == (-1, f"{name}: n_levels={n_levels} out of range"), name
+        h = table(4, temporal); h.table_dtype = 2
+        assert call(name, h) == (-1, f"{name}: table_dtype must be 0 (f32) or 1 (f16)"), name
+        h = table(4, temporal); h.size[2] = 6
+        assert call(name, h) == (-1, f"{name}: hashed level 2 size 6 is not a power of two"), name
+        h = table(4, temporal); h.hashed[1] = 0; h.size[1] = 7                # res 2: a dense level needs 8 entries
+        assert call(name, h) == (-1, f"{name}: dense level 1 smaller than res^3"), name
+        h = table(4, temporal); h.total_entries = 8 * 4 - 1
+        assert call(name, h) == (-1, f"{name}: level 3 exceeds the table"), name
+        assert call(name, table(4, temporal), -1) == (-1, f"{name}: n < 0"), name
+        assert call(name, table(4, temporal), 0)[0] == 0, name
+    assert call("hash_encode_backward", table(4, 1)) == (-1, "hash_encode_backward: the temporal table has no backward yet")
+    assert call("hash_encode_backward_temporal", table(4, 0)) == \
+        (-1, "hash_encode_backward_temporal: the table is not temporal (use ced_hash_encode_backward)")
+
+    # the fused entries address the table by 32-bit byte offsets: total_entries * bytes per entry < 2^32.  One entry
+    # below the limit each call gets as far as its next check.
+    for dtype, temporal in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        limit = (1 << 32) // ((4 if dtype else 8) * (4 if temporal else 1))
+        for total in (limit, limit - 1):
+            d = _lib.FieldDesc()
+            d.packed_weights = ptr
+            d.packed_floats = L.ced_packed_weight_words(0, 0, 0)
+            d.hash = table(16, temporal)
+            d.hash.table_dtype, d.hash.total_entries = dtype, total
+            d.hash.scale[0] = 0.0
+            d.max_workgroups = -1                                         # field_forward's next check
+            rc = L.ced_field_forward(C.byref(d), 4, ptr, ptr, None, None, ptr, None, None)
+            want = "field_forward: hash table larger than 4 GiB" if total == limit else "field_forward: max_workgroups=-1"
+            assert (rc, L.ced_last_error_string().decode()) == (-1, want), (dtype, temporal, total)
+            d.max_workgroups = 0                                          # the gradient's next check: the level scales
+            rc = L.ced_field_density_gradient(C.byref(d), 4, ptr, ptr, ptr, None, None, None, None)
+            want = ("field_density_gradient: hash table larger than 4 GiB" if total == limit
+                    else "field_density_gradient: level 0 has scale 0")
+            assert (rc, L.ced_last_error_string().decode()) == (-1, want), (dtype, temporal, total)
+
+
 def test_closed_form_skip_matches_sequential_recurrence(oracle):
     """ced_host_skip_march runs the kernels' skip code on the host: the O(#binades) closed form for
     cone_angle == 0 must land on exactly the float the oracle's step-by-step loop reaches."""

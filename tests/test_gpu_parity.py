@@ -135,6 +135,29 @@ def test_hash_encode(oracle, max_res, log2T, dtype, temporal):
     assert np.abs(want).max() > 0.1
 
 
+@pytest.mark.parametrize("temporal", [False, True])
+@pytest.mark.parametrize("dtype", [np.float32, np.float16])
+@pytest.mark.parametrize("n_levels", [7, 8])
+def test_hash_encode_few_levels(oracle, n_levels, dtype, temporal):
+    """ced_hash_encode with fewer than sixteen levels, bit for bit: an odd level count leaves by the kernel's scalar stores,
+    an even one by its 16-byte stores; 257 points cross a wave and a workgroup and include the corner and outside points
+    of _points; both table dtypes and both entry layouts."""
+    from ced_nerf_amd import ops, synthetic as S
+    p = S.init_field_params([-1, -1, -1, 1, 1, 1], 1e-4, 256, 12, regime="trained", table_dtype=dtype, temporal_hash=temporal,
+                            n_levels=n_levels)
+    of = oracle.OracleField({"hash": p["hash"]})
+    x = _points(257, 11)
+    t = np.random.default_rng(12).uniform(0, 1, size=x.shape[0]).astype(np.float32)
+    t[:3] = [0.0, 1.0, 1.0 / 3.0]
+    want = of.hash_encode(x, t if temporal else None)
+    table = T(p["hash"]["table"])      # the descriptor holds a raw pointer: keep the tensor alive
+    desc, _ = ops.make_hash_desc(table, 16, 256, n_levels, 12, temporal)
+    got = ops.hash_encode(desc, T(x), T(t) if temporal else None)
+    assert got.shape == (257, 2 * n_levels) and got.data_ptr() % 16 == 0
+    assert_bitexact(N(got), want, "hash features")
+    assert np.abs(want).max() > 0.1
+
+
 @pytest.mark.parametrize("max_res,log2T,dtype", [(1024, 17, np.float32), (4096, 15, np.float16), (256, 19, np.float32)])
 def test_hash_encode_backward(oracle, max_res, log2T, dtype):
     """SURVEY 8f row 2, first piece: hash_encoder_backward_kernel (hash_encoder_half.py:164-226).  The table gradient
@@ -177,7 +200,6 @@ def test_hash_encode_backward(oracle, max_res, log2T, dtype):
     # <dy, encode(T + dT) - encode(T)> == <grad_table, dT>
     if dtype == np.float32:
         dT = torch.randn_like(table) * 0.1
-        d2, _ = ops.make_hash_desc((table + dT).contiguous(), 16, max_res, 16, log2T, False)
         t2 = (table + dT).contiguous()
         d2, _ = ops.make_hash_desc(t2, 16, max_res, 16, log2T, False)
         lhs = ((ops.hash_encode(d2, T(x)) - ops.hash_encode(desc, T(x))).double() * T(dy).double()).sum().item()
