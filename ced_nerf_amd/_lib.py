@@ -13,7 +13,7 @@ from typing import List, Optional
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("CED_NERF_LIB", os.path.join(_PKG, "libcednerf_hip.so"))
-SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "hash.hip", "field_half.hip", "field_mixed.hip", "field_move.hip", "field_jacobian.hip", "field_density_gradient.hip", "frame.hip", "occgrid.hip",
+SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "hash.hip", "field_half.hip", "field_mixed.hip", "field_move.hip", "field_jacobian.hip", "field_density_gradient.hip", "field_time_max.hip", "frame.hip", "occgrid.hip",
            "raygen.hip", "wgrad.hip", "pixels.hip", "accel.hip", "linear.hip", "mlp.hip", "train_glue.hip", "losses.hip",
            "metrics.hip", "train_batch.hip", "importance.hip", "bake.hip", "mesh.hip"]
 MLP_F32, MLP_F16X2, MLP_F16, MLP_F32_HEAD16X2 = 0, 1, 2, 3          # ced_field_desc.mlp_precision
@@ -111,6 +111,7 @@ PROTOTYPES = {
     "ced_field_density_gradient": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ced_field_density_gradient_rays": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
                                                   _vp, _vp, _vp]),
+    "ced_field_density_time_max": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _i32, _i32, _vp, _vp, _vp]),
     "ced_field_velocity": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ced_field_velocity_rays": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "ced_field_move_inverse_newton": (C.c_int, [C.POINTER(FieldDesc), _i64, _vp, _vp, _vp, _i32, _f, _vp, _vp, _vp, _vp]),
@@ -149,6 +150,8 @@ PROTOTYPES = {
     "ced_finalize_pixels": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
     "ced_occ_cell_points": (C.c_int, [_i64, _vp, _vp, _i32, C.POINTER(C.c_float), _vp, _vp]),
     "ced_occ_ema_update": (C.c_int, [_i64, _vp, _vp, _f, _f, _vp, _vp]),
+    "ced_occ_time_slices_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ced_occ_time_slices": (C.c_int, [_i64, _vp, _vp, _i32, _f, _f, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "ced_generate_rays_pinhole": (C.c_int, [_i32, _i32, _f, _f, _f, _f, C.POINTER(C.c_float), _i32, _vp, _vp, _vp, _vp]),
     "ced_generate_rays_hypercam": (C.c_int, [_i32, _i32, C.POINTER(C.c_float), C.POINTER(C.c_float), _f, _f, _f, _f, _f,
                                              C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),

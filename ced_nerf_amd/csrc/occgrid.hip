@@ -37,7 +37,82 @@ __global__ __launch_bounds__(256) void occ_ema_kernel(int64_t n, const int64_t *
     occs[id] = __builtin_fmaxf(occs[id] * decay, occ);
 }
 
+// Time slices (ced_occ_time_slices), first kernel: hit[b, cell_ids[p]] = max_sigma[b, p] * step_size > thre.  One thread per
+// (bin, row); a listed cell's byte is written by its row alone (or by several rows with one value), unlisted cells keep
+// the 0 the caller cleared them to.  An id outside the grid is skipped.
+__global__ __launch_bounds__(256) void occ_slice_mark_kernel(int64_t n, int64_t total, const int64_t *__restrict__ cell_ids,
+                                                             const float *__restrict__ max_sigma, float step_size, float thre,
+                                                             int64_t cells, uint8_t *__restrict__ hit)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t b = i / n, p = i - b * n;
+    const int64_t id = cell_ids[p];
+    if (id < 0 || id >= cells) return;
+    hit[b * cells + id] = __fmul_rn(max_sigma[i], step_size) > thre ? 1 : 0;      // false for a NaN
+}
+
+// second kernel: out[b, l, c] = (hit[b, l, c], or the OR of hit over c's 3x3x3 neighbourhood inside level l) AND union[l, c]
+__global__ __launch_bounds__(256) void occ_slice_finish_kernel(int64_t total, int64_t cells, int res, int dilate,
+                                                               const uint8_t *__restrict__ hit, const uint8_t *__restrict__ uni,
+                                                               uint8_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t id = i % cells;                                        // level * R^3 + cell
+    uint8_t v = hit[i];
+    if (dilate && !v) {
+        const int64_t per = (int64_t)res * res * res;
+        const int64_t c = id % per;
+        const int iz = (int)(c % res), iy = (int)((c / res) % res), ix = (int)(c / ((int64_t)res * res));
+        for (int dx = -1; dx <= 1; ++dx) {
+            for (int dy = -1; dy <= 1; ++dy) {
+                for (int dz = -1; dz <= 1; ++dz) {
+                    const int x = ix + dx, y = iy + dy, z = iz + dz;
+                    if (x < 0 || x >= res || y < 0 || y >= res || z < 0 || z >= res) continue;
+                    v |= hit[i + ((int64_t)dx * res + dy) * res + dz];
+                }
+            }
+        }
+    }
+    if (uni) v = v && uni[id];
+    out[i] = v ? 1 : 0;
+}
+
 }  // namespace ced
+
+extern "C" int64_t ced_occ_time_slices_workspace_bytes(int32_t n_bins, int32_t levels, int32_t res)
+{
+    if (n_bins < 1 || n_bins > CED_TIME_MAX_BINS || levels < 1 || levels > 64 || res < 1 || res > 1024) return -1;
+    return (int64_t)n_bins * levels * res * res * res;
+}
+
+extern "C" int ced_occ_time_slices(int64_t n, const int64_t *cell_ids, const float *max_sigma, int32_t n_bins, float step_size,
+                                   float thre, int32_t levels, int32_t res, const uint8_t *union_binaries, int32_t dilate,
+                                   uint8_t *out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    CED_REQUIRE(n >= 0, "occ_time_slices: n < 0");
+    CED_REQUIRE(n_bins >= 1 && n_bins <= CED_TIME_MAX_BINS, "occ_time_slices: n_bins=%d outside 1 .. %d", n_bins, CED_TIME_MAX_BINS);
+    CED_REQUIRE(levels >= 1 && levels <= 64 && res >= 1 && res <= 1024, "occ_time_slices: levels=%d res=%d", levels, res);
+    CED_REQUIRE(dilate == 0 || dilate == 1, "occ_time_slices: dilate=%d must be 0 or 1", dilate);
+    const int64_t need = ced_occ_time_slices_workspace_bytes(n_bins, levels, res);
+    CED_REQUIRE(need / 256 < 2147483647 && n <= INT64_MAX / n_bins && (n * n_bins) / 256 < 2147483647,
+                "occ_time_slices: too many cells for one launch");
+    CED_REQUIRE(workspace && workspace_bytes >= need, "occ_time_slices: workspace too small (%lld < %lld bytes)",
+                (long long)workspace_bytes, (long long)need);
+    CED_REQUIRE(n == 0 || (cell_ids && max_sigma), "occ_time_slices: null cell_ids/max_sigma");
+    const int64_t cells = need / n_bins;
+    uint8_t *hit = reinterpret_cast<uint8_t *>(workspace);
+    if (n > 0) {
+        const int64_t total = n * n_bins;
+        hipLaunchKernelGGL(ced::occ_slice_mark_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                           total, cell_ids, max_sigma, step_size, thre, cells, hit);
+    }
+    if (out)
+        hipLaunchKernelGGL(ced::occ_slice_finish_kernel, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           need, cells, (int)res, (int)dilate, hit, union_binaries, out);
+    return ced::check_launch("occ_time_slices");
+}
 
 extern "C" int ced_occ_cell_points(int64_t n, const int64_t *cell_indices, const float *noise, int32_t res,
                                    const float *aabb_host, float *positions, void *stream)

@@ -27,6 +27,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .nerfacc_api import TimeSlicedOccGrid
+from .utils import grid_for
 
 _CPU = "Only support cuda inputs: the volume export runs on the HIP kernels (no CPU fallback)."
 
@@ -113,6 +115,15 @@ def _candidates(reso, center, radius, dev, estimator, max_cells_per_launch):
     return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
 
+def _candidates_by_time(reso, center, radius, dev, estimator, max_cells_per_launch):
+    """t -> `_candidates`: computed once and shared by every time, or, through a TimeSlicedOccGrid, per time from the grid
+    of that time (`utils.grid_for`)"""
+    if isinstance(estimator, TimeSlicedOccGrid):
+        return lambda t: _candidates(reso, center, radius, dev, grid_for(estimator, t), max_cells_per_launch)
+    shared = _candidates(reso, center, radius, dev, estimator, max_cells_per_launch)
+    return lambda t: shared
+
+
 def _bake(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max_rows: int, meta: Dict) -> Dict:
     desc = field._descriptor()
     index, xyz = cand
@@ -162,9 +173,9 @@ def bake_sequence(field, times: Sequence, reso: int = 128, sigma_thresh: float =
                                                   max_cells_per_launch)
     times = [_time_value(t) for t in times]
     with torch.cuda.device(dev):
-        cand = _candidates(int(reso), center, radius, dev, estimator, max_cells)
+        cand_at = _candidates_by_time(int(reso), center, radius, dev, estimator, max_cells)
         meta = dict(reso=int(reso), center=center, radius=radius, apply_act=bool(apply_act))
-        return [_bake(field, cand, t, float(sigma_thresh), dirs, apply_act, max_cells, meta) for t in times]
+        return [_bake(field, cand_at(t), t, float(sigma_thresh), dirs, apply_act, max_cells, meta) for t in times]
 
 
 def bake_volume(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None, apply_act: bool = False,
@@ -263,10 +274,10 @@ def extract_mesh_sequence(field, times: Sequence, reso: int = 128, sigma_thresh:
                                                          center, radius, max_cells_per_launch)
     times = [_time_value(t) for t in times]
     with torch.cuda.device(dev):
-        cand = _candidates(int(reso), center, radius, dev, estimator, max_cells)
+        cand_at = _candidates_by_time(int(reso), center, radius, dev, estimator, max_cells)
         meta = dict(reso=int(reso), center=center, radius=radius, sigma_thresh=float(sigma_thresh),
                     apply_act=bool(apply_act))
-        return [_mesh(field, cand, t, float(sigma_thresh), "normal" if by_normal else tensor_dirs, apply_act, max_cells,
+        return [_mesh(field, cand_at(t), t, float(sigma_thresh), "normal" if by_normal else tensor_dirs, apply_act, max_cells,
                       meta, field_normals) for t in times]
 
 

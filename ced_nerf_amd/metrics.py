@@ -17,7 +17,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .utils import Rays, render_frames_test, render_image_test
+from .utils import Rays, grid_for, render_frames_test, render_image_test
 
 MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # pytorch_msssim's default level weights
 
@@ -157,14 +157,15 @@ def evaluate_views(radiance_field, estimator, views: Iterable[Dict], max_samples
         bkgd = group[0]["color_bkgd"]
         if len(group) == 1:
             v = group[0]
-            rgb, _, _, total = render_image_test(max_samples, radiance_field, estimator, v["rays"], render_bkgd=bkgd,
-                                                 timestamps=v["timestamps"].to(dev), **render_kwargs)
+            ts = v["timestamps"].to(dev)
+            rgb, _, _, total = render_image_test(max_samples, radiance_field, grid_for(estimator, ts), v["rays"], render_bkgd=bkgd,
+                                                 timestamps=ts, **render_kwargs)
             rgbs, n = rgb[None], [int(total)]
         else:
             rays = Rays(origins=torch.stack([v["rays"].origins for v in group]),
                         viewdirs=torch.stack([v["rays"].viewdirs for v in group]))
             ts = torch.cat([v["timestamps"].to(dev).reshape(-1) for v in group])
-            rgbs, _, _, n = render_frames_test(max_samples, radiance_field, estimator, rays, render_bkgd=bkgd,
+            rgbs, _, _, n = render_frames_test(max_samples, radiance_field, grid_for(estimator, ts), rays, render_bkgd=bkgd,
                                                timestamps=ts, **render_kwargs)
         pix = torch.stack([v["pixels"].to(dev, torch.float32) for v in group])
         s, p = _view_metrics(rgbs, pix)

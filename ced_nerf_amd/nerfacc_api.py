@@ -450,3 +450,166 @@ class OccGridEstimator(torch.nn.Module):
             masks = ops.visibility_mask(packed_info, t_starts, t_ends, sigmas.contiguous(), early_stop_eps, alpha_thre)
             ray_indices, t_starts, t_ends = ray_indices[masks], t_starts[masks], t_ends[masks]
         return ray_indices, t_starts, t_ends
+
+
+class TimeSlicedOccGrid(torch.nn.Module):
+    """B occupancy grids of one scene, slice b marking the cells that are occupied at SOME probed time of bin b =
+    [b / B, (b + 1) / B]: a frame at time t marches what is occupied around t, not the whole volume a moving object sweeps
+    over the clip (which is what `OccGridEstimator.binaries`, an EMA maximum over random times, marks).
+
+    It is for rendering a trained field: `from_field` builds the slices, `at_time(t)` hands out a plain OccGridEstimator
+    (cached per range of bins, so its `occupancy_accel()` is built once) that every renderer takes as it takes any other;
+    `utils.grid_for` is where the renderers resolve one.  Training keeps the reference's estimator.
+
+    A slice probes cell centres at S times per bin: structure thinner than a cell, or faster than a cell per 1 / (B (S - 1)),
+    can be missed.  dilate = 1 (the default) and a larger S trade samples for safety.  A slice estimator's `occs` are its
+    binaries as 0 / 1 (`set_binaries`), not the training EMA.
+
+    Buffers: binaries_t [B, levels, R, R, R] bool, aabbs [levels, 6], resolution [3]."""
+
+    def __init__(self, roi_aabb, resolution=128, levels: int = 1, n_bins: int = 16, device=None) -> None:
+        super().__init__()
+        if isinstance(resolution, int):
+            resolution = [resolution] * 3
+        resolution = torch.as_tensor(resolution, dtype=torch.int32).cpu()
+        res = int(resolution[0])
+        if not bool((resolution == res).all()):
+            raise ValueError("cubic grids only")
+        if not 1 <= int(n_bins) <= ops.TIME_MAX_BINS:
+            raise ValueError(f"n_bins must be in 1 .. {ops.TIME_MAX_BINS}, got {n_bins}")
+        if not isinstance(roi_aabb, torch.Tensor):
+            roi_aabb = torch.tensor(roi_aabb, dtype=torch.float32)
+        assert roi_aabb.shape == (6,), f"Invalid shape: {roi_aabb.shape}!"
+        self.levels, self.n_bins = int(levels), int(n_bins)
+        aabbs = torch.stack([_enlarge_aabb(roi_aabb.float().cpu(), 2 ** i) for i in range(self.levels)], dim=0)
+        self.register_buffer("resolution", resolution.to(device))
+        self.register_buffer("aabbs", aabbs.to(device))
+        # on `device` from the start: B * m * R^3 bytes are not worth a trip through host memory
+        self.register_buffer("binaries_t", torch.zeros([self.n_bins, self.levels, res, res, res], dtype=torch.bool, device=device))
+
+    # ---- the estimators handed out ------------------------------------------------------------------------------------
+    def _forget(self) -> None:
+        self.__dict__["_estimators"] = {}
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._forget()
+
+    def set_slices(self, binaries_t: torch.Tensor) -> None:
+        assert binaries_t.shape == self.binaries_t.shape, (binaries_t.shape, self.binaries_t.shape)
+        self.binaries_t.copy_(binaries_t.to(self.binaries_t.device, torch.bool))
+        self._forget()
+
+    def bin_range(self, t) -> Tuple[int, int]:
+        """(lo, hi), the bins that hold min t and max t: times clamped to [0, 1], bin = min(floor(t * B), B - 1).  t: a
+        float, a sequence, or a tensor of any shape (a device tensor costs one host read)."""
+        if isinstance(t, torch.Tensor):
+            if t.numel() == 0:
+                raise ValueError("at_time: no time given")
+            tf = t.detach().reshape(-1).double()
+            t_min, t_max = torch.stack([tf.min(), tf.max()]).tolist()        # the one host read
+        else:
+            seq = [float(v) for v in (t if isinstance(t, (list, tuple)) else [t])]
+            if not seq:
+                raise ValueError("at_time: no time given")
+            t_min, t_max = min(seq), max(seq)
+        if t_min != t_min or t_max != t_max:
+            raise ValueError("at_time: a time is NaN")
+        B = self.n_bins
+        lo, hi = (min(int(min(max(v, 0.0), 1.0) * B), B - 1) for v in (t_min, t_max))
+        return lo, hi
+
+    def _range(self, lo: int, hi: int) -> "OccGridEstimator":
+        cache = self.__dict__.setdefault("_estimators", {})
+        key = (lo, hi, str(self.binaries_t.device), self.binaries_t.data_ptr(), self.binaries_t._version)
+        est = cache.get(key)
+        if est is None:
+            dev = self.binaries_t.device
+            est = OccGridEstimator(self.aabbs[0].detach().cpu(), self.resolution.detach().cpu(), self.levels).to(dev).eval()
+            est.aabbs.copy_(self.aabbs)
+            est.set_binaries(self.binaries_t[lo:hi + 1].any(dim=0))
+            cache[key] = est
+        return est
+
+    @torch.no_grad()
+    def at_time(self, t) -> "OccGridEstimator":
+        """A plain OccGridEstimator whose binaries are the OR of the bins that cover min t .. max t; the same object for the
+        same range of bins, until the slices change."""
+        return self._range(*self.bin_range(t))
+
+    @torch.no_grad()
+    def union(self) -> "OccGridEstimator":
+        """The OR of all bins, as an OccGridEstimator."""
+        return self._range(0, self.n_bins - 1)
+
+    @torch.no_grad()
+    def occupied_fraction(self) -> torch.Tensor:
+        """[B]: each slice's occupied cells as a share of the union's (0 where the union is empty)."""
+        counts = self.binaries_t.flatten(1).sum(dim=1).double()
+        total = float(self.binaries_t.any(dim=0).sum())
+        return (counts / total if total > 0 else torch.zeros_like(counts)).float()
+
+    # ---- the build ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def probe_times(n_bins: int, times_per_bin: int, device=None) -> torch.Tensor:
+        """[B, S] float32: t[b, s] = (b + s / (S - 1)) / B, so neighbouring bins share their end time; S = 1 probes the
+        bin's midpoint.  Every operation in float32."""
+        B, S = int(n_bins), int(times_per_bin)
+        if not (1 <= B <= ops.TIME_MAX_BINS and 1 <= S <= ops.TIME_MAX_TIMES):
+            raise ValueError(f"n_bins in 1 .. {ops.TIME_MAX_BINS} and times_per_bin in 1 .. {ops.TIME_MAX_TIMES}: got {B}, {S}")
+        b = torch.arange(B, dtype=torch.float32, device=device)[:, None]
+        s = torch.arange(S, dtype=torch.float32, device=device)[None, :]
+        frac = s / float(S - 1) if S >= 2 else torch.full_like(s, 0.5)
+        return ((b + frac) / float(B)).contiguous()
+
+    @classmethod
+    @torch.no_grad()
+    def from_field(cls, field, estimator: Optional["OccGridEstimator"] = None, *, roi_aabb=None, resolution=128,
+                   levels: int = 1, n_bins: int = 16, times_per_bin: int = 5, render_step_size: float,
+                   occ_thre: float = 0.01, dilate: int = 1, chunk: int = 1 << 20) -> "TimeSlicedOccGrid":
+        """Slices of a trained field.  Per level the candidates are the cells `estimator.binaries` marks, in ascending
+        order -- every slice is then a subset of that grid --, or every cell of a grid made from roi_aabb / resolution /
+        levels.  Each candidate's centre is probed at `probe_times` by ONE fused launch per chunk of `chunk` cells
+        (ops.field_density_time_max: B * chunk * 4 bytes of maxima at a time); a cell is hit in bin b where max density *
+        render_step_size > thre, thre = min(occ_thre, mean of estimator.occs[occs >= 0]) as OccGridEstimator._update forms
+        it (occ_thre without an estimator); dilate = 1 adds each hit's 26 neighbours (ops.occ_time_slices)."""
+        if estimator is not None:
+            roi_aabb, resolution, levels = estimator.aabbs[0].detach().cpu(), estimator.resolution.detach().cpu(), estimator.levels
+            dev = estimator.binaries.device
+        else:
+            if roi_aabb is None:
+                raise ValueError("from_field: give an estimator or roi_aabb")
+            dev = field.aabb.device
+        if int(chunk) < 1:
+            raise ValueError(f"from_field: chunk={chunk}")
+        self = cls(roi_aabb, resolution, levels, n_bins, device=dev)
+        res, cells = int(self.resolution[0]), int(self.binaries_t[0, 0].numel())
+        thre, union = float(occ_thre), None
+        if estimator is not None:
+            self.aabbs.copy_(estimator.aabbs)
+            union = estimator.binaries.contiguous()
+            seen = estimator.occs[estimator.occs >= 0]
+            if seen.numel():
+                thre = float(torch.clamp(seen.mean(), max=occ_thre))
+        with torch.cuda.device(dev):
+            times = cls.probe_times(n_bins, times_per_bin, dev)
+            desc = field._descriptor()
+            aabbs = self.aabbs.detach().cpu().numpy()
+            workspace = ops.occ_time_slices_workspace(self.n_bins, self.levels, res, dev)
+            for lvl in range(self.levels):
+                if union is not None:
+                    candidates = torch.nonzero(union[lvl].flatten())[:, 0]
+                else:
+                    candidates = torch.arange(cells, device=dev)
+                for i in range(0, candidates.numel(), int(chunk)):
+                    idx = candidates[i:i + int(chunk)].contiguous()
+                    centres = ops.occ_cell_points(idx, torch.full((idx.numel(), 3), 0.5, device=dev), res, aabbs[lvl])
+                    maxima = ops.field_density_time_max(desc, centres, times)
+                    ops.occ_time_slices((lvl * cells + idx).contiguous(), maxima, render_step_size, thre, self.levels, res,
+                                        union, dilate, workspace=workspace, finish=False)
+            none = torch.empty((0,), device=dev, dtype=torch.int64)
+            slices = ops.occ_time_slices(none, torch.empty((self.n_bins, 0), device=dev), render_step_size, thre, self.levels,
+                                         res, union, dilate, workspace=workspace)
+        self.binaries_t = slices                                         # the buffer itself: no second copy of the slices
+        self._forget()
+        return self.eval()

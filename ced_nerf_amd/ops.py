@@ -1461,3 +1461,67 @@ def occ_ema_update_(occs: torch.Tensor, cell_ids: torch.Tensor, density: torch.T
     rc = _lib.lib().ced_occ_ema_update(cell_ids.shape[0], _p(cell_ids), _p(density), float(step_size), float(ema_decay),
                                        _p(occs), _stream())
     _lib.check(rc, "occ_ema_update")
+
+
+# ----------------------------------------------------------------------------------------------
+# time-sliced occupancy grids
+# ----------------------------------------------------------------------------------------------
+TIME_MAX_BINS, TIME_MAX_TIMES = 256, 64           # ced_field_density_time_max: 1 <= B <= 256, 1 <= S <= 64
+
+
+def field_density_time_max(desc: _lib.FieldDesc, positions, times, out=None):
+    """ced_field_density_time_max: out[b, p] = fmax over s of the density at (positions[p], times[b, s]), started from 0,
+    from one launch.  positions [n,3], times [B,S] (each in [0,1]) -> [B,n]; every density has `field_forward`'s bits, a
+    NaN density is ignored.  out = a [B,n] buffer to write into instead of a fresh one."""
+    _chk(positions, torch.float32, "positions"); _chk(times, torch.float32, "times")
+    n = positions.shape[0]
+    if positions.shape != (n, 3) or times.dim() != 2:
+        raise ValueError(f"field_density_time_max: positions [n,3], times [B,S]: got {list(positions.shape)}, {list(times.shape)}")
+    b, s = times.shape
+    if not (1 <= b <= TIME_MAX_BINS and 1 <= s <= TIME_MAX_TIMES):
+        raise ValueError(f"field_density_time_max: times [B,S] with 1 <= B <= {TIME_MAX_BINS}, 1 <= S <= {TIME_MAX_TIMES}: "
+                         f"got {list(times.shape)}")
+    (out,) = _outputs((("out", (n,), torch.float32),), b, positions.device, (True,), None if out is None else (out,),
+                      "field_density_time_max")
+    rc = _lib.lib().ced_field_density_time_max(C.byref(desc), n, _p(positions), b, s, _p(times), _p(out), _stream())
+    _lib.check(rc, "field_density_time_max")
+    return out
+
+
+def occ_time_slices_workspace(n_bins: int, levels: int, res: int, device) -> torch.Tensor:
+    """The zeroed `hit` workspace of one build of time slices (ced_occ_time_slices_workspace_bytes)."""
+    need = int(_lib.lib().ced_occ_time_slices_workspace_bytes(int(n_bins), int(levels), int(res)))
+    if need < 0:
+        raise ValueError(f"occ_time_slices: n_bins={n_bins} (1 .. {TIME_MAX_BINS}), levels={levels} (1 .. 64), res={res} (1 .. 1024)")
+    return torch.zeros((need,), device=device, dtype=torch.uint8)
+
+
+def occ_time_slices(cell_ids, max_sigma, step_size: float, thre: float, levels: int, res: int, union_binaries=None,
+                    dilate: int = 1, workspace=None, finish: bool = True):
+    """ced_occ_time_slices: B occupancy grids from the maxima of `field_density_time_max`.  cell_ids [n] int64 (level * R^3 +
+    cell), max_sigma [B,n] -> bool [B, levels, R, R, R]: a listed cell is hit where max_sigma * step_size > thre (float32
+    product; false for a NaN), an unlisted one is not; dilate = 1 ORs the hits over each cell's 3x3x3 neighbourhood inside
+    its level; union_binaries [levels, R, R, R] bool, where given, is ANDed on.  workspace / finish: a build that hands its
+    rows over in several calls makes one `occ_time_slices_workspace`, passes it to every call and finish=False (mark only,
+    returns None) to all but the last."""
+    _chk(cell_ids, torch.int64, "cell_ids"); _chk(max_sigma, torch.float32, "max_sigma")
+    _chk(union_binaries, torch.bool, "union_binaries", allow_none=True)
+    n = cell_ids.shape[0]
+    if cell_ids.shape != (n,) or max_sigma.dim() != 2 or max_sigma.shape[1] != n:
+        raise ValueError(f"occ_time_slices: cell_ids [n], max_sigma [B,n]: got {list(cell_ids.shape)}, {list(max_sigma.shape)}")
+    b, levels, res = max_sigma.shape[0], int(levels), int(res)
+    if dilate not in (0, 1) or isinstance(dilate, bool):
+        raise ValueError(f"occ_time_slices: dilate must be 0 or 1, got {dilate!r}")
+    grid = (levels, res, res, res)
+    if union_binaries is not None and tuple(union_binaries.shape) != grid:
+        raise ValueError(f"occ_time_slices: union_binaries must be {list(grid)}, got {list(union_binaries.shape)}")
+    dev = cell_ids.device
+    if workspace is None:
+        workspace = occ_time_slices_workspace(b, levels, res, dev)
+    _chk(workspace, torch.uint8, "workspace")
+    out = torch.empty((b,) + grid, device=dev, dtype=torch.bool) if finish else None
+    rc = _lib.lib().ced_occ_time_slices(n, _p(cell_ids), _p(max_sigma), b, float(step_size), float(thre), levels, res,
+                                        _p(_as_u8(union_binaries)), int(dilate), _p(_as_u8(out)), _p(workspace),
+                                        workspace.numel(), _stream())
+    _lib.check(rc, "occ_time_slices")
+    return out

@@ -325,9 +325,8 @@ def write_video_frames(out_dir: str, inference, estimator, cfg: Dict, test: Trai
     return len(frames)
 
 
-def main(argv=None) -> int:
-    """CLI over a D-NeRF synthetic, HyperNeRF or DyNeRF scene folder, with the flag names of opt.py."""
-    from . import checkpoint, scenes
+def build_parser() -> argparse.ArgumentParser:
+    """The CLI's arguments (flag names of opt.py)."""
     p = argparse.ArgumentParser(description="Train a D-NeRF synthetic, HyperNeRF or DyNeRF scene (train_real.py's loop)")
     p.add_argument("--data_root", required=True)
     p.add_argument("--scene", required=True)
@@ -348,6 +347,9 @@ def main(argv=None) -> int:
                    help="with --render_video: also write flow_%%04d.png, the optical flow over one frame of the path (pinhole cameras)")
     p.add_argument("--video_flow_max", type=float, default=None, metavar="PX",
                    help="flow magnitude in pixels at full saturation (default: the largest of the frames written)")
+    p.add_argument("--time_bins", type=int, default=None, metavar="B",
+                   help="with --render_video: render through B time slices of the occupancy grid (TimeSlicedOccGrid.from_field)")
+    p.add_argument("--time_bin_samples", type=int, default=5, metavar="S", help="probe times per bin of --time_bins")
     p.add_argument("--ist_from_step", type=int, default=None, help="DyNeRF: sample by the IST map from this step on")
     p.add_argument("-df", "--use_div_offsets", action="store_true")
     p.add_argument("-f", "--use_feat_predict", action="store_true")
@@ -359,6 +361,13 @@ def main(argv=None) -> int:
     p.add_argument("-d", "--distortion_loss", action="store_true")
     p.add_argument("-wr", "--weight_rgbper", action="store_true")
     p.add_argument("-ae", "--acc_entorpy_loss", action="store_true")
+    return p
+
+
+def main(argv=None) -> int:
+    """CLI over a D-NeRF synthetic, HyperNeRF or DyNeRF scene folder, with the flag names of opt.py."""
+    from . import checkpoint, scenes
+    p = build_parser()
     a = p.parse_args(argv)
     if a.dataset != "auto":
         kind = a.dataset
@@ -380,6 +389,12 @@ def main(argv=None) -> int:
                  use_weight_predict=a.use_weight_predict)
     if a.video_flow and not a.render_video:
         p.error("--video_flow goes with --render_video DIR")
+    if a.time_bins is not None:
+        from . import ops
+        if not a.render_video:
+            p.error("--time_bins goes with --render_video DIR")
+        if not (1 <= a.time_bins <= ops.TIME_MAX_BINS and 1 <= a.time_bin_samples <= ops.TIME_MAX_TIMES):
+            p.error(f"--time_bins takes 1 .. {ops.TIME_MAX_BINS}, --time_bin_samples 1 .. {ops.TIME_MAX_TIMES}")
     test = load_scene(a.data_root, a.scene, kind, test_split, a.factor)
     if a.video_flow and test.model != CAMERA_PINHOLE:
         p.error("--video_flow needs pinhole cameras (D-NeRF test views, the DyNeRF spiral): these views have distorted "
@@ -401,7 +416,14 @@ def main(argv=None) -> int:
                   log_every=log_every, save_path=a.save_path, **flags, **sampling, **extra)
         inference, estimator, cfg = res["inference"], res["estimator"], res["config"]
     if a.render_video:
-        n = write_video_frames(a.render_video, inference.eval(), estimator.eval(), cfg, test, kind, a.video_frames,
+        grid = estimator.eval()
+        if a.time_bins is not None:
+            from .nerfacc_api import TimeSlicedOccGrid
+            grid = TimeSlicedOccGrid.from_field(inference.eval(), grid, n_bins=a.time_bins, times_per_bin=a.time_bin_samples,
+                                                render_step_size=cfg["render_step_size"])
+            shares = ", ".join(f"{100.0 * v:.1f}" for v in grid.occupied_fraction().tolist())
+            print(f"{a.time_bins} time slices of the occupancy grid; occupied share of the union per bin (%): {shares}", flush=True)
+        n = write_video_frames(a.render_video, inference.eval(), grid, cfg, test, kind, a.video_frames,
                                flow=a.video_flow, flow_max=a.video_flow_max)
         print(f"wrote {n} rgb and depth{' and flow' if a.video_flow else ''} frames to {a.render_video}", flush=True)
     return 0

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .nerfacc_api import (OccGridEstimator, _packed_info_from, accumulate_along_rays, march_packed, ray_aabb_intersect,
+from .nerfacc_api import (OccGridEstimator, TimeSlicedOccGrid, _packed_info_from, accumulate_along_rays, march_packed, ray_aabb_intersect,
                           render_weight_from_density, sort_intersections)
 from .render import rendering
 
@@ -54,6 +54,15 @@ trunc_exp = _TruncExp.apply
 _EVAL_PASS_RAYS = 1 << 21     # rays per internal eval pass of render_image
 
 
+def grid_for(estimator, timestamps):
+    """The occupancy grid a render at `timestamps` marches through: `estimator.at_time(timestamps)` for a TimeSlicedOccGrid
+    (the OR of the bins that cover the range of the times; one host read for a device tensor), the estimator itself --
+    the same object, nothing read -- for anything else.  Every renderer calls it first thing."""
+    if isinstance(estimator, TimeSlicedOccGrid) and timestamps is not None:
+        return estimator.at_time(timestamps)
+    return estimator
+
+
 def _flatten_rays(rays: Rays):
     rays_shape = rays.origins.shape
     if len(rays_shape) == 3:
@@ -86,6 +95,7 @@ def render_image(
     `rendering` from ONE field evaluation per sample, rays stopped where their transmittance falls below the filter's
     threshold -- the same arrays bit for bit (tests/test_gpu_parity.py).  native=False forces the staged composition
     (sampling with sigma_fn, then rendering) that training mode always uses."""
+    estimator = grid_for(estimator, timestamps)
     if timestamps is None:
         raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:78-86)")
     rays, rays_shape, num_rays = _flatten_rays(rays)
@@ -210,6 +220,7 @@ def _render_sample_values(radiance_field, estimator, rays, near_plane, far_plane
     tuple of names, a dict of per-sample tensors that holds at least those names: each named one ([S,C] float, or [S] bool
     taken as 0 / 1) becomes an image, in that order, and every entry of the dict goes into the sample dicts.
     Returns (image [H,W,C] per name, opacity [H,W,1], n_samples[, samples])."""
+    estimator = grid_for(estimator, timestamps)
     _check_eval_frame(radiance_field, timestamps, who)
     rays, rays_shape, num_rays = _flatten_rays(rays)
     ts = timestamps
@@ -427,6 +438,7 @@ def render_image_test(
     reference.  The whole loop runs inside the native library (ced_render_image_test): four
     launches per iteration, the N_samples schedule computed on the device; `render_image_test_staged` is the
     same algorithm driven from Python through the nerfacc-shaped ops."""
+    estimator = grid_for(estimator, timestamps)
     if timestamps is None:
         raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:186-194)")
     rays, rays_shape, N_rays = _flatten_rays(rays)
@@ -468,6 +480,7 @@ def render_frames_test(
     depth [F,...,1], [total_samples of every frame]).
     exchange (ops.ScheduleExchange): rays[f] is this rank's share of frame f, whose other rays other ranks render; the
     loop of every frame is then the WHOLE image's (N_rays // N_alive over all ranks, cednerf/utils.py:231-235)."""
+    estimator = grid_for(estimator, timestamps)              # the range of the frames' times
     if timestamps is None:
         raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:186-194)")
     if radiance_field.training:
@@ -506,6 +519,7 @@ def render_image_test_staged(
     """render_image_test (cednerf/utils.py:153-318) staged from Python through the nerfacc-shaped
     ops (count -> scan -> fill marching, field, composite_step): the reference's own structure,
     kept for per-kernel profiling and as a cross-check of the native loop."""
+    estimator = grid_for(estimator, timestamps)
     if timestamps is None:
         raise NotImplementedError("DNGPradianceField needs timestamps (dnerf path of cednerf/utils.py:186-194)")
     rays, rays_shape, N_rays = _flatten_rays(rays)

@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .dist import PipelinedRenderer, ShardedRenderer
+from .nerfacc_api import TimeSlicedOccGrid
 from .utils import Rays, render_motion, render_normals, render_optical_flow, render_scene_flow
 
 
@@ -49,7 +50,10 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
     scene_flow=True: likewise `scene_flow_f32` [H,W,3] (`utils.render_scene_flow`'s flow3d).
     optical_flow=(projector_of_frame, dt): likewise `flow_f32` [H,W,2] and `flow_coverage_f32` [H,W,1],
     `utils.render_optical_flow` with project = projector_of_frame(i) (e.g. `cameras.pinhole_projector(K, c2w_i)`) and the
-    time step dt; the expected flow of the visible surface, in pixels per dt, is flow_f32 / flow_coverage_f32."""
+    time step dt; the expected flow of the visible surface, in pixels per dt, is flow_f32 / flow_coverage_f32.
+    estimator may be a `TimeSlicedOccGrid`: every native call then marches through `estimator.at_time(the times of its
+    frames)` -- the frames' times are read to the host once, before the pipeline starts -- and the post passes resolve
+    their grid per frame (`utils.grid_for`)."""
     if n_frames <= 0:
         return []
     device = radiance_field.aabb.device if hasattr(radiance_field, "aabb") else torch.device("cuda")
@@ -63,7 +67,21 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
     # frames of the call (lane, step); the tail of the path repeats the last frame
     frames_of = lambda lane, step: [min((step * n_lanes + lane) * per_call + k, n_frames - 1) for k in range(per_call)]
 
+    # a sliced grid: one host read of all the frames' times, and every call's grid (with its distance field) built and
+    # finished here, on this thread, before the pipeline's lane threads start
+    grids = None
+    if isinstance(estimator, TimeSlicedOccGrid):
+        host_times = torch.cat([timestamps_of_frame(i).reshape(-1)[:1] for i in range(n_frames)]).tolist()
+        grids = {}
+        for step in range(n_steps):
+            for lane in range(n_lanes):
+                grids[lane, step] = estimator.at_time([host_times[i] for i in frames_of(lane, step)])
+                grids[lane, step].occupancy_accel()
+        torch.cuda.synchronize(device)
+
     def before_frame(lane, step):
+        if grids is not None:
+            lanes[lane].estimator = grids[lane, step]
         rs = [rays_of_frame(i) for i in frames_of(lane, step)]
         lanes[lane].set_rays(torch.stack([r.origins for r in rs]), torch.stack([r.viewdirs for r in rs]))
 

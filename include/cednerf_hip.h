@@ -431,6 +431,39 @@ int ced_field_density_gradient_rays(const ced_field_desc *desc, int64_t n, const
                                     const float *timestamps, int32_t t_per_ray, float *sigma, float *grad, float *dlog,
                                     float *dlog_canonical, void *stream);
 
+/* ---- the density's maximum over windows of time, and occupancy slices made from it ----
+ * What a time-sliced occupancy grid is built from: n positions, B windows ("bins") of S probe times each, one launch.
+ *     out[b, p] = fmaxf over s = 0 .. S-1 of sigma(positions[p], times[b * S + s])
+ * The maximum starts from 0.0f.  sigma has ced_field_forward's bits in the descriptor's arithmetic (desc->mlp_precision,
+ * either f16x2 layout, time_mode 0 / 1 / 2, use_div_offsets on and off, fp32 / fp16 / temporal tables), 0 outside the box.
+ * fmaxf ignores a NaN density: a cell whose density is NaN at every probe keeps 0, as `occs > thre` is false for a NaN.
+ * times [B * S] floats on the device (each in [0, 1], as for ced_field_forward), out [B, n] floats.  A wave keeps its rows'
+ * positions and running maxima in registers across the whole loop: besides positions, times and out only the hash table's
+ * gathers touch device memory; a probe time that equals the one before it bit for bit is not evaluated twice.  Limits: 1 <= B <= CED_TIME_MAX_BINS, 1 <= S <= CED_TIME_MAX_TIMES, n >= 0; n == 0 launches
+ * nothing.  A row's outputs do not depend on n or on the other rows. */
+#define CED_TIME_MAX_BINS 256
+#define CED_TIME_MAX_TIMES 64
+int ced_field_density_time_max(const ced_field_desc *desc, int64_t n, const float *positions, int32_t n_bins,
+                               int32_t n_times, const float *times, float *out, void *stream);
+
+/* B occupancy grids [levels, R, R, R] from those maxima.  cell_ids [n] int64 lists the probed cells as level * R^3 + cell
+ * (cell = (ix * R + iy) * R + iz), max_sigma [B, n] their maxima.  With M = levels * R^3:
+ *     hit[b, id]    = __fmul_rn(max_sigma[b, p], step_size) > thre   for id = cell_ids[p], 0 for a cell that is not listed
+ *                     (false for a NaN; an id outside 0 .. M-1 is skipped)
+ *     out[b, l, c]  = (dilate == 0 ? hit[b, l, c] : OR of hit[b, l, c'] over the 3x3x3 neighbourhood c' of c inside level l)
+ *                     AND (union_binaries == NULL or union_binaries[l, c] != 0)
+ * out [B, levels, R, R, R] bytes (1 / 0), union_binaries [levels, R, R, R] bytes or NULL.  Two plain kernels (mark, then
+ * dilate / AND), no atomics: a cell's byte is written by the one row that lists it; listing a cell twice is allowed only
+ * with equal maxima.  workspace holds hit: ced_occ_time_slices_workspace_bytes(B, levels, R) bytes of device memory
+ * (negative for sizes outside 1 <= B <= CED_TIME_MAX_BINS, 1 <= levels <= 64, 1 <= R <= 1024), ZEROED BY THE CALLER before
+ * the first call of a build.  out == NULL marks only: a build may hand its rows over in several calls (max_sigma is then
+ * [B, n] of that call's rows) and passes out with the last, which marks its rows and then writes every slice.  dilate is
+ * 0 or 1. */
+int64_t ced_occ_time_slices_workspace_bytes(int32_t n_bins, int32_t levels, int32_t res);
+int ced_occ_time_slices(int64_t n, const int64_t *cell_ids, const float *max_sigma, int32_t n_bins, float step_size,
+                        float thre, int32_t levels, int32_t res, const uint8_t *union_binaries, int32_t dilate,
+                        uint8_t *out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* DNGPradianceField._query_rgb(dir, embedding, apply_act) -- cednerf/model.py:447-466: dirs [n,3] are normalised,
  * mapped to [0,1], SH degree 2; mlp_head on [SH(4), embedding(15)]; the sigmoid iff apply_act.  embedding [n,15] is what
  * ced_field_forward writes to `geo`; rgb [n,3].  The head runs in the arithmetic of desc->mlp_precision. */
