@@ -211,6 +211,36 @@ def test_hash_entries_report_descriptor_errors():
             assert (rc, L.ced_last_error_string().decode()) == (-1, want), (dtype, temporal, total)
 
 
+def test_time_max_reports_table_errors():
+    """ced_field_density_time_max asks of the hash table what the density-gradient pair asks, in the same words: sixteen
+    levels (the twelve-level table of test_per_sample_entries_report_the_same_argument_errors) and the 32-bit byte-offset
+    limit (the sixteen-level table of test_hash_entries_report_descriptor_errors).  Sizes and pointers are valid; both
+    cases return before a launch, so host pointers stand in for device memory."""
+    from ced_nerf_amd import _lib
+    L = _lib.lib()
+    buf = (C.c_float * 64)()
+    ptr = C.cast(buf, C.c_void_p)
+
+    def desc(n_levels, total_entries):
+        d = _lib.FieldDesc()
+        d.packed_weights = ptr
+        d.packed_floats = L.ced_packed_weight_words(0, 0, 0)
+        d.hash.n_levels, d.hash.table, d.hash.total_entries = n_levels, ptr, total_entries
+        for l in range(n_levels):
+            d.hash.scale[l], d.hash.res[l], d.hash.offset[l], d.hash.size[l], d.hash.hashed[l] = 1.0, 2, 8 * l, 8, 1
+        return d
+
+    def call(d):
+        rc = L.ced_field_density_time_max(C.byref(d), 4, ptr, 2, 3, ptr, ptr, None)
+        return rc, L.ced_last_error_string().decode()
+
+    assert call(desc(12, 8 * 12)) == (-1, "field_density_time_max: the kernel needs n_levels == 16 (got 12)")
+    for dtype, temporal in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        d = desc(16, (1 << 32) // ((4 if dtype else 8) * (4 if temporal else 1)))
+        d.hash.table_dtype, d.hash.temporal = dtype, temporal
+        assert call(d) == (-1, "field_density_time_max: hash table larger than 4 GiB"), (dtype, temporal)
+
+
 def test_closed_form_skip_matches_sequential_recurrence(oracle):
     """ced_host_skip_march runs the kernels' skip code on the host: the O(#binades) closed form for
     cone_angle == 0 must land on exactly the float the oracle's step-by-step loop reaches."""
@@ -481,34 +511,43 @@ def test_built_library_has_no_src1_high_op_sel_packed_fp32():
     assert not bad, f"kernels with a src1-high op_sel packed-fp32 instruction: {sorted(bad)}"
 
 
-def test_default_field_kernels_fit_their_launch_geometry():
-    """The automatic launch geometry of the field kernels (field.hip / field_half.hip: workgroup size per arithmetic and
-    table kind) is chosen so that the kernel runs WITHOUT scratch at that many waves per SIMD.  hipcc's register allocation
-    of these kernels is sensitive to their code shape (round 4: 168 registers + scratch became 107-145 after an unrelated
-    edit), so the built code objects are checked: kernel (template arguments) -> registers allowed, spilt registers allowed."""
+def _kernel_notes(path):
+    """kernel name -> (vgpr_count, vgpr_spill_count, private_segment_fixed_size) from the metadata notes of the code
+    objects inside a built library; None where llvm-readelf is missing.  Reads metadata only."""
     import importlib.util
     import re
     import shutil
     import subprocess
     import tempfile
-    from ced_nerf_amd import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(root, "tools", "isa_lint.py"))
     lint = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(lint)
     readelf = os.path.join(os.path.dirname(lint.OBJDUMP), "llvm-readelf")
     if not (os.path.exists(readelf) or shutil.which(readelf)):
-        pytest.skip("llvm-readelf not found")
+        return None
     stats = {}
-    for image in lint.code_objects(_lib.build()):
+    for image in lint.code_objects(path):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(image)
             f.flush()
             notes = subprocess.run([readelf, "--notes", f.name], capture_output=True, text=True, check=True).stdout
         for blk in notes.split("- .agpr_count")[1:]:
             name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-            stats[name] = (int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)),
-                           int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)))
+            stats[name] = tuple(int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
+                                for key in ("vgpr_count", "vgpr_spill_count", "private_segment_fixed_size"))
+    return stats
+
+
+def test_default_field_kernels_fit_their_launch_geometry():
+    """The automatic launch geometry of the field kernels (field.hip / field_half.hip: workgroup size per arithmetic and
+    table kind) is chosen so that the kernel runs WITHOUT scratch at that many waves per SIMD.  hipcc's register allocation
+    of these kernels is sensitive to their code shape (round 4: 168 registers + scratch became 107-145 after an unrelated
+    edit), so the built code objects are checked: kernel (template arguments) -> registers allowed, spilt registers allowed."""
+    from ced_nerf_amd import _lib
+    stats = _kernel_notes(_lib.build())
+    if stats is None:
+        pytest.skip("llvm-readelf not found")
     half = "_ZN3ced17field_half_kernelILb{te}ELb{f16}ELb{temporal}ELb{split}ELi2ELi{threads}EEEvNS_9FieldArgsE"
     f32 = "_ZN3ced12field_kernelILb{te}ELb{f16}ELb{temporal}ELi2ELi{threads}ELb{head16}EEEvNS_9FieldArgsE"
     want = []
@@ -525,6 +564,21 @@ def test_default_field_kernels_fit_their_launch_geometry():
     for name, regs, spills in want:
         assert name in stats, f"{name} not in the built library"
         assert stats[name][0] <= regs and stats[name][1] <= spills, f"{name}: {stats[name][0]} registers, {stats[name][1]} spilt"
+
+
+def test_canonical_density_ops_run_without_scratch():
+    """DESIGN 4.1d / 4.1f, "no scratch in any": the two ops on the canonical density (field_density_device.hpp) are built
+    for eight table kinds x three staged planes each, and none of the 24 + 24 kernels spills a register or has a private
+    segment."""
+    from ced_nerf_amd import _lib
+    stats = _kernel_notes(_lib.build())
+    if stats is None:
+        pytest.skip("llvm-readelf not found")
+    for op in ("GradientOp", "TimeMaxOp"):
+        kernels = {name: s for name, s in stats.items() if op in name}
+        assert len(kernels) == 24, f"{op}: {len(kernels)} kernels in the built library"
+        for name, (_, spilt, private) in kernels.items():
+            assert spilt == 0 and private == 0, f"{name}: {spilt} spilt registers, {private} B private segment"
 
 
 def test_reference_checkpoint_layout_round_trip_cpu(tmp_path):
