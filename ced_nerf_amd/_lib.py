@@ -149,7 +149,7 @@ PROTOTYPES = {
     "ced_composite_test": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     "ced_finalize_pixels": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
     "ced_occ_cell_points": (C.c_int, [_i64, _vp, _vp, _i32, C.POINTER(C.c_float), _vp, _vp]),
-    "ced_occ_ema_update": (C.c_int, [_i64, _vp, _vp, _f, _f, _vp, _vp]),
+    "ced_occ_ema_update": (C.c_int, [_i64, _vp, _vp, _f, _f, _vp, _vp, _i64, _vp]),
     "ced_occ_time_slices_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ced_occ_time_slices": (C.c_int, [_i64, _vp, _vp, _i32, _f, _f, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "ced_generate_rays_pinhole": (C.c_int, [_i32, _i32, _f, _f, _f, _f, C.POINTER(C.c_float), _i32, _vp, _vp, _vp, _vp]),

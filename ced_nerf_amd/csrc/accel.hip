@@ -240,17 +240,22 @@ static void host_build_cells(const uint8_t *binaries, int n_grids, int res, cons
                 out[col * res + z] = (uint8_t)std::min((int)out[col * res + z], dmin);
             }
         }
+        // a z row at a time: the neighbours k steps along y or x of a whole row are a whole row, so the inner loops run
+        // over contiguous bytes.  max(k, .) >= k: the kernel's early exit "while k < best" leaves out only no-ops.
         for (int axis = 1; axis >= 0; --axis) {
             const int64_t stride = axis == 0 ? (int64_t)res * res : res;
-            for (int64_t i = 0; i < n; ++i) {
-                const int y = (int)((i / res) % res), x = (int)(i / ((int64_t)res * res));
-                const int pos = axis == 0 ? x : y;
-                int best = out[i];
-                for (int k = 1; k < best && k <= kCellCap; ++k) {
-                    if (pos - k >= 0) best = std::min(best, std::max(k, (int)out[i - k * stride]));
-                    if (pos + k < res) best = std::min(best, std::max(k, (int)out[i + k * stride]));
+            for (int64_t row = 0; row < (int64_t)res * res; ++row) {
+                const int pos = axis == 0 ? (int)(row / res) : (int)(row % res);
+                const uint8_t *src = out + row * res;
+                uint8_t *best = tmp.data() + row * res;
+                for (int z = 0; z < res; ++z) best[z] = src[z];
+                for (int k = 1; k <= kCellCap; ++k) {
+                    for (int side = -1; side <= 1; side += 2) {
+                        if (pos + side * k < 0 || pos + side * k >= res) continue;
+                        const uint8_t *nbr = src + side * k * stride;
+                        for (int z = 0; z < res; ++z) best[z] = std::min(best[z], std::max((uint8_t)k, nbr[z]));
+                    }
                 }
-                tmp[(size_t)i] = (uint8_t)best;
             }
             for (int64_t i = 0; i < n; ++i) out[i] = tmp[(size_t)i];
         }

@@ -1,7 +1,8 @@
 // Occupancy-grid maintenance: the device side of
 // nerfacc.OccGridEstimator._update / update_every_n_steps as driven at train_real.py:324-336.
 // nerfacc itself does these steps with torch ops; here the two per-sample pieces around the density
-// query are single launches: cell index + jitter -> world position, and the EMA-max write-back.
+// query are native: cell index + jitter -> world position (one launch), and the EMA-max write-back (three
+// small ones, so that a cell listed several times decays once and takes the largest of its samples).
 #include "ced_common.hpp"
 
 namespace ced {
@@ -25,16 +26,45 @@ __global__ __launch_bounds__(256) void occ_points_kernel(int64_t n, const int64_
     pos[3 * i + 2] = a2 + z * e2;
 }
 
-// occs[id] = max(occs[id] * decay, density * step)   (one writer per sample, like the index_put it replaces)
-__global__ __launch_bounds__(256) void occ_ema_kernel(int64_t n, const int64_t *__restrict__ cell_ids,
-                                                      const float *__restrict__ density, float step_size, float decay,
-                                                      float *__restrict__ occs)
+// EMA write-back, occs[c] = fmax(occs[c] * decay, max over the samples of c of density * step), for a list that may name
+// a cell any number of times (the sampled draw is with replacement and then appends the occupied cells).  Three launches,
+// none of which reads a cell after a write to it:
+//   gather : decayed[i] = occs[id_i] * decay               reads occs, writes the workspace
+//   spread : occs[id_i] = decayed[i]                        the writers of one cell all store the same bits
+//   max    : occs[id_i] = max(occs[id_i], density_i * step) an integer atomic on the float's bits, so any order of the
+//                                                           writers leaves the largest; a NaN sample is skipped (fmaxf)
+__global__ __launch_bounds__(256) void occ_ema_gather_kernel(int64_t n, const int64_t *__restrict__ cell_ids, float decay,
+                                                             const float *__restrict__ occs, float *__restrict__ decayed)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int64_t id = cell_ids[i];
-    const float occ = density[i] * step_size;
-    occs[id] = __builtin_fmaxf(occs[id] * decay, occ);
+    const float v = __fmul_rn(occs[cell_ids[i]], decay);
+    // a NaN loses against every sample (fmaxf): the pattern below is under both atomics of the max kernel, and still a NaN
+    decayed[i] = v == v ? v : __uint_as_float(0xffffffffu);
+}
+
+__global__ __launch_bounds__(256) void occ_ema_spread_kernel(int64_t n, const int64_t *__restrict__ cell_ids,
+                                                             const float *__restrict__ decayed, float *__restrict__ occs)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    occs[cell_ids[i]] = decayed[i];
+}
+
+// Floats without the sign bit order like their bits as signed integers (and above every pattern with the sign bit);
+// floats with it order opposite to their bits as unsigned integers (and below every pattern without it).  -0 < +0.
+__global__ __launch_bounds__(256) void occ_ema_max_kernel(int64_t n, const int64_t *__restrict__ cell_ids,
+                                                          const float *__restrict__ density, float step_size,
+                                                          float *__restrict__ occs)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float occ = __fmul_rn(density[i], step_size);
+    if (occ != occ) return;
+    const unsigned int b = __float_as_uint(occ);
+    float *cell = occs + cell_ids[i];
+    if (b >> 31) atomicMin(reinterpret_cast<unsigned int *>(cell), b);
+    else atomicMax(reinterpret_cast<int *>(cell), (int)b);
 }
 
 // Time slices (ced_occ_time_slices), first kernel: hit[b, cell_ids[p]] = max_sigma[b, p] * step_size > thre.  One thread per
@@ -127,12 +157,17 @@ extern "C" int ced_occ_cell_points(int64_t n, const int64_t *cell_indices, const
 }
 
 extern "C" int ced_occ_ema_update(int64_t n, const int64_t *cell_ids, const float *density, float step_size,
-                                  float ema_decay, float *occs, void *stream)
+                                  float ema_decay, float *occs, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    CED_REQUIRE(n >= 0, "occ_ema_update: n < 0");
+    CED_REQUIRE(n >= 0 && n / 256 < 2147483647, "occ_ema_update: n=%lld outside one launch", (long long)n);
     if (n == 0) return CED_OK;
     CED_REQUIRE(cell_ids && density && occs, "occ_ema_update: null pointer");
-    hipLaunchKernelGGL(ced::occ_ema_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
-                       cell_ids, density, step_size, ema_decay, occs);
+    CED_REQUIRE(workspace && workspace_bytes >= n * (int64_t)sizeof(float), "occ_ema_update: workspace too small (%lld < %lld bytes)",
+                (long long)workspace_bytes, (long long)(n * (int64_t)sizeof(float)));
+    float *decayed = reinterpret_cast<float *>(workspace);
+    const dim3 grd((unsigned)((n + 255) / 256)), blk(256);
+    hipLaunchKernelGGL(ced::occ_ema_gather_kernel, grd, blk, 0, (hipStream_t)stream, n, cell_ids, ema_decay, occs, decayed);
+    hipLaunchKernelGGL(ced::occ_ema_spread_kernel, grd, blk, 0, (hipStream_t)stream, n, cell_ids, decayed, occs);
+    hipLaunchKernelGGL(ced::occ_ema_max_kernel, grd, blk, 0, (hipStream_t)stream, n, cell_ids, density, step_size, occs);
     return ced::check_launch("occ_ema_update");
 }

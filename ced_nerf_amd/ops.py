@@ -1455,11 +1455,13 @@ def occ_cell_points(cell_indices: torch.Tensor, noise: torch.Tensor, res: int, a
 
 def occ_ema_update_(occs: torch.Tensor, cell_ids: torch.Tensor, density: torch.Tensor, step_size: float,
                     ema_decay: float) -> None:
-    """occs[cell_ids] = max(occs[cell_ids] * ema_decay, density * step_size), in place."""
+    """ced_occ_ema_update, in place: every listed cell c of occs becomes fmax(occs[c] * ema_decay, the largest
+    density * step_size among its entries of cell_ids); cell_ids may repeat cells, in any order."""
     _chk(occs, torch.float32, "occs"); _chk(cell_ids, torch.int64, "cell_ids"); _chk(density, torch.float32, "density")
-    assert density.shape == cell_ids.shape
+    assert cell_ids.ndim == 1 and density.shape == cell_ids.shape
+    decayed = torch.empty_like(density)                          # the call's workspace
     rc = _lib.lib().ced_occ_ema_update(cell_ids.shape[0], _p(cell_ids), _p(density), float(step_size), float(ema_decay),
-                                       _p(occs), _stream())
+                                       _p(occs), _p(decayed), decayed.numel() * 4, _stream())
     _lib.check(rc, "occ_ema_update")
 
 

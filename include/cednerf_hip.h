@@ -713,10 +713,14 @@ int ced_finalize_pixels(int64_t n_rays, const float *bkgd, float *rgb, const flo
 int ced_occ_cell_points(int64_t n, const int64_t *cell_indices, const float *noise, int32_t res,
                         const float *aabb_host, float *positions, void *stream);
 
-/* occs[cell_ids[i]] = max(occs[cell_ids[i]] * ema_decay, density[i] * step_size)  (the EMA write-back of
- * _update; duplicates in cell_ids race exactly like the index assignment they replace). */
+/* The EMA write-back of _update, for any cell_ids (the sampled draw lists cells several times): every listed cell c
+ * becomes  fmax(occs[c] * ema_decay, max over i with cell_ids[i] == c of density[i] * step_size)  -- it decays once and
+ * takes the largest of its samples, whatever the order of the list; a NaN sample contributes nothing (fmaxf), unlisted
+ * cells keep their bits.  Of the outcomes the index assignment it replaces can have with duplicates, this is the one
+ * that does not depend on the order of the writers, so a call is reproducible.  cell_ids must lie inside occs.
+ * workspace: n floats of device memory (workspace_bytes >= 4 * n), overwritten. */
 int ced_occ_ema_update(int64_t n, const int64_t *cell_ids, const float *density, float step_size,
-                       float ema_decay, float *occs, void *stream);
+                       float ema_decay, float *occs, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- on-device ray generation: full-frame rays from camera parameters, so no
  * [H,W,3] x 2 upload per frame.  Outputs [height*width, 3] row-major (pixel x fastest), i.e. Rays of

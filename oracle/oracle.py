@@ -427,7 +427,9 @@ class OracleEstimator:
 def occ_grid_update(occs, aabbs, res, lvl_indices, lvl_noise, occ_eval_fn, occ_thre=0.01, ema_decay=0.95):
     """nerfacc OccGridEstimator._update with the random draws supplied:
     x = aabb_min + (coord + noise)/res * extent; occs[id] = max(occs[id]*decay, occ_eval_fn(x));
-    binaries = occs > min(mean(occs[occs >= 0]), occ_thre).  float32 throughout; returns (occs, binaries)."""
+    binaries = occs > min(mean(occs[occs >= 0]), occ_thre).  float32 throughout; returns (occs, binaries).
+    A cell listed several times (the sampled draw is with replacement) decays once and takes the largest of its samples:
+    of the outcomes nerfacc's index assignment can have, the one that does not depend on the order of the writers."""
     f32 = np.float32
     occs = occs.astype(f32).copy()
     cells = res ** 3
@@ -441,7 +443,9 @@ def occ_grid_update(occs, aabbs, res, lvl_indices, lvl_noise, occ_eval_fn, occ_t
         pos = (ab[:3] + x * (ab[3:] - ab[:3])).astype(f32)
         occ = occ_eval_fn(pos).astype(f32)
         ids = lvl * cells + idx
-        occs[ids] = np.maximum((occs[ids] * f32(ema_decay)).astype(f32), occ)
+        listed = np.unique(ids)
+        occs[listed] = (occs[listed] * f32(ema_decay)).astype(f32)
+        np.maximum.at(occs, ids, occ)
     visible = occs[occs >= 0]
     thre = min(f32(visible.astype(np.float64).mean()) if visible.size else f32(0), f32(occ_thre))
     return occs, occs > thre
