@@ -212,10 +212,15 @@ __global__ __launch_bounds__(256) void finalize_kernel(int64_t n_rays, const flo
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // Backward of the training-time compositing: d(colors, opacities, depths)/d(sigmas, rgbs) of
-// cednerf/render.py:158-169.  One lane per ray, two sweeps: forward for the total optical depth, then backward
-// with the suffix sum S_i = sum_{k>i} g_k w_k:
+// cednerf/render.py:158-169.  One lane per ray, two sweeps.  The forward sweep is render_weights_kernel's: it sums the
+// optical depth in sample order and keeps T_i = det_expf(-acc_i) in d_sig[i] -- the output buffer is the scratch, as in
+// ray_density (losses.hip); nothing outside the ray's [s0, s0 + cnt) is touched.  The reverse sweep reads T_i back before
+// it overwrites the slot, takes a_i with det_expf, so that w_i = T_i a_i is the forward kernel's weight bit for bit, and
+// carries the suffix sum S_i = sum_{k>i} g_k w_k:
 //   g_i = <d_color, rgb_i> + d_opacity + d_depth * t_mid_i,   d rgb_i = w_i d_color,
 //   d sigma_i = dt_i * (g_i (T_i - w_i) - S_i).
+// (Recovering the prefix by subtracting back from the ray's total instead costs one ulp of the TOTAL in every prefix:
+//  in front of a dense surface T_i, and with it d sigma_i, was off by up to 1e-2 relative.)
 __global__ __launch_bounds__(256) void composite_backward_kernel(int64_t n_rays, const int64_t *__restrict__ packed,
                                                                  const float *__restrict__ t0, const float *__restrict__ t1,
                                                                  const float *__restrict__ sig, const float *__restrict__ rgbs,
@@ -230,17 +235,18 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(int64_t n_rays,
     if (cnt <= 0) return;
     const float dc0 = d_color[3 * r], dc1 = d_color[3 * r + 1], dc2 = d_color[3 * r + 2];
     const float dop = d_opacity ? d_opacity[r] : 0.0f, ddp = d_depth ? d_depth[r] : 0.0f;
-    float total = 0.0f;
-    for (int64_t i = s0; i < s0 + cnt; ++i) total = total + sig[i] * (t1[i] - t0[i]);
-    float acc_after = total, suffix = 0.0f;
+    float acc = 0.0f;
+    for (int64_t i = s0; i < s0 + cnt; ++i) {
+        d_sig[i] = det_expf(-acc);
+        acc = acc + sig[i] * (t1[i] - t0[i]);
+    }
+    float suffix = 0.0f;
     for (int64_t i = s0 + cnt - 1; i >= s0; --i) {
         const float ts = t0[i], te = t1[i];
         const float dt = te - ts;
         const float sd = sig[i] * dt;
-        // optical depth before the sample; the first sample's is exactly 0 (no cancellation residue in T_0 = 1)
-        const float acc_before = (i == s0) ? 0.0f : (acc_after - sd);
-        const float T = __expf(-acc_before);
-        const float a = 1.0f - __expf(-sd);
+        const float T = d_sig[i];
+        const float a = 1.0f - det_expf(-sd);
         const float w = T * a;
         const float g = ((dc0 * rgbs[3 * i] + dc1 * rgbs[3 * i + 1]) + dc2 * rgbs[3 * i + 2]) + dop + ddp * ((ts + te) * 0.5f);
         d_sig[i] = dt * (g * (T - w) - suffix);
@@ -248,7 +254,6 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(int64_t n_rays,
         d_rgbs[3 * i + 1] = w * dc1;
         d_rgbs[3 * i + 2] = w * dc2;
         suffix = suffix + g * w;
-        acc_after = acc_before;
     }
 }
 
@@ -393,8 +398,8 @@ extern "C" int ced_composite_test(int64_t n_alive, const float *sigmas, const fl
 {
     CED_REQUIRE(n_alive >= 0, "composite_test: n_alive < 0");
     if (n_alive == 0) return CED_OK;
-    CED_REQUIRE(sigmas && rgbs && t_start && t_end && pack_info && alive_indices && opacity && depth && rgb,
-                "composite_test: null pointer");
+    // (the sample arrays may be empty, i.e. NULL, when no entry has a step: every entry then only gets alive = -1)
+    CED_REQUIRE(pack_info && alive_indices && opacity && depth && rgb, "composite_test: null pointer");
     hipLaunchKernelGGL(ced::composite_test_kernel, ced::grid_for(n_alive), dim3(256), 0, (hipStream_t)stream, n_alive,
                        sigmas, rgbs, t_start, t_end, pack_info, alive_indices, T_threshold, alpha_threshold, opacity,
                        depth, rgb);

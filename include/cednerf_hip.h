@@ -575,7 +575,9 @@ int ced_composite_prefix(int64_t n_rays, const int64_t *packed_info, const float
  * (colors, opacities, depths) = accumulate_along_rays(render_weight_from_density(...), {rgbs, 1, t_mid}) of
  * cednerf/render.py:158-169 w.r.t. the per-sample sigmas [S] and rgbs [S,3], given d_color [n_rays,3],
  * d_opacity [n_rays] and d_depth [n_rays] (the last two may be NULL = zero).  Replaces the backward of nerfacc's
- * render_weight_from_density / accumulate_along_rays autograd functions. */
+ * render_weight_from_density / accumulate_along_rays autograd functions.  d_sigmas doubles as the kernel's scratch (it
+ * holds each sample's transmittance between the two sweeps), so it must not alias an input; the weights the backward
+ * uses are ced_render_weights' bit for bit, and only the slots [start, start + count) of each ray are written. */
 int ced_composite_backward(int64_t n_rays, const int64_t *packed_info, const float *t_starts,
                            const float *t_ends, const float *sigmas, const float *rgbs,
                            const float *d_color, const float *d_opacity, const float *d_depth,
@@ -693,7 +695,8 @@ int ced_composite_step(int64_t n_rays, const int64_t *packed_info, const float *
                        void *stream);
 
 /* composite_test -- cednerf/taichi_kernel/volume_render_test.py:4-59 (same arguments, same
- * in-place semantics; alive_indices entries are set to -1 when a ray finishes). */
+ * in-place semantics; alive_indices entries are set to -1 when a ray finishes).  The four sample arrays may be NULL
+ * when no entry has a step (an empty sample set): every entry then only becomes -1. */
 int ced_composite_test(int64_t n_alive, const float *sigmas, const float *rgbs, const float *t_start,
                        const float *t_end, const int64_t *pack_info, int64_t *alive_indices,
                        float T_threshold, float alpha_threshold,
