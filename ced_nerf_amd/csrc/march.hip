@@ -17,11 +17,20 @@ __device__ __forceinline__ bool ray_aabb_one(const float o[3], const float inv_d
     else               { tmin = (aabb[3] - o[0]) * inv_d[0]; tmax = (aabb[0] - o[0]) * inv_d[0]; }
     if (inv_d[1] >= 0) { tymin = (aabb[1] - o[1]) * inv_d[1]; tymax = (aabb[4] - o[1]) * inv_d[1]; }
     else               { tymin = (aabb[4] - o[1]) * inv_d[1]; tymax = (aabb[1] - o[1]) * inv_d[1]; }
+    // A ray that lies in a face plane of the box (d_a == 0 and o_a on the plane) makes 0 * inf = NaN bounds on that axis;
+    // NaN compares false below and would drop an end of the interval (t_min = -inf or t_max = +inf: samples outside
+    // every box, or none behind a fine box).  The box is closed: such a ray is inside that slab for all t.
+    if (tmin != tmin) tmin = -__builtin_inff();
+    if (tmax != tmax) tmax = __builtin_inff();
+    if (tymin != tymin) tymin = -__builtin_inff();
+    if (tymax != tymax) tymax = __builtin_inff();
     if (tmin > tymax || tymin > tmax) return false;
     if (tymin > tmin) tmin = tymin;
     if (tymax < tmax) tmax = tymax;
     if (inv_d[2] >= 0) { tzmin = (aabb[2] - o[2]) * inv_d[2]; tzmax = (aabb[5] - o[2]) * inv_d[2]; }
     else               { tzmin = (aabb[5] - o[2]) * inv_d[2]; tzmax = (aabb[2] - o[2]) * inv_d[2]; }
+    if (tzmin != tzmin) tzmin = -__builtin_inff();
+    if (tzmax != tzmax) tzmax = __builtin_inff();
     if (tmin > tzmax || tzmin > tmax) return false;
     if (tzmin > tmin) tmin = tzmin;
     if (tzmax < tmax) tmax = tzmax;

@@ -171,7 +171,13 @@ __device__ __forceinline__ int traverse_ray(const GridSpec &G, const float (&o)[
             float tm = ((ab[a] + (((float)(cur[a] + idelta) * vox) - ps)) * inv_d[a]) + this_tmin;
             float stepf = (d[a] == 0.0f) ? 0.0f : (d[a] > 0.0f ? 1.0f : -1.0f);
             stp[a] = (int)stepf;
-            tdist[a] = (d[a] == 0.0f) ? this_tmax : tm;
+            // An axis on which the segment starts and ends in the same cell (cur == fin) has no crossing inside the segment.  A
+            // first boundary computed before te all the same (a ray that hugs a cell face with a tiny d_a stands within a
+            // rounding error of that face, and tm is then off by that error / |d_a|, even behind the start) is not a crossing:
+            // the one step it would take leads straight past the final cell and would end the segment there, dropping the
+            // rest of it.  Such an axis is treated as a d_a == 0 axis is.
+            bool no_crossing = d[a] == 0.0f || (cur[a] == fin && tm < te);
+            tdist[a] = no_crossing ? this_tmax : tm;
             delta[a] = (d[a] == 0.0f) ? this_tmax : (vox * inv_d[a]) * stepf;
             ovf[a] = fin + stp[a];
         }

@@ -128,11 +128,20 @@ static int ray_aabb_one(const float *o, const float *inv_d, const float *aabb,
     else               { tmin = (aabb[3] - o[0]) * inv_d[0]; tmax = (aabb[0] - o[0]) * inv_d[0]; }
     if (inv_d[1] >= 0) { tymin = (aabb[1] - o[1]) * inv_d[1]; tymax = (aabb[4] - o[1]) * inv_d[1]; }
     else               { tymin = (aabb[4] - o[1]) * inv_d[1]; tymax = (aabb[1] - o[1]) * inv_d[1]; }
+    /* A ray that lies in a face plane of the box (d_a == 0 and o_a on the plane) makes 0 * inf = NaN bounds on that axis;
+     * NaN compares false below and would drop an end of the interval (t_min = -inf or t_max = +inf: samples outside
+     * every box, or none behind a fine box).  The box is closed: such a ray is inside that slab for all t. */
+    if (tmin != tmin) tmin = -INFINITY;
+    if (tmax != tmax) tmax = INFINITY;
+    if (tymin != tymin) tymin = -INFINITY;
+    if (tymax != tymax) tymax = INFINITY;
     if (tmin > tymax || tymin > tmax) return 0;
     if (tymin > tmin) tmin = tymin;
     if (tymax < tmax) tmax = tymax;
     if (inv_d[2] >= 0) { tzmin = (aabb[2] - o[2]) * inv_d[2]; tzmax = (aabb[5] - o[2]) * inv_d[2]; }
     else               { tzmin = (aabb[5] - o[2]) * inv_d[2]; tzmax = (aabb[2] - o[2]) * inv_d[2]; }
+    if (tzmin != tzmin) tzmin = -INFINITY;
+    if (tzmax != tzmax) tzmax = INFINITY;
     if (tmin > tzmax || tzmin > tmax) return 0;
     if (tzmin > tmin) tmin = tzmin;
     if (tzmax < tmax) tmax = tzmax;
@@ -239,7 +248,13 @@ static int64_t traverse_one_ray(
             float tm = ((ab[a] + (((float)(cur[a] + idelta) * vox[a]) - ps)) * inv_d[a]) + this_tmin;
             float stepf = (d[a] == 0.0f) ? 0.0f : (d[a] > 0.0f ? 1.0f : -1.0f);
             stp[a] = (int)stepf;
-            tdist[a] = (d[a] == 0.0f) ? this_tmax : tm;
+            /* An axis on which the segment starts and ends in the same cell (cur == fin) has no crossing inside the segment.  A
+             * first boundary computed before te all the same (a ray that hugs a cell face with a tiny d_a stands within a
+             * rounding error of that face, and tm is then off by that error / |d_a|, even behind the start) is not a crossing:
+             * the one step it would take leads straight past the final cell and would end the segment there, dropping the
+             * rest of it.  Such an axis is treated as a d_a == 0 axis is. */
+            int no_crossing = d[a] == 0.0f || (cur[a] == fin[a] && tm < te);
+            tdist[a] = no_crossing ? this_tmax : tm;
             delta[a] = (d[a] == 0.0f) ? this_tmax : (vox[a] * inv_d[a]) * stepf;
             ovf[a] = fin[a] + stp[a];
         }
