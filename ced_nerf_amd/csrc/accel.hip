@@ -311,19 +311,20 @@ extern "C" int ced_host_march_frame(int64_t n_rays, const float *rays_o, const f
                                     int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes,
                                     float far_plane, float step_size, float cone_angle, int32_t limit,
                                     const float *t_sorted, const int64_t *t_indices, const uint8_t *hits,
-                                    const uint8_t *accel_host, int32_t accel_mode, int32_t use_lattice, int32_t start_coarse,
+                                    const uint8_t *accel_host, int32_t accel_mode, int32_t use_lattice, int32_t walk,
                                     int32_t *counts, float *t_starts, float *t_ends, float *t_term)
 {
     CED_REQUIRE(n_rays >= 0 && n_grids >= 1 && res >= 1 && limit >= 1, "host_march_frame: bad sizes");
     CED_REQUIRE(rays_o && rays_d && binaries && aabbs && near_planes && t_sorted && t_indices && hits && counts &&
                     t_starts && t_ends && t_term, "host_march_frame: null pointer");
     CED_REQUIRE(accel_mode >= 0 && accel_mode <= 2 && (accel_mode == 0 || accel_host), "host_march_frame: accel_mode 0 (none), 1 (bricks), 2 (cells)");
+    CED_REQUIRE(walk >= 0 && walk <= 3, "host_march_frame: walk 0..3");
     // use_lattice: every near plane must be a point of the lattice that starts at near_planes[0] (as in a frame:
     // the frame's near plane, or termination planes of earlier iterations)
     float lattice[256];
     if (use_lattice) ced::build_lattice(near_planes[0], step_size, lattice);
     const ced::GridSpec G{ binaries, aabbs, n_grids, res, step_size, cone_angle, limit,
-                           (use_lattice && cone_angle == 0.0f && step_size > 0.0f) ? lattice : nullptr };
+                           (use_lattice && walk != 3 && cone_angle == 0.0f && step_size > 0.0f) ? lattice : nullptr };
     ced::AccelSpec S{ nullptr, (res + ced::kBrick - 1) / ced::kBrick, nullptr };
     if (accel_mode) S = ced::accel_view(accel_host, n_grids, res, accel_mode == 2);
     for (int64_t r = 0; r < n_rays; ++r) {
@@ -334,13 +335,19 @@ extern "C" int ced_host_march_frame(int64_t n_rays, const float *rays_o, const f
         const float *ts = t_sorted + r * 2 * n_grids;
         const int64_t *ti = t_indices + r * 2 * n_grids;
         const uint8_t *hr = hits + r * n_grids;
-        // the kernels' instantiations: one grid level recomputes the ray/box interval, LOOK = 4 cells
-        if (n_grids == 1)
-            counts[r] = start_coarse == 1 ? ced::traverse_ray_frame<ced::kFrameLook, true, true>(G, S, true, o, d, near_planes[r], far_plane, ts, ti, hr, emit, t_term[r])
-                                          : ced::traverse_ray_frame<ced::kFrameLook, true, false>(G, S, start_coarse != 0, o, d, near_planes[r], far_plane, ts, ti, hr, emit, t_term[r]);
+        // the kernels' instantiations.  Frame renderer and one-shot march: LOOK = 4 cells, one grid level recomputes
+        // the ray/box interval; walk 1 traces first in the looking-loop form, walk 2 traces first, walk 0 does not.
+        // walk 3: traverse_ray, what ced_traverse_grids' kernel runs (LOOK = 8, every termination plane exact).
+        const float near = near_planes[r];
+        float &tt = t_term[r];
+        if (walk == 3)
+            counts[r] = ced::traverse_ray(G, o, d, near, far_plane, ts, ti, hr, emit, tt);
+        else if (n_grids == 1)
+            counts[r] = walk == 1 ? ced::traverse_ray_frame<ced::kFrameLook, true, true>(G, S, true, o, d, near, far_plane, ts, ti, hr, emit, tt)
+                                  : ced::traverse_ray_frame<ced::kFrameLook, true, false>(G, S, walk != 0, o, d, near, far_plane, ts, ti, hr, emit, tt);
         else
-            counts[r] = start_coarse == 1 ? ced::traverse_ray_frame<ced::kFrameLook, false, true>(G, S, true, o, d, near_planes[r], far_plane, ts, ti, hr, emit, t_term[r])
-                                        : ced::traverse_ray_frame<ced::kFrameLook, false, false>(G, S, start_coarse != 0, o, d, near_planes[r], far_plane, ts, ti, hr, emit, t_term[r]);
+            counts[r] = walk == 1 ? ced::traverse_ray_frame<ced::kFrameLook, false, true>(G, S, true, o, d, near, far_plane, ts, ti, hr, emit, tt)
+                                  : ced::traverse_ray_frame<ced::kFrameLook, false, false>(G, S, walk != 0, o, d, near, far_plane, ts, ti, hr, emit, tt);
     }
     return CED_OK;
 }

@@ -32,7 +32,7 @@ struct CandidateOp {
     }
 
     // The smallest level whose box contains the centre (faces included) decides, with the marcher's point-to-cell
-    // expression (march_core.hpp traverse_ray: clamp((int)(((p - min) / extent) * res), 0, res - 1)).
+    // expression (march_accel.hpp dda_setup: clamp((int)(((p - min) / extent) * res), 0, res - 1)).
     __device__ __forceinline__ bool keep(int64_t k) const
     {
         if (!binaries) return true;

@@ -460,34 +460,19 @@ __global__ __launch_bounds__(kCullThreads) void march_cull_kernel(MarchArgs A, I
 #pragma unroll
             for (int a = 0; a < 3; ++a) { o[a] = A.rays_o[3 * r + a]; d[a] = A.rays_d[3 * r + a]; }
             const float near = A.near_planes[r];
-            if constexpr (SINGLE) {
-                const float inv_d[3] = { 1.0f / d[0], 1.0f / d[1], 1.0f / d[2] };
+            const float inv_d[3] = { 1.0f / d[0], 1.0f / d[1], 1.0f / d[2] };
+            // the segments traverse_ray_frame visits, in its order (decode_segment)
+            const float *ts_row = SINGLE ? nullptr : A.t_sorted + r * 2 * m;
+            const uint8_t *ti_row = SINGLE ? nullptr : A.t_indices + r * 2 * m;
+            const uint8_t *hit_row = SINGLE ? nullptr : A.hits + r * m;
+            for (int i = 0; i < 2 * m - 1 && !cand; ++i) {
+                int lvl;
                 float seg_a, seg_b;
-                if (slab_test(o, inv_d, A.grid.aabbs, seg_a, seg_b)) {
-                    const float t0 = fmaxf(seg_a, near), t1 = fminf(seg_b, A.far_plane);
-                    float t_stop, cells;
-                    if (t0 < t1) cand = !coarse_advance(A.accel, 0, res, A.grid.aabbs, o, d, t0, t1, t_stop, cells);
-                }
-            } else {
-                // the segments traverse_ray_frame visits, in its order (nerfacc's sorted entry / exit events)
-                const float *ts_row = A.t_sorted + r * 2 * m;
-                const uint8_t *ti_row = A.t_indices + r * 2 * m;
-                const uint8_t *hit_row = A.hits + r * m;
-                for (int i = 0; i < 2 * m - 1 && !cand; ++i) {
-                    const int ti = ti_row[i];
-                    int lvl = (int)(ti % m);
-                    if (!hit_row[lvl]) continue;
-                    if (!(ti < m)) {
-                        const int tn = ti_row[i + 1];
-                        if (tn < m) continue;
-                        lvl = (int)(tn % m);
-                        if (!hit_row[lvl]) continue;
-                    }
-                    const float t0 = fmaxf(ts_row[i], near), t1 = fminf(ts_row[i + 1], A.far_plane);
-                    if (t0 >= t1) continue;
-                    float t_stop, cells;
-                    cand = !coarse_advance(A.accel, lvl, res, A.grid.aabbs + 6 * lvl, o, d, t0, t1, t_stop, cells);
-                }
+                if (!decode_segment<SINGLE>(A.grid, o, inv_d, ts_row, ti_row, hit_row, i, lvl, seg_a, seg_b)) continue;
+                const float t0 = fmaxf(seg_a, near), t1 = fminf(seg_b, A.far_plane);
+                if (t0 >= t1) continue;
+                float t_stop, cells;
+                cand = !coarse_advance(A.accel, lvl, res, A.grid.aabbs + 6 * lvl, o, d, t0, t1, t_stop, cells);
             }
             if (!cand) { A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0; }
         }

@@ -1,44 +1,13 @@
-// Occupancy-grid ray marching: ray/AABB slab test and multi-level DDA traversal.
+// Occupancy-grid ray marching, the nerfacc-shaped entries: ray/AABB intersection, event sort and multi-level traversal.
 // Replaces nerfacc.ray_aabb_intersect / nerfacc.traverse_grids (un-vendored CUDA ops) at the call
 // sites cednerf/utils.py:215 and cednerf/utils.py:241-264 (and, through OccGridEstimator.sampling,
-// cednerf/utils.py:115-125) of the reference.  One lane per ray; integer outputs are bit-exact
-// with the oracle because every float operation below is a single IEEE op in a fixed order
-// (-ffp-contract=off) -- do not "simplify" the arithmetic.
+// cednerf/utils.py:115-125) of the reference.  One lane per ray.  The slab test (march_core.hpp) and the pieces of the
+// walk (traverse_ray, march_accel.hpp) are the frame renderer's: every float operation there is a single IEEE op in a
+// fixed order (-ffp-contract=off), bit-exact with the oracle.
 #include "ced_common.hpp"
-#include "march_core.hpp"
+#include "march_accel.hpp"
 
 namespace ced {
-
-__device__ __forceinline__ bool ray_aabb_one(const float o[3], const float inv_d[3], const float *__restrict__ aabb,
-                                             float near, float far, float &tmin_out, float &tmax_out)
-{
-    float tmin, tmax, tymin, tymax, tzmin, tzmax;
-    if (inv_d[0] >= 0) { tmin = (aabb[0] - o[0]) * inv_d[0]; tmax = (aabb[3] - o[0]) * inv_d[0]; }
-    else               { tmin = (aabb[3] - o[0]) * inv_d[0]; tmax = (aabb[0] - o[0]) * inv_d[0]; }
-    if (inv_d[1] >= 0) { tymin = (aabb[1] - o[1]) * inv_d[1]; tymax = (aabb[4] - o[1]) * inv_d[1]; }
-    else               { tymin = (aabb[4] - o[1]) * inv_d[1]; tymax = (aabb[1] - o[1]) * inv_d[1]; }
-    // A ray that lies in a face plane of the box (d_a == 0 and o_a on the plane) makes 0 * inf = NaN bounds on that axis;
-    // NaN compares false below and would drop an end of the interval (t_min = -inf or t_max = +inf: samples outside
-    // every box, or none behind a fine box).  The box is closed: such a ray is inside that slab for all t.
-    if (tmin != tmin) tmin = -__builtin_inff();
-    if (tmax != tmax) tmax = __builtin_inff();
-    if (tymin != tymin) tymin = -__builtin_inff();
-    if (tymax != tymax) tymax = __builtin_inff();
-    if (tmin > tymax || tymin > tmax) return false;
-    if (tymin > tmin) tmin = tymin;
-    if (tymax < tmax) tmax = tymax;
-    if (inv_d[2] >= 0) { tzmin = (aabb[2] - o[2]) * inv_d[2]; tzmax = (aabb[5] - o[2]) * inv_d[2]; }
-    else               { tzmin = (aabb[5] - o[2]) * inv_d[2]; tzmax = (aabb[2] - o[2]) * inv_d[2]; }
-    if (tzmin != tzmin) tzmin = -__builtin_inff();
-    if (tzmax != tzmax) tzmax = __builtin_inff();
-    if (tmin > tzmax || tzmin > tmax) return false;
-    if (tzmin > tmin) tmin = tzmin;
-    if (tzmax < tmax) tmax = tzmax;
-    if (tmax <= 0) return false;
-    tmin_out = __builtin_fmaxf(tmin, near);
-    tmax_out = __builtin_fminf(tmax, far);
-    return true;
-}
 
 __global__ __launch_bounds__(256) void ray_aabb_kernel(int64_t n_rays, const float *__restrict__ rays_o,
                                                        const float *__restrict__ rays_d, int n_aabbs,
@@ -48,14 +17,13 @@ __global__ __launch_bounds__(256) void ray_aabb_kernel(int64_t n_rays, const flo
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
-    float o[3] = { rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2] };
-    float inv_d[3] = { 1.0f / rays_d[3 * r], 1.0f / rays_d[3 * r + 1], 1.0f / rays_d[3 * r + 2] };
+    const float o[3] = { rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2] };
+    const float inv_d[3] = { 1.0f / rays_d[3 * r], 1.0f / rays_d[3 * r + 1], 1.0f / rays_d[3 * r + 2] };
     for (int a = 0; a < n_aabbs; ++a) {
-        float t0 = miss, t1 = miss;
-        bool hit = ray_aabb_one(o, inv_d, aabbs + 6 * a, near, far, t0, t1);
-        if (!hit) { t0 = miss; t1 = miss; }
-        t_mins[r * n_aabbs + a] = t0;
-        t_maxs[r * n_aabbs + a] = t1;
+        float t0, t1;
+        const bool hit = slab_test(o, inv_d, aabbs + 6 * a, t0, t1);
+        t_mins[r * n_aabbs + a] = hit ? fmaxf(t0, near) : miss;
+        t_maxs[r * n_aabbs + a] = hit ? fminf(t1, far) : miss;
         hits[r * n_aabbs + a] = hit ? 1 : 0;
     }
 }
@@ -210,7 +178,8 @@ extern "C" int ced_traverse_grids(int64_t n_rays, const float *rays_o, const flo
     if (mode == 1 || mode == 3)
         CED_REQUIRE(base && t_starts && t_ends, "traverse_grids: fill mode needs base/t_starts/t_ends");
     if (mode == 2) CED_REQUIRE(limit > 0 && t_starts && t_ends, "traverse_grids: over-allocate needs limit > 0");
-    ced::TraverseArgs A{ n_rays, rays_o, rays_d, ced::GridSpec{ binaries, aabbs, n_grids, res, step_size, cone_angle, limit },
+    const int32_t budget = limit > 0 ? limit : 0x7fffffff;      // limit <= 0: unlimited
+    ced::TraverseArgs A{ n_rays, rays_o, rays_d, ced::GridSpec{ binaries, aabbs, n_grids, res, step_size, cone_angle, budget },
                          near_planes, far_planes, rays_mask, t_sorted, t_indices, hits, mode, base, counts, t_starts,
                          t_ends, ray_indices, termination_planes, packed_info_out };
     dim3 block(256), grid((unsigned)((n_rays + 255) / 256));

@@ -169,7 +169,9 @@ int ced_sort_intersections(int64_t n_rays, int32_t n_grids, const float *t_mins,
  * packed_info_out (may be NULL): [n_rays,2] = (start, count) written by the same launch.
  * near_planes and termination_planes may alias (each ray reads its near plane before writing).
  * rays_mask may be NULL (all rays).  ray_indices may be NULL.  binaries: [n_grids,res,res,res]
- * bytes; t_sorted/t_indices: [n_rays, 2*n_grids]; hits: [n_rays, n_grids]. */
+ * bytes; t_sorted/t_indices: [n_rays, 2*n_grids]; hits: [n_rays, n_grids].  limit <= 0: no limit.
+ * Implemented in csrc/march.hip on traverse_ray of csrc/march_accel.hpp (the frame renderer's helpers, no distance
+ * fields); ced_host_march_frame(walk = 3) runs the same function on the host. */
 int ced_traverse_grids(int64_t n_rays, const float *rays_o, const float *rays_d,
                        const uint8_t *binaries, int32_t n_grids, int32_t res, const float *aabbs,
                        const float *near_planes, const float *far_planes,
@@ -198,17 +200,20 @@ int ced_build_occupancy_accel(const uint8_t *binaries, int32_t n_grids, int32_t 
  * cell-by-cell walk, 1 = brick field only (what a render call builds for itself), 2 = brick + cell fields (what
  * ced_build_occupancy_accel provides).  use_lattice: far skips start from the table of first lattice points per
  * binade, as in a frame with cone_angle == 0 (every near plane must then be a point of the lattice t_0 = near_planes[0],
- * t_{k+1} = t_k + step: the frame's near plane or an earlier termination plane).  start_coarse: 0 = the walk of a
- * frame's later iterations (no trace at a segment's start, emission inline), 1 = a frame's first iteration (trace
- * first, looking loop + emission phase), 2 = the one-shot march (trace first, emission inline).  All pointers are
- * host pointers. */
+ * t_{k+1} = t_k + step: the frame's near plane or an earlier termination plane).  walk selects what runs: the
+ * instantiations of the walker traverse_ray_frame -- 0 = a frame's later iterations (no trace at a segment's start,
+ * emission inline), 1 = a frame's first iteration (trace first, looking loop + emission phase), 2 = the one-shot march
+ * (trace first, emission inline) -- or 3 = traverse_ray, the walk of ced_traverse_grids' kernel (the same helpers,
+ * look-ahead of 8 cells, events always read from t_sorted / t_indices; t_term[r] is then the termination plane of EVERY
+ * ray; it has neither distance fields nor a lattice: pass accel_mode 0 and use_lattice 0, other values are ignored).
+ * All pointers are host pointers. */
 int ced_host_build_occupancy_accel(const uint8_t *binaries_host, int32_t n_grids, int32_t res, uint8_t *accel_host);
 int32_t ced_host_count_steps(float *x, float d, float tau, int32_t kcap, float *prev);
 int ced_host_march_frame(int64_t n_rays, const float *rays_o, const float *rays_d, const uint8_t *binaries,
                          int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes, float far_plane,
                          float step_size, float cone_angle, int32_t limit, const float *t_sorted,
                          const int64_t *t_indices, const uint8_t *hits, const uint8_t *accel_host, int32_t accel_mode,
-                         int32_t use_lattice, int32_t start_coarse, int32_t *counts, float *t_starts, float *t_ends,
+                         int32_t use_lattice, int32_t walk, int32_t *counts, float *t_starts, float *t_ends,
                          float *t_term);
 
 /* HOST function (validation aid): the kernels' empty-space skip -- advance t_last by whole steps

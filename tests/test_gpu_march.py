@@ -1,5 +1,5 @@
 """GPU suite: the marching kernels against the geometric float64 reference of tests/march64.py -- ced_traverse_grids
-(csrc/march_core.hpp through march.hip) and the accelerated walk (csrc/march_accel.hpp through ced_march_all), on the
+(march.hip) and the accelerated walk (ced_march_all), both on the helpers of csrc/march_accel.hpp, on the
 cases and with the comparison of tests/test_march64_cpu.py.  The reference's own conditions (how much it decides) are
 asserted there, on the CPU."""
 import numpy as np
@@ -60,6 +60,46 @@ def test_traverse_grids_is_the_geometric_march(name):
     assert np.array_equal(term[~mask].view(np.uint32), c["near"][~mask].view(np.uint32))
     assert np.array_equal(packed[:, 0], np.cumsum(packed[:, 1]) - packed[:, 1])
     M.check_march(M.subset(ref, np.flatnonzero(mask)), t0, t1, _scan(packed[mask, 1]), term=term[mask])
+
+
+@pytest.mark.parametrize("name", M.SPECKLE_CASES)
+def test_traverse_grids_kernel_and_its_host_twin_run_the_same_code(name):
+    """ced_traverse_grids on the device (over-allocated, budget 7) against ced_host_march_frame's walk 3 -- the same
+    function (traverse_ray, march_accel.hpp) compiled for the host -- on the same sorted events: counts, samples and the
+    termination planes of all rays as bit patterns."""
+    import ctypes
+    from ced_nerf_amd import _lib, nerfacc_api as A
+    c = M.case(name)
+    limit = 7
+    n = c["o"].shape[0]
+    b8 = np.ascontiguousarray(c["binaries"]).astype(np.uint8)
+    m, res = b8.shape[0], b8.shape[1]
+    t_mins, t_maxs, hits = A.ray_aabb_intersect(T(c["o"]), T(c["d"]), T(c["aabbs"]))
+    ts, ti = A.sort_intersections(t_mins, t_maxs)
+    i_, s_, term = A.traverse_grids(T(c["o"]), T(c["d"]), T(c["binaries"]), T(c["aabbs"]), T(c["near"]), T(c["far"]), c["step"],
+                                    c["cone_angle"], limit, True, None, ts, ti, hits)
+    d_counts = N(s_.packed_info)[:, 1]
+    d_valid = N(s_.is_valid).reshape(n, limit)
+    vals = N(i_.vals).reshape(n, limit, 2)                   # (t_start, t_end) of every slot
+    d_t0, d_t1 = vals[..., 0], vals[..., 1]
+    assert (c["far"] == c["far"][0]).all()
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    o, d, aabbs, near = (np.ascontiguousarray(c[k], np.float32) for k in ("o", "d", "aabbs", "near"))
+    h_ts = np.ascontiguousarray(N(ts), np.float32); h_ti = np.ascontiguousarray(N(ti), np.int64)
+    h_hits = np.ascontiguousarray(N(hits).astype(np.uint8))
+    counts = np.empty(n, np.int32); tt = np.zeros(n, np.float32)
+    t0 = np.zeros((n, limit), np.float32); t1 = np.zeros((n, limit), np.float32)
+    rc = _lib.lib().ced_host_march_frame(n, P(o), P(d), P(b8), m, res, P(aabbs), P(near), float(c["far"][0]), c["step"],
+                                         c["cone_angle"], limit, P(h_ts), P(h_ti), P(h_hits), None, 0, 0, 3, P(counts), P(t0),
+                                         P(t1), P(tt))
+    assert rc == 0
+    assert np.array_equal(counts.astype(np.int64), d_counts)
+    keep = np.arange(limit)[None, :] < counts[:, None]
+    assert np.array_equal(keep, d_valid)
+    assert (counts < limit).any()            # rays that end below their budget: their planes are compared too
+    assert np.array_equal(t0[keep].view(np.uint32), d_t0[keep].view(np.uint32))
+    assert np.array_equal(t1[keep].view(np.uint32), d_t1[keep].view(np.uint32))
+    assert np.array_equal(tt.view(np.uint32), N(term).view(np.uint32))
 
 
 def _estimator(binaries, levels):

@@ -1,5 +1,5 @@
 """CPU suite: the march against the geometric float64 reference of tests/march64.py -- the reference alone, the C oracle
-(oracle/cednerf_oracle.c restates the DDA of csrc/march_core.hpp, so the bit-exact suites cannot see a mistake the two
+(oracle/cednerf_oracle.c restates the DDA of csrc/march_accel.hpp, so the bit-exact suites cannot see a mistake the two
 share) and the host twin of the accelerated walk (csrc/march_accel.hpp through ced_host_march_frame)."""
 import ctypes as C
 
@@ -109,8 +109,9 @@ def _build_accel(hip, binaries):
 
 @pytest.mark.parametrize("name", M.SPECKLE_CASES)
 def test_host_twin_is_the_geometric_march(hip, oracle, name):
-    """ced_host_march_frame: accel_mode 0 / 1 / 2, start_coarse 0 / 1, the lattice table where it applies (cone angle 0, one
-    near plane).  Its termination plane is specified only for a ray that used its whole budget (march_accel.hpp)."""
+    """ced_host_march_frame: accel_mode 0 / 1 / 2, walk 0 / 1, the lattice table where it applies (cone angle 0, one
+    near plane).  Its termination plane is specified only for a ray that used its whole budget (march_accel.hpp) --
+    except in walk 3 (accel_mode 0), where it is specified for every ray."""
     c = M.case(name)
     o, d, aabbs, near = c["o"], c["d"], c["aabbs"], c["near"]
     n = o.shape[0]
@@ -139,6 +140,16 @@ def test_host_twin_is_the_geometric_march(hip, oracle, name):
                     term = np.where(cnt == limit, tt, np.float32(np.nan))
                     M.check_march(c["ref"], t0[keep], t1[keep], np.stack([np.cumsum(cnt) - cnt, cnt], -1), term=term, limit=limit)
                     runs += 1
+        # walk 3, the instantiation ced_traverse_grids' kernel runs: no distance fields, the plane of every ray specified
+        counts = np.empty(n, np.int32); tt = np.zeros(n, np.float32)
+        t0 = np.zeros((n, limit), np.float32); t1 = np.zeros((n, limit), np.float32)
+        rc = hip.ced_host_march_frame(n, P(o), P(d), P(b8), m, res, P(aabbs), P(near), float(c["far"][0]), c["step"],
+                                      c["cone_angle"], limit, P(ts), P(ti), P(hits8), None, 0, 0, 3, P(counts), P(t0), P(t1), P(tt))
+        assert rc == 0
+        keep = np.arange(limit)[None, :] < counts[:, None]
+        cnt = counts.astype(np.int64)
+        M.check_march(c["ref"], t0[keep], t1[keep], np.stack([np.cumsum(cnt) - cnt, cnt], -1), term=tt, limit=limit)
+        runs += 1
     print(f"{name}: {runs} host marches pass")
 
 

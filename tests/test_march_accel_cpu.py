@@ -105,6 +105,8 @@ def _march_case(hip, oracle, sc, limit, near, start_coarse, accel_mode=2, use_la
     assert_bitexact(t1[mask], w["t_ends"], "t_ends")
     full = wc == limit
     assert_bitexact(tt[full], w["termination_planes"][full], "termination planes of the rays that stay alive")
+    if start_coarse == 3:        # ced_traverse_grids' walk: the plane is an output for every ray
+        assert_bitexact(tt, w["termination_planes"], "termination planes of all rays")
     if want_out:
         return wc, w["termination_planes"]
     return int(wc.sum()), int(full.sum()), dist
@@ -203,6 +205,40 @@ def test_march_frame_matches_oracle_on_random_configurations(hip, oracle, seed):
         if rng.random() < 0.5:
             near = (near + rng.uniform(0, 3, size=n)).astype(np.float32)
         _march_case(hip, oracle, sc, limit, near, int(rng.integers(4)), accel_mode=int(rng.integers(1, 3)))
+
+
+@pytest.mark.parametrize("name,wh", [("dnerf", (64, 48)), ("hypernerf", (40, 56)), ("dynerf", (56, 40))])
+def test_traverse_grids_walk_matches_oracle_on_the_dataset_shaped_scenes(hip, oracle, name, wh):
+    """Walk 3 is the function ced_traverse_grids' kernel runs (traverse_ray: no distance fields, look-ahead 8, eager skips):
+    counts, samples and the termination plane of EVERY ray, dead ones included, against the oracle."""
+    from ced_nerf_amd import synthetic as S
+    sc = S.make_scene(name, wh[0], wh[1], "trained", log2_hashmap_size=10)
+    rng = np.random.default_rng(4)
+    n = wh[0] * wh[1]
+    total = dead = 0
+    for limit in (1, int(rng.integers(2, 40)), 64):
+        for resume in (False, True):
+            near = np.full((n,), sc["render"]["near_plane"], np.float32)
+            if resume:
+                near = (near + rng.uniform(0, 6, size=n)).astype(np.float32)
+            s, full, _ = _march_case(hip, oracle, sc, limit, near, 3, accel_mode=0)
+            total += s
+            dead += n - full
+    assert total > 4000 and dead > 0
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_traverse_grids_walk_matches_oracle_on_random_configurations(hip, oracle, seed):
+    sc, rng = _fuzz_scene(seed)
+    n = sc["origins"].shape[0] * sc["origins"].shape[1]
+    for limit in (1, int(rng.integers(2, 40)), 64):
+        near = np.full((n,), sc["render"]["near_plane"], np.float32)
+        if rng.random() < 0.5:
+            near = (near + rng.uniform(0, 3, size=n)).astype(np.float32)
+        _march_case(hip, oracle, sc, limit, near, 3, accel_mode=0)
+        # the one-shot march with the distance fields at the same limits (the selector that the test above draws is 3
+        # for some seeds, and 3 takes no distance fields)
+        _march_case(hip, oracle, sc, limit, near, 2, accel_mode=int(rng.integers(1, 3)))
 
 
 def test_distance_fields_are_chebyshev_distances(hip):
