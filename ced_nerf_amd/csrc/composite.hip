@@ -6,9 +6,8 @@
 // walks its samples in order, so every per-ray sum has the oracle's summation order (bit-exact
 // transmittance => bit-exact visibility masks and termination decisions).  These passes stream
 // ~30 B per sample; they are bandwidth-trivial next to the field kernel.
-#include <cfloat>
-
 #include "ced_common.hpp"
+#include "composite_core.hpp"
 
 namespace ced {
 
@@ -23,14 +22,13 @@ __global__ __launch_bounds__(256) void render_weights_kernel(int64_t n_rays, con
     int64_t s0 = packed[2 * r], cnt = packed[2 * r + 1];
     float acc = 0.0f;
     for (int64_t i = s0; i < s0 + cnt; ++i) {
-        float sd = sig[i] * (t1[i] - t0[i]);
-        float a = 1.0f - det_expf(-sd);
-        float t = det_expf(-acc);
+        float t = trans_of(acc);
         if (prefix) t = t * prefix[i];
-        if (al) al[i] = a;
-        if (tr) tr[i] = t;
-        if (w) w[i] = t * a;
-        acc = acc + sd;
+        const Sample s = sample_step(sig[i], t0[i], t1[i], t);
+        if (al) al[i] = s.a;
+        if (tr) tr[i] = s.T;
+        if (w) w[i] = s.w;
+        acc = acc + s.sd;
     }
 }
 
@@ -59,18 +57,13 @@ __global__ __launch_bounds__(256) void visibility_kernel(int64_t n_rays, const i
     int64_t s0 = packed[2 * r], cnt = packed[2 * r + 1];
     float acc = 0.0f;
     for (int64_t i = s0; i < s0 + cnt; ++i) {
-        float sd = sig[i] * (t1[i] - t0[i]);
-        float a = 1.0f - det_expf(-sd);
-        float t = det_expf(-acc);
-        bool vis = t >= eps;
-        if (alpha_thre > 0.0f) vis = vis && (a >= alpha_thre);
-        mask[i] = vis ? 1 : 0;
-        acc = acc + sd;
+        const Sample s = sample_step(sig[i], t0[i], t1[i], trans_of(acc));
+        mask[i] = visible(s.T, s.a, eps, alpha_thre) ? 1 : 0;
+        acc = acc + s.sd;
     }
 }
 
-// weights (prefix_trans = 1 - opacity[ray]) + rgb / opacity / depth accumulation, one pass.
-// Same operation order as the unfused sequence of cednerf/utils.py:274-299.
+// weights (prefix_trans = 1 - opacity[ray]) + rgb / opacity / depth accumulation, one pass (composite_ray)
 __global__ __launch_bounds__(256) void composite_prefix_kernel(int64_t n_rays, const int64_t *__restrict__ packed,
                                                                const float *__restrict__ t0,
                                                                const float *__restrict__ t1,
@@ -80,28 +73,7 @@ __global__ __launch_bounds__(256) void composite_prefix_kernel(int64_t n_rays, c
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
-    int64_t s0 = packed[2 * r], cnt = packed[2 * r + 1];
-    if (cnt == 0) return;
-    float op = opacity[r];
-    const float prefix = 1.0f - op;
-    float c0 = rgb[3 * r], c1 = rgb[3 * r + 1], c2 = rgb[3 * r + 2], dp = depth[r];
-    float acc = 0.0f;
-    for (int64_t i = s0; i < s0 + cnt; ++i) {
-        float ts = t0[i], te = t1[i];
-        float sd = sig[i] * (te - ts);
-        float a = 1.0f - det_expf(-sd);
-        float t = det_expf(-acc) * prefix;
-        float w = t * a;
-        c0 = c0 + w * rgbs[3 * i];
-        c1 = c1 + w * rgbs[3 * i + 1];
-        c2 = c2 + w * rgbs[3 * i + 2];
-        op = op + w;
-        dp = dp + w * ((ts + te) / 2.0f);
-        acc = acc + sd;
-    }
-    rgb[3 * r] = c0; rgb[3 * r + 1] = c1; rgb[3 * r + 2] = c2;
-    opacity[r] = op;
-    depth[r] = dp;
+    composite_ray(r, packed[2 * r], packed[2 * r + 1], t0, t1, sig, rgbs, rgb, opacity, depth);
 }
 
 // composite_prefix + the ray bookkeeping of cednerf/utils.py:301-307 (mask update, alive count, sample count)
@@ -118,31 +90,9 @@ __global__ __launch_bounds__(256) void composite_step_kernel(int64_t n_rays, con
     int64_t cnt = 0;
     bool alive = false;
     if (r < n_rays) {
-        int64_t s0 = packed[2 * r];
         cnt = packed[2 * r + 1];
-        float op = opacity[r];
-        if (cnt > 0) {
-            const float prefix = 1.0f - op;
-            float c0 = rgb[3 * r], c1 = rgb[3 * r + 1], c2 = rgb[3 * r + 2], dp = depth[r];
-            float acc = 0.0f;
-            for (int64_t i = s0; i < s0 + cnt; ++i) {
-                float ts = t0[i], te = t1[i];
-                float sd = sig[i] * (te - ts);
-                float a = 1.0f - det_expf(-sd);
-                float t = det_expf(-acc) * prefix;
-                float w = t * a;
-                c0 = c0 + w * rgbs[3 * i];
-                c1 = c1 + w * rgbs[3 * i + 1];
-                c2 = c2 + w * rgbs[3 * i + 2];
-                op = op + w;
-                dp = dp + w * ((ts + te) / 2.0f);
-                acc = acc + sd;
-            }
-            rgb[3 * r] = c0; rgb[3 * r + 1] = c1; rgb[3 * r + 2] = c2;
-            opacity[r] = op;
-            depth[r] = dp;
-        }
-        alive = (op <= opc_thres) && (cnt == (int64_t)n_samples_iter);
+        const float op = composite_ray(r, packed[2 * r], cnt, t0, t1, sig, rgbs, rgb, opacity, depth);
+        alive = survives(op, cnt, n_samples_iter, opc_thres);
         ray_mask[r] = alive ? 1 : 0;
     }
     // wave-level reduction, one atomic pair per wave
@@ -171,26 +121,19 @@ __global__ __launch_bounds__(256) void composite_test_kernel(int64_t n_alive, co
     int64_t ray = alive[n];
     if (steps == 0) { alive[n] = -1; return; }
     float T = 1.0f - opacity[ray];
-    float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, dacc = 0.0f, oacc = 0.0f;
+    RaySums sums;
     for (int64_t s = 0; s < steps; ++s) {
         int64_t i = start + s;
-        float delta = t_end[i] - t_start[i];
-        float a = 1.0f - det_expf(-sigmas[i] * delta);
-        if (a > a_thr) {
-            float w = a * T;
-            float tmid = (t_start[i] + t_end[i]) / 2.0f;
-            c0 = c0 + w * rgbs[3 * i];
-            c1 = c1 + w * rgbs[3 * i + 1];
-            c2 = c2 + w * rgbs[3 * i + 2];
-            dacc = dacc + w * tmid;
-            oacc = oacc + w;
-            T = T * (1.0f - a);
+        const Sample p = sample_step(sigmas[i], t_start[i], t_end[i], T);
+        if (p.a > a_thr) {
+            sums.add(p.w, rgbs[3 * i], rgbs[3 * i + 1], rgbs[3 * i + 2], t_start[i], t_end[i]);
+            T = T * (1.0f - p.a);
             if (T <= T_thr) { alive[n] = -1; break; }
         }
     }
-    rgb[3 * ray] += c0; rgb[3 * ray + 1] += c1; rgb[3 * ray + 2] += c2;
-    depth[ray] += dacc;
-    opacity[ray] += oacc;
+    rgb[3 * ray] += sums.c0; rgb[3 * ray + 1] += sums.c1; rgb[3 * ray + 2] += sums.c2;
+    depth[ray] += sums.dp;
+    opacity[ray] += sums.op;
 }
 
 __global__ __launch_bounds__(256) void finalize_kernel(int64_t n_rays, const float *__restrict__ bkgd,
@@ -199,23 +142,16 @@ __global__ __launch_bounds__(256) void finalize_kernel(int64_t n_rays, const flo
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
-    float op = opacity[r];
-    if (bkgd) {
-        float rem = 1.0f - op;
-        rgb[3 * r] = rgb[3 * r] + bkgd[0] * rem;
-        rgb[3 * r + 1] = rgb[3 * r + 1] + bkgd[1] * rem;
-        rgb[3 * r + 2] = rgb[3 * r + 2] + bkgd[2] * rem;
-    }
-    depth[r] = depth[r] / __builtin_fmaxf(op, FLT_EPSILON);
+    finalize_pixel(r, bkgd, rgb, opacity, depth);
 }
 
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // Backward of the training-time compositing: d(colors, opacities, depths)/d(sigmas, rgbs) of
 // cednerf/render.py:158-169.  One lane per ray, two sweeps.  The forward sweep is render_weights_kernel's: it sums the
-// optical depth in sample order and keeps T_i = det_expf(-acc_i) in d_sig[i] -- the output buffer is the scratch, as in
+// optical depth in sample order and keeps T_i = trans_of(acc_i) in d_sig[i] -- the output buffer is the scratch, as in
 // ray_density (losses.hip); nothing outside the ray's [s0, s0 + cnt) is touched.  The reverse sweep reads T_i back before
-// it overwrites the slot, takes a_i with det_expf, so that w_i = T_i a_i is the forward kernel's weight bit for bit, and
+// it overwrites the slot, takes a_i with alpha_of, so that w_i = T_i a_i is the forward kernel's weight bit for bit, and
 // carries the suffix sum S_i = sum_{k>i} g_k w_k:
 //   g_i = <d_color, rgb_i> + d_opacity + d_depth * t_mid_i,   d rgb_i = w_i d_color,
 //   d sigma_i = dt_i * (g_i (T_i - w_i) - S_i).
@@ -237,17 +173,16 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(int64_t n_rays,
     const float dop = d_opacity ? d_opacity[r] : 0.0f, ddp = d_depth ? d_depth[r] : 0.0f;
     float acc = 0.0f;
     for (int64_t i = s0; i < s0 + cnt; ++i) {
-        d_sig[i] = det_expf(-acc);
-        acc = acc + sig[i] * (t1[i] - t0[i]);
+        const Sample s = sample_step(sig[i], t0[i], t1[i], trans_of(acc));
+        d_sig[i] = s.T;
+        acc = acc + s.sd;
     }
     float suffix = 0.0f;
     for (int64_t i = s0 + cnt - 1; i >= s0; --i) {
         const float ts = t0[i], te = t1[i];
         const float dt = te - ts;
-        const float sd = sig[i] * dt;
-        const float T = d_sig[i];
-        const float a = 1.0f - det_expf(-sd);
-        const float w = T * a;
+        const Sample s = sample_step(sig[i], ts, te, d_sig[i]);
+        const float T = s.T, w = s.w;
         const float g = ((dc0 * rgbs[3 * i] + dc1 * rgbs[3 * i + 1]) + dc2 * rgbs[3 * i + 2]) + dop + ddp * ((ts + te) * 0.5f);
         d_sig[i] = dt * (g * (T - w) - suffix);
         d_rgbs[3 * i] = w * dc0;
@@ -324,9 +259,6 @@ extern "C" int ced_composite_backward(int64_t n_rays, const int64_t *packed_info
                        d_sigmas, d_rgbs);
     return ced::check_launch("composite_backward");
 }
-
-namespace ced {
-}  // namespace ced
 
 extern "C" int ced_render_weights(int64_t n_rays, const int64_t *packed_info, const float *t_starts,
                                   const float *t_ends, const float *sigmas, const float *prefix_trans, float *weights,

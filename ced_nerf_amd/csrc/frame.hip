@@ -18,11 +18,11 @@
 //     published; iterations enqueued after the frame has finished are empty launches.
 // Pixels, per-iteration schedule and sample counts are bit-identical to the reference loop.
 #include <atomic>
-#include <cfloat>
 #include <chrono>
 #include <vector>
 
 #include "ced_common.hpp"
+#include "composite_core.hpp"
 #include "field_args.hpp"
 #include "march_accel.hpp"
 
@@ -612,57 +612,9 @@ __global__ __launch_bounds__(kCompositeThreads) void frame_composite_kernel(
         int cnt = 0;
         bool alive = false;
         if (active) {
-            const int64_t sb = packed[2 * r];
             cnt = packed[2 * r + 1];
-            float op = opacity[r];
-            if (cnt > 0) {
-                const float prefix = 1.0f - op;
-                float c0 = rgb[3 * r], c1 = rgb[3 * r + 1], c2 = rgb[3 * r + 2], dp = depth[r];
-                float acc = 0.0f;
-                // Samples are consumed strictly in order (the per-ray sums are sequential by contract), but
-                // their loads are issued kU at a time so one memory round trip feeds kU samples.
-                constexpr int kU = 4;
-                int64_t i = sb;
-                const int64_t end = sb + cnt;
-                for (; i + kU <= end; i += kU) {
-                    float ts[kU], te[kU], sg[kU], cr[kU], cg[kU], cb[kU];
-#pragma unroll
-                    for (int u = 0; u < kU; ++u) {
-                        ts[u] = t0[i + u]; te[u] = t1[i + u]; sg[u] = sig[i + u];
-                        cr[u] = rgbs[3 * (i + u)]; cg[u] = rgbs[3 * (i + u) + 1]; cb[u] = rgbs[3 * (i + u) + 2];
-                    }
-#pragma unroll
-                    for (int u = 0; u < kU; ++u) {
-                        float sd = sg[u] * (te[u] - ts[u]);
-                        float a = 1.0f - det_expf(-sd);
-                        float t = det_expf(-acc) * prefix;
-                        float w = t * a;
-                        c0 = c0 + w * cr[u];
-                        c1 = c1 + w * cg[u];
-                        c2 = c2 + w * cb[u];
-                        op = op + w;
-                        dp = dp + w * ((ts[u] + te[u]) / 2.0f);
-                        acc = acc + sd;
-                    }
-                }
-                for (; i < end; ++i) {
-                    float ts = t0[i], te = t1[i];
-                    float sd = sig[i] * (te - ts);
-                    float a = 1.0f - det_expf(-sd);
-                    float t = det_expf(-acc) * prefix;
-                    float w = t * a;
-                    c0 = c0 + w * rgbs[3 * i];
-                    c1 = c1 + w * rgbs[3 * i + 1];
-                    c2 = c2 + w * rgbs[3 * i + 2];
-                    op = op + w;
-                    dp = dp + w * ((ts + te) / 2.0f);
-                    acc = acc + sd;
-                }
-                rgb[3 * r] = c0; rgb[3 * r + 1] = c1; rgb[3 * r + 2] = c2;
-                opacity[r] = op;
-                depth[r] = dp;
-            }
-            alive = !P.last[f] && (op <= opc_thres) && (cnt == limit);
+            const float op = composite_ray(r, packed[2 * r], cnt, t0, t1, sig, rgbs, rgb, opacity, depth);
+            alive = !P.last[f] && survives(op, cnt, limit, opc_thres);
         }
         const int slot = workgroup_append<kCompositeThreads / 64, 1>(alive, &cnt, [&](int run, const int *samples) {
             const unsigned long long add = (unsigned long long)run + ((unsigned long long)samples[0] << 32);
@@ -691,22 +643,6 @@ __global__ __launch_bounds__(64) void frame_pack_counts_kernel(const IterPlan *_
     const unsigned long long nx = __hip_atomic_load(&plan->next[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool finished = plan->last[f] || plan->gcount[f] == 0 || plan->count[f] == 0;
     row[f] = finished ? 0 : (int64_t)(nx & 0xffffffffull);
-}
-
-__global__ __launch_bounds__(256) void frame_finalize_kernel(int64_t n_rays, const float *__restrict__ bkgd,
-                                                             float *__restrict__ rgb, const float *__restrict__ opacity,
-                                                             float *__restrict__ depth)
-{
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rays) return;
-    float op = opacity[r];
-    if (bkgd) {
-        float rem = 1.0f - op;
-        rgb[3 * r] = rgb[3 * r] + bkgd[0] * rem;
-        rgb[3 * r + 1] = rgb[3 * r + 1] + bkgd[1] * rem;
-        rgb[3 * r + 2] = rgb[3 * r + 2] + bkgd[2] * rem;
-    }
-    depth[r] = depth[r] / __builtin_fmaxf(op, FLT_EPSILON);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -812,60 +748,38 @@ __global__ __launch_bounds__(kCompositeThreads) void image_composite_kernel(
             const int64_t sb = packed[2 * r];
             cnt = packed[2 * r + 1];
             if (cnt > 0) {
-                float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, op = 0.0f, dp = 0.0f;
-                if constexpr (FULL) { c0 = rgb[3 * r]; c1 = rgb[3 * r + 1]; c2 = rgb[3 * r + 2]; op = opacity[r]; dp = depth[r]; }
+                RaySums sums;
+                if constexpr (FULL) sums.load(rgb, opacity, depth, r);
                 float acc = st.acc_all[r], acck = st.acc_kept[r];
                 int kept = st.kept[r];
                 const int kept_before = kept;
                 bool open = true;                   // false once a sample failed the transmittance test: the rest fail too
-                constexpr int kU = 4;
-                const int64_t end = sb + cnt;
-                for (int64_t i = sb; i < end; i += kU) {
-                    float ts[kU], te[kU], sg[kU], cr[kU], cg[kU], cb[kU];
-#pragma unroll
-                    for (int u = 0; u < kU; ++u) {
-                        const int64_t j = i + u < end ? i + u : end - 1;
-                        ts[u] = t0[j]; te[u] = t1[j]; sg[u] = sig[j];
-                        if constexpr (FULL) { cr[u] = rgbs[3 * j]; cg[u] = rgbs[3 * j + 1]; cb[u] = rgbs[3 * j + 2]; }
-                    }
-#pragma unroll
-                    for (int u = 0; u < kU; ++u) {
-                        if (i + u >= end) break;
-                        const float sd = sg[u] * (te[u] - ts[u]);
-                        const float a = 1.0f - det_expf(-sd);
-                        const float tv = det_expf(-acc);
-                        open = open && (tv >= eps);
-                        const bool vis = open && !(alpha_thre > 0.0f && !(a >= alpha_thre));
-                        acc = acc + sd;
-                        int rank = -1;
-                        if (vis) {
-                            if constexpr (FULL) {
-                                const float t = alpha_thre > 0.0f ? det_expf(-acck) : tv;   // no alpha test: the two sums coincide
-                                const float w = t * a;
-                                c0 = c0 + w * cr[u];
-                                c1 = c1 + w * cg[u];
-                                c2 = c2 + w * cb[u];
-                                op = op + w;
-                                dp = dp + w * ((ts[u] + te[u]) / 2.0f);
-                                acck = acck + sd;
-                                w_out[i + u] = w; tr_out[i + u] = t; al_out[i + u] = a;
-                            }
-                            rank = kept++;
+                walk_samples<4, FULL>(sb, sb + cnt, t0, t1, sig, rgbs,
+                                      [&](float ts, float te, float sg, float cr, float cg, float cb, int64_t i) __attribute__((always_inline)) {
+                    const Sample all = sample_step(sg, ts, te, trans_of(acc));
+                    open = open && (all.T >= eps);          // visible()'s transmittance half, kept for the rest of the ray
+                    const bool vis = open && visible(all.T, all.a, eps, alpha_thre);
+                    acc = acc + all.sd;
+                    int rank = -1;
+                    if (vis) {
+                        if constexpr (FULL) {
+                            // the weight's transmittance is over the KEPT samples; no alpha test: the two sums coincide
+                            const Sample k = alpha_thre > 0.0f ? sample_step(sg, ts, te, trans_of(acck)) : all;
+                            sums.add(k.w, cr, cg, cb, ts, te);
+                            acck = acck + k.sd;
+                            w_out[i] = k.w; tr_out[i] = k.T; al_out[i] = k.a;
                         }
-                        rank_out[i + u] = rank;
+                        rank = kept++;
                     }
-                }
-                if constexpr (FULL) {
-                    rgb[3 * r] = c0; rgb[3 * r + 1] = c1; rgb[3 * r + 2] = c2;
-                    opacity[r] = op;
-                    depth[r] = dp;
-                }
+                    rank_out[i] = rank;
+                });
+                if constexpr (FULL) sums.store(rgb, opacity, depth, r);
                 const int cur = st.cursor[r] + cnt;
                 st.cursor[r] = cur;
                 st.acc_all[r] = acc; st.acc_kept[r] = acck; st.kept[r] = kept;
                 kept_new = kept - kept_before;
                 // alive: samples left, and the next one would pass the transmittance test
-                alive = open && (int64_t)cur < ray_count(packed_all, r, n_all) && (det_expf(-acc) >= eps);
+                alive = open && (int64_t)cur < ray_count(packed_all, r, n_all) && (trans_of(acc) >= eps);
             }
         }
         const int sums[2] = { cnt, kept_new };
@@ -1341,8 +1255,7 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
         if (rc) return rc;
     }
     const int enqueued = it;
-    hipLaunchKernelGGL(frame_finalize_kernel, grd, blk, 0, stream, n_rays, bkgd, rgb, opacity, depth);
-    rc = check_launch("render_image_test (finalize)");
+    rc = ced_finalize_pixels(n_rays, bkgd, rgb, opacity, depth, stream);
     if (rc) return rc;
     std::vector<IterPlan> plans;
     int n_iters = 0;
@@ -1494,9 +1407,10 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
         if (rc) return rc;
     }
     const int enqueued = it;
-    if (full) hipLaunchKernelGGL(frame_finalize_kernel, grd, blk, 0, stream, n_rays, bkgd, rgb, opacity, depth);
-    rc = check_launch("render_image (finalize)");
-    if (rc) return rc;
+    if (full) {
+        rc = ced_finalize_pixels(n_rays, bkgd, rgb, opacity, depth, stream);
+        if (rc) return rc;
+    }
     std::vector<IterPlan> plans;
     int n_iters = 0;
     rc = read_back_plans(W.plans, enqueued, stream, "render_image (read-back)", who, plans, n_iters);

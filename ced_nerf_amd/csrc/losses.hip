@@ -17,6 +17,7 @@
 // sums the partials in a fixed order: no float atomics, two calls give the same bits.  Precondition (met by every producer in this package): samples are grouped by ray, in the order of
 // packed_info, and t_starts does not decrease within a ray.
 #include "ced_common.hpp"
+#include "composite_core.hpp"
 
 namespace ced {
 
@@ -58,7 +59,7 @@ __device__ __forceinline__ double ray_weights(int64_t s0, int64_t cnt, const flo
     return L;
 }
 
-// fused route, one ray: the weights of render_weights_kernel (same arithmetic, same bits), L_ray, and the gradient through
+// fused route, one ray: the weights of render_weights_kernel (the same sample_step, composite_core.hpp), L_ray, and the gradient through
 // the weights to the densities, d sigma_i = s_i (g_i (T_i - w_i) - sum_{k>i} g_k w_k), g = dL_ray/dw (the composite
 // backward's formula).  d_sig holds D_i and trans T_i between the two sweeps, so the reverse sweep sees the forward's
 // weights bit for bit.  d_sig and trans are both NULL (loss only) or both set.
@@ -69,11 +70,9 @@ __device__ __forceinline__ double ray_density(int64_t s0, int64_t cnt, const flo
     double W = 0.0, D = 0.0, L = 0.0;
     for (int64_t i = s0; i < s0 + cnt; ++i) {
         const float ts = t0[i], te = t1[i];
-        const float sd = sig[i] * (te - ts);
-        const float a = 1.0f - det_expf(-sd);
-        const float t = det_expf(-acc);
-        const float wi = t * a;
-        acc = acc + sd;
+        const Sample s = sample_step(sig[i], ts, te, trans_of(acc));
+        const float t = s.T, wi = s.w;
+        acc = acc + s.sd;
         if (i > s0) D = D + W * (double)mid_step(p0, p1, ts, te);
         L = L + dist_term(wi, D, te - ts);
         if (d_sig) { d_sig[i] = (float)D; trans[i] = t; }
@@ -85,9 +84,8 @@ __device__ __forceinline__ double ray_density(int64_t s0, int64_t cnt, const flo
     for (int64_t i = s0 + cnt - 1; i >= s0; --i) {
         const float ts = t0[i], te = t1[i];
         const float dt = te - ts;
-        const float a = 1.0f - det_expf(-(sig[i] * dt));
-        const float t = trans[i];
-        const float wi = t * a;
+        const Sample s = sample_step(sig[i], ts, te, trans[i]);
+        const float t = s.T, wi = s.w;
         if (i < s0 + cnt - 1) E = E + Wg * (double)mid_step(ts, te, p0, p1);
         const double g = 2.0 * ((double)d_sig[i] + E) + (2.0 / 3.0) * ((double)dt * wi);
         d_sig[i] = (float)(dt * (g * ((double)t - (double)wi) - suffix));

@@ -28,7 +28,12 @@ def test_generators_produce_what_they_name():
         assert np.array_equal(pb.packed[:, 0], np.cumsum(cnt) - cnt) and pb.S == cnt.sum()
         if n >= 255:
             assert 0.15 < (cnt == 0).mean() < 0.45
+    # the sample walker (composite_core.hpp: walk_samples) loads kU = 4 samples at a time and finishes one by one:
+    # test_gpu_compositing's shapes must hold every count around one and two batches (asserted: a new seed may not lose them)
+    kU = 4
+    assert set(range(2 * kU + 1)) <= set(M.make("edge257", "mixed").packed[:, 1])
     pb = M.make("long", "mixed")
+    assert {kU - 1, kU, kU + 1} <= set(pb.packed[:, 1])
     assert sorted(set(pb.packed[:, 1])) == sorted(M.LONG_LENGTHS) and pb.n_rays == 60 and pb.S <= 2e5
     pb = M.make("all_empty", "mixed")
     assert pb.n_rays == 300 and pb.S == 0 and not pb.packed.any()

@@ -5,6 +5,11 @@ Shapes (composite64.SHAPES): n_rays at grid and wave edges (1, 63, 64, 65, 255, 
 regimes: thin, the mixed law of test_gpu_parity, exact zeros (sigma and dt), saturated (a = 1, T = 0), walls of
 sigma = 1e3, 1e5, e^15 behind 20-40 thin samples.
 
+composite_prefix_ and composite_step_ run composite_core.hpp's composite_ray on walk_samples<4> -- the frame renderer's
+loop (frame_composite_kernel) -- so these cases are the hard-shape test of that walker too: edge257 and edge513 hold every
+per-ray count 0 .. 12, long holds 0, 1, 3, 4, 5, 63 .. 65, ..., 4099 (whole batches, batches plus a one-by-one rest, no
+batch at all; test_composite64_cpu.py asserts the counts).
+
 Forward kernels, two checks per case:
  (a) bit for bit against the C oracle: weights / transmittance / alpha with and without a per-sample prefix,
      accumulate_along_rays_, the visibility mask, composite_test; composite_prefix_ and composite_step_ against the

@@ -1,5 +1,5 @@
 """Timeline of the LAST frame in a rocprofv3 --kernel-trace CSV: every dispatch with start offset, duration and the gap
-to the previous dispatch's end (one frame = from frame_prep_kernel to frame_finalize_kernel).
+to the previous dispatch's end (one frame = from frame_prep_kernel to finalize_kernel).
 usage: python tools/frame_timeline.py <dir with *_kernel_trace.csv> [frame index from the end, default 1]"""
 import csv, glob, os, sys
 path = sys.argv[1]
@@ -10,7 +10,7 @@ short = lambda n: n.split("(")[0].replace("void ", "").replace("ced::", "")[:40]
 starts = [i for i, r in enumerate(rows) if "frame_prep" in r["Kernel_Name"]]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 a = starts[-k]
-b = next(i for i in range(a, len(rows)) if "frame_finalize_kernel" in rows[i]["Kernel_Name"])
+b = next(i for i in range(a, len(rows)) if "finalize_kernel" in rows[i]["Kernel_Name"])
 t0 = int(rows[a]["Start_Timestamp"]); prev_end = t0
 tot = {}
 for r in rows[a:b + 1]:
