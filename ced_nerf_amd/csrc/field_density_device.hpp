@@ -1,5 +1,6 @@
 // The canonical density on tile_kernel's skeleton (field_move_device.hpp), stated once for the ops that evaluate it after
-// the warp: GradientOp (field_density_gradient.hip) and TimeMaxOp (field_time_max.hip).  Such an op stages the motion
+// the warp: GradientOp (field_density_gradient.hip), TimeMaxOp (field_time_max.hip) and LevelSetOp
+// (field_level_set.hip).  Such an op stages the motion
 // network AND mlp_base (adjacent at the start of every blob: DensityF32 / DensityHalf), keeps the sixteen levels'
 // constants in LDS beside them (DensityLevels), and per tile goes from `move` to the raw density through
 //   canonical_point: x_norm, the selector and |move|, as the fused kernels form them;

@@ -229,8 +229,24 @@ def _check_mesh_reso(reso):
         raise ValueError(f"reso must be an int in 1 .. {MESH_MAX_RESO} for a mesh, got {reso!r}")
 
 
+def _vertex_values(field, vertices, normals, t: float, dirs, apply_act: bool, field_normals: bool) -> Dict:
+    """What a mesh carries per vertex besides its position: sigma, embedding, the normals (the given ones, or the field's
+    own slope at the vertices) and the colours."""
+    v, dev = vertices.shape[0], vertices.device
+    res = field.query_density(vertices, torch.full((v, 1), t, device=dev, dtype=torch.float32), return_feat=True)
+    if field_normals:                                                            # the field's own slope at the vertices
+        normals = field.query_normals(vertices, torch.full((v,), t, device=dev, dtype=torch.float32))[0]
+    out = dict(normals=normals, sigma=res["density"].reshape(v), embedding=res["base_mlp_out"])
+    if isinstance(dirs, str):                                                    # "normal": head-on, one direction each
+        head_on = torch.where((normals == 0).all(-1, keepdim=True), normals.new_tensor([0.0, 0.0, 1.0]), -normals)
+        out["rgb"] = field._query_rgb(head_on, out["embedding"], apply_act).view(v, 1, 3)
+    elif dirs is not None:
+        out["rgb"] = ops.field_rgb_bcast(field._descriptor(), dirs, out["embedding"], apply_act)
+    return out
+
+
 def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max_rows: int, meta: Dict,
-          field_normals: bool = False) -> Dict:
+          field_normals: bool = False, refine: bool = False, refine_reach: float = 1.0) -> Dict:
     desc = field._descriptor()
     index, xyz = cand
     reso, dev = meta["reso"], xyz.device
@@ -244,28 +260,76 @@ def _mesh(field, cand, t: float, sigma_thresh: float, dirs, apply_act: bool, max
     vertices, normals, cube, faces = ops.mesh_surface_nets(lattice.view(reso, reso, reso), sigma_thresh, meta["center"],
                                                            meta["radius"])
     del lattice
-    v = vertices.shape[0]
-    res = field.query_density(vertices, torch.full((v, 1), t, device=dev, dtype=torch.float32), return_feat=True)
-    if field_normals:                                                            # the field's own slope at the vertices
-        normals = field.query_normals(vertices, torch.full((v,), t, device=dev, dtype=torch.float32))[0]
-    out = dict(vertices=vertices, normals=normals, faces=faces, cube=cube, sigma=res["density"].reshape(v),
-               embedding=res["base_mlp_out"])
-    if isinstance(dirs, str):                                                    # "normal": head-on, one direction each
-        head_on = torch.where((normals == 0).all(-1, keepdim=True), normals.new_tensor([0.0, 0.0, 1.0]), -normals)
-        out["rgb"] = field._query_rgb(head_on, out["embedding"], apply_act).view(v, 1, 3)
-    elif dirs is not None:
-        out["rgb"] = ops.field_rgb_bcast(desc, dirs, out["embedding"], apply_act)
-    out.update(meta, t=t)
+    out = dict(vertices=vertices, faces=faces, cube=cube)
+    out.update(_vertex_values(field, vertices, normals, t, dirs, apply_act, field_normals))
+    out.update(meta, t=t, dirs=dirs, normals_kind="field" if field_normals else "lattice")
+    return refine_mesh(field, out, reach=refine_reach) if refine else out
+
+
+def _check_reach(reach) -> float:
+    try:
+        reach_f = float(reach)
+    except (TypeError, ValueError):
+        raise ValueError(f"reach must be a positive finite number (in lattice spacings), got {reach!r}") from None
+    if not (np.isfinite(reach_f) and reach_f > 0):
+        raise ValueError(f"reach must be a positive finite number (in lattice spacings), got {reach!r}")
+    return reach_f
+
+
+@torch.no_grad()
+def refine_mesh(field, mesh: Dict, reach: float = 1.0, max_iters: int = 32, tol: float = 0.0) -> Dict:
+    """Move the vertices of `mesh` (a dict from `extract_mesh`) onto the level set density == sigma_thresh itself.  Surface
+    nets put a vertex at the centroid of its lattice cube's edge crossings, up to a cell away from the surface: mesh["sigma"]
+    scatters widely around the threshold.  Here each vertex v with a non-zero normal n (towards lower density) becomes the
+    row o = v, d = -n, lo = -reach * h, hi = +reach * h of `DNGPradianceField.query_level_set` (h = the lattice spacing
+    2 radius / reso, the mesh's t and sigma_thresh, one launch for all vertices): the bracket starts reach * h outside the
+    surface nets' position and ends reach * h inside.  A row with a crossing (status 0) moves to it; every other row -- a
+    zero normal, a bracket that starts at or above the threshold or never reaches it -- keeps its vertex, bit for bit.
+    Returns a new mesh dict:
+        vertices [V,3], refined [V] bool, offset [V] (the signed distance moved along n; 0 where not refined),
+        width [V] (of the final bracket: density(vertex + n * width) < sigma_thresh <= sigma on refined vertices),
+        sigma, embedding, rgb (if the mesh has colours) and, for a mesh extracted with normals="field", normals:
+        re-evaluated at the new vertices as `extract_mesh` evaluates them,
+        faces, cube, reso, center, radius, t, sigma_thresh, apply_act: the mesh's own.
+    A hand-built mesh dict needs vertices, normals, reso, center, radius, t and sigma_thresh; without `dirs` it comes back
+    without colours."""
+    reach = _check_reach(reach)
+    thresh, max_iters, tol = ops.check_level_set(mesh["sigma_thresh"], max_iters, tol)
+    vertices, normals = mesh["vertices"], mesh["normals"]
+    if not vertices.is_cuda:
+        raise NotImplementedError(_CPU)
+    t = _time_value(mesh["t"])
+    _, h = _origin_and_step(int(mesh["reso"]), mesh["center"], mesh["radius"])
+    with torch.cuda.device(vertices.device):
+        v = vertices.shape[0]
+        hi = torch.full((v,), float(np.float32(reach) * h), device=vertices.device, dtype=torch.float32)
+        if v:
+            s, x, _, width, status, _ = field.query_level_set(vertices, -normals, -hi, hi, t, thresh, max_iters, tol)
+        else:
+            s, x, width = hi, vertices, hi
+            status = torch.ones((0,), device=vertices.device, dtype=torch.int32)
+        refined = (status == 0) & (normals != 0).any(-1)
+        out = dict(mesh)
+        if "dirs" not in mesh:                                                   # a hand-built mesh: its colours cannot follow
+            out.pop("rgb", None)
+        out["vertices"] = torch.where(refined[:, None], x, vertices)
+        out["refined"] = refined
+        out["offset"] = torch.where(refined, -s, torch.zeros_like(s))
+        out["width"] = torch.where(refined, width, torch.zeros_like(width))
+        out.update(_vertex_values(field, out["vertices"], normals, t, mesh.get("dirs"), bool(mesh.get("apply_act", False)),
+                                  mesh.get("normals_kind") == "field"))
     return out
 
 
 @torch.no_grad()
 def extract_mesh_sequence(field, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None,
                           apply_act: bool = False, center=None, radius=None,
-                          max_cells_per_launch: int = 1 << 22, normals: str = "lattice") -> List[Dict]:
+                          max_cells_per_launch: int = 1 << 22, normals: str = "lattice", refine: bool = False,
+                          refine_reach: float = 1.0) -> List[Dict]:
     """`extract_mesh` at every time of `times`: the candidate cells (the occupancy mask and the centres) are computed
     once and reused for every time."""
     field_normals = check_mesh_normals(normals) == "field"
+    refine_reach = _check_reach(refine_reach)
     _check_mesh_reso(reso)
     by_normal = isinstance(dirs, str)
     if by_normal and dirs != "normal":
@@ -278,11 +342,12 @@ def extract_mesh_sequence(field, times: Sequence, reso: int = 128, sigma_thresh:
         meta = dict(reso=int(reso), center=center, radius=radius, sigma_thresh=float(sigma_thresh),
                     apply_act=bool(apply_act))
         return [_mesh(field, cand_at(t), t, float(sigma_thresh), "normal" if by_normal else tensor_dirs, apply_act, max_cells,
-                      meta, field_normals) for t in times]
+                      meta, field_normals, bool(refine), refine_reach) for t in times]
 
 
 def extract_mesh(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None, estimator=None, apply_act: bool = False,
-                 center=None, radius=None, max_cells_per_launch: int = 1 << 22, normals: str = "lattice") -> Dict:
+                 center=None, radius=None, max_cells_per_launch: int = 1 << 22, normals: str = "lattice",
+                 refine: bool = False, refine_reach: float = 1.0) -> Dict:
     """The iso-surface density == sigma_thresh of `field` at time t as a triangle mesh: naive surface nets (the
     definition is in include/cednerf_hip.h) on the lattice of `voxel_centers`(reso, center, radius), reso <= 512, whose
     densities are query_density's bits (0 at the cells an `estimator` does not mark).  Returns
@@ -294,11 +359,13 @@ def extract_mesh(field, t, reso: int = 128, sigma_thresh: float = 1.0, dirs=None
         sigma [V] and embedding [V,15] (query_density(vertices, t, return_feat=True)'s bits),
         rgb [V,D,3]: for dirs [D,3] _query_rgb on every pair; for dirs="normal" D = 1 and every vertex is viewed head-on,
         along -normal ((0,0,1) where the normal is zero); the sigmoid iff apply_act; absent without dirs,
-        reso, center, radius, t, sigma_thresh, apply_act.
+        reso, center, radius, t, sigma_thresh, apply_act (and dirs, normals_kind: what `refine_mesh` re-evaluates with).
     The mesh is closed away from the lattice border and open on it; its vertex and face order do not depend on the run
-    or on max_cells_per_launch."""
+    or on max_cells_per_launch.
+    refine=True: the result is `refine_mesh`(field, mesh, reach=refine_reach) -- the vertices moved along their normals
+    onto density == sigma_thresh, with `refined`, `offset` and `width` per vertex; refine=False leaves the mesh as it is."""
     return extract_mesh_sequence(field, [t], reso, sigma_thresh, dirs, estimator, apply_act, center, radius,
-                                 max_cells_per_launch, normals)[0]
+                                 max_cells_per_launch, normals, refine, refine_reach)[0]
 
 
 # ---- a mesh that moves -----------------------------------------------------------------------------------------------
@@ -360,16 +427,18 @@ def track_mesh(field, mesh: Dict, t_src, times: Sequence, max_iters: int = 32, t
 def extract_mesh_tracked(field, t_ref, times: Sequence, reso: int = 128, sigma_thresh: float = 1.0, dirs=None,
                          estimator=None, apply_act: bool = False, center=None, radius=None,
                          max_cells_per_launch: int = 1 << 22, max_iters: int = 32, tol: float = 1e-6,
-                         method: str = "fixed_point", normals=False, velocities: bool = False) -> Dict:
+                         method: str = "fixed_point", normals=False, velocities: bool = False, refine: bool = False,
+                         refine_reach: float = 1.0) -> Dict:
     """`extract_mesh` at t_ref followed by `track_mesh` to `times`: one mesh with shared faces and per-time vertex
     positions (see `track_mesh` for the result, `method`, `normals` and `velocities`).  normals: False / True as
     `track_mesh`'s, on the lattice normals; "lattice" or "field": the reference mesh takes those normals
-    (`extract_mesh`'s normals=) and they are carried along."""
+    (`extract_mesh`'s normals=) and they are carried along.  refine / refine_reach: `extract_mesh`'s; the reference
+    mesh is refined before it is tracked."""
     max_iters, tol = ops.check_solve(max_iters, tol)
     ops.check_method(method)
     kind = "lattice" if isinstance(normals, bool) else check_mesh_normals(normals)
     mesh = extract_mesh(field, t_ref, reso, sigma_thresh, dirs, estimator, apply_act, center, radius, max_cells_per_launch,
-                        normals=kind)
+                        normals=kind, refine=refine, refine_reach=refine_reach)
     return track_mesh(field, mesh, t_ref, times, max_iters=max_iters, tol=tol, method=method, normals=bool(normals),
                       velocities=velocities)
 
@@ -433,12 +502,12 @@ def save_ply(path: str, volume: Dict, dirs_reduce: str = "mean") -> None:
         f.write(rec.tobytes())
 
 
-_MESH_ARRAYS = ("vertices", "normals", "faces", "cube", "sigma", "embedding", "rgb")
+_MESH_ARRAYS = ("vertices", "normals", "faces", "cube", "sigma", "embedding", "rgb", "refined", "offset", "width")
 
 
 def save_mesh_npz(path: str, mesh: Dict) -> None:
     """The mesh's arrays and scalars as a numpy .npz (vertices, normals, faces, cube, sigma, embedding, rgb if present,
-    reso, center, radius, t, sigma_thresh, apply_act)."""
+    refined / offset / width of a refined mesh, reso, center, radius, t, sigma_thresh, apply_act)."""
     out = {k: mesh[k].detach().cpu().numpy() for k in _MESH_ARRAYS if k in mesh}
     out.update(reso=np.int64(mesh["reso"]), center=np.asarray(mesh["center"], np.float32),
                radius=np.float32(mesh["radius"]), t=np.float32(mesh["t"]), sigma_thresh=np.float32(mesh["sigma_thresh"]),
@@ -544,6 +613,10 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--mesh_normals", choices=MESH_NORMALS, default="lattice",
                    help="vertex normals of the meshes: central differences of the density lattice, or the field's analytic "
                         "gradient at the vertices")
+    p.add_argument("--mesh_refine", action="store_true",
+                   help="with --mesh: move every vertex along its normal onto density == sigma_thresh (bisection on the field)")
+    p.add_argument("--mesh_refine_reach", type=float, default=1.0, metavar="R",
+                   help="--mesh_refine: how far from a vertex the surface is searched, in lattice spacings")
     p.add_argument("--mesh_track", type=float, default=None, metavar="T_REF",
                    help="with --mesh: also write ONE mesh that moves -- the mesh of time T_REF, its vertices tracked to every "
                         "time of --times by inverting the warp: tracked_%%04d.ply per time and tracked.npz")
@@ -588,6 +661,10 @@ def main(argv=None) -> int:
         raise SystemExit("--n_dirs must be >= 0")
     if a.mesh_track is not None and not a.mesh:
         raise SystemExit("--mesh_track needs --mesh")
+    if a.mesh_refine and not a.mesh:
+        raise SystemExit("--mesh_refine needs --mesh")
+    if not (np.isfinite(a.mesh_refine_reach) and a.mesh_refine_reach > 0):
+        raise SystemExit("--mesh_refine_reach must be positive")
     extra = {} if a.moving_step is None else dict(moving_step=a.moving_step)
     cfg = trainer.resolve_config(a.preset, None, log2_hashmap_size=a.log2_hashmap_size, **extra)
     ckpt = checkpoint.read_checkpoint(a.load_model)
@@ -613,16 +690,21 @@ def main(argv=None) -> int:
         else:
             mesh_dirs = torch.from_numpy(fibonacci_dirs(a.mesh_dirs)).to(field.hash_table.device)
         meshes = extract_mesh_sequence(field, a.times, reso=a.reso, sigma_thresh=a.sigma_thresh, dirs=mesh_dirs,
-                                       estimator=None if a.no_occupancy else estimator, normals=a.mesh_normals)
+                                       estimator=None if a.no_occupancy else estimator, normals=a.mesh_normals,
+                                       refine=a.mesh_refine, refine_reach=a.mesh_refine_reach)
         for i, mesh in enumerate(meshes):
             stem = os.path.join(a.out, f"mesh_{i:04d}")
             save_mesh_npz(stem + ".npz", mesh)
             save_mesh_ply(stem + ".ply", mesh)
             print(f"t={mesh['t']:g}: {mesh['vertices'].shape[0]} vertices, {mesh['faces'].shape[0]} triangles -> "
                   f"{stem}.npz / .ply", flush=True)
+            if a.mesh_refine:
+                share = 100.0 * float(mesh["refined"].float().mean()) if mesh["refined"].numel() else 0.0
+                print(f"t={mesh['t']:g}: {share:.2f} % of the vertices refined onto sigma == {a.sigma_thresh:g}", flush=True)
         if a.mesh_track is not None:
             ref = extract_mesh(field, a.mesh_track, reso=a.reso, sigma_thresh=a.sigma_thresh, dirs=mesh_dirs,
-                               estimator=None if a.no_occupancy else estimator, normals=a.mesh_normals)
+                               estimator=None if a.no_occupancy else estimator, normals=a.mesh_normals,
+                               refine=a.mesh_refine, refine_reach=a.mesh_refine_reach)
             tracked = track_mesh(field, ref, a.mesh_track, a.times, max_iters=a.track_iters, tol=a.track_tol,
                                  method=a.mesh_track_method, normals=a.mesh_track_normals)
             save_tracked_npz(os.path.join(a.out, "tracked.npz"), tracked)

@@ -299,6 +299,29 @@ class DNGPradianceField(torch.nn.Module):
         return sigma[:, None], out
 
     @torch.no_grad()
+    def query_level_set(self, origins: torch.Tensor, directions: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor,
+                        t: torch.Tensor, sigma_thresh: float = 1.0, max_iters: int = 32, tol: float = 0.0):
+        """Where the density reaches sigma_thresh along rays: per row the ray origins + directions * s, a bracket
+        [lo, hi] of distances and a time t ([N], or one value for all rows), bisected on `query_density` in this field's
+        mlp_precision, from one launch that keeps the rows in registers (ced_field_level_set; include/cednerf_hip.h states
+        it operation by operation).  origins / directions are viewed as [-1, 3], lo / hi as [-1].  Returns
+        (t [N], x [N,3], sigma [N], width [N], status [N] int32, evals [N] int32):
+            status 0  a crossing: density(x) = sigma >= sigma_thresh > density one `width` back along the ray; with
+                      tol = 0 and enough rounds (max_iters 0 .. 64) width is 0 or one float32 spacing at t,
+            status 1  the bracket starts at or above the threshold: t = lo, width = 0,
+            status 2  the bracket's end is below the threshold (or NaN): t = hi, width = hi - lo.
+        The bisection stops when hi - lo <= tol, when the midpoint is an endpoint, or after max_iters rounds; evals counts
+        the density evaluations (the two endpoints included)."""
+        sigma_thresh, max_iters, tol = ops.check_level_set(sigma_thresh, max_iters, tol)
+        if not (origins.is_cuda and directions.is_cuda and lo.is_cuda and hi.is_cuda):
+            raise NotImplementedError("Only support cuda inputs: query_level_set runs on the HIP kernel (no CPU fallback).")
+        o = origins.reshape(-1, 3).float().contiguous()
+        times = torch.as_tensor(t, dtype=torch.float32, device=o.device).reshape(-1).contiguous()
+        return ops.field_level_set(self._descriptor(), o, directions.reshape(-1, 3).float().contiguous(),
+                                   lo.reshape(-1).float().contiguous(), hi.reshape(-1).float().contiguous(), times,
+                                   sigma_thresh, max_iters, tol)
+
+    @torch.no_grad()
     def query_move_inverse(self, c: torch.Tensor, t: torch.Tensor, max_iters: int = 32, tol: float = 1e-6,
                            init: Optional[torch.Tensor] = None, method: str = "fixed_point"):
         """The inverse of the warp: per row the x with x + move(x, t) = c, `move` being `query_move`'s.  The density at

@@ -1490,6 +1490,73 @@ def field_density_time_max(desc: _lib.FieldDesc, positions, times, out=None):
     return out
 
 
+def surface_first_crossing(packed_info, t_starts, t_ends, sigmas, thresh: float):
+    """ced_surface_first_crossing: per ray of packed_info [N,2] the first sample with sigma >= thresh and the bracket that
+    holds the crossing -> (k [N] int64, -1 where there is none; lo [N]; hi [N]).  hi is sample k's midpoint, lo the
+    midpoint of the sample before it where that one ends at sample k's start, else sample k's start; 0 for k = -1."""
+    _chk(packed_info, torch.int64, "packed_info")
+    _chk(t_starts, torch.float32, "t_starts"); _chk(t_ends, torch.float32, "t_ends"); _chk(sigmas, torch.float32, "sigmas")
+    n, s = packed_info.shape[0], t_starts.shape[0]
+    if packed_info.shape != (n, 2) or t_starts.shape != (s,) or t_ends.shape != (s,) or sigmas.numel() != s:
+        raise ValueError(f"surface_first_crossing: packed_info [N,2], t_starts / t_ends / sigmas [S]: got "
+                         f"{list(packed_info.shape)}, {list(t_starts.shape)}, {list(t_ends.shape)}, {list(sigmas.shape)}")
+    thresh = float(thresh)
+    if thresh != thresh:
+        raise ValueError("surface_first_crossing: thresh is a NaN")
+    dev = packed_info.device
+    k = torch.empty((n,), device=dev, dtype=torch.int64)
+    lo = torch.empty((n,), device=dev, dtype=torch.float32)
+    hi = torch.empty((n,), device=dev, dtype=torch.float32)
+    rc = _lib.lib().ced_surface_first_crossing(n, _p(packed_info), _p(t_starts), _p(t_ends), _p(sigmas), thresh, _p(k), _p(lo),
+                                               _p(hi), _stream())
+    _lib.check(rc, "surface_first_crossing")
+    return k, lo, hi
+
+
+LEVEL_SET_MAX_ITERS = 64                          # ced_field_level_set: 0 <= max_iters <= 64
+LEVEL_SET_OUTPUTS = ("t", "x", "sigma", "width", "status", "evals")   # its outputs, in `want=` order
+_LEVEL_SET = (("t", *_F32_1), ("x", *_F32_3), ("sigma", *_F32_1), ("width", *_F32_1), ("status", (), torch.int32),
+              ("evals", (), torch.int32))
+
+
+def check_level_set(sigma_thresh, max_iters, tol):
+    """(sigma_thresh, max_iters, tol) of the bisection as (float, int, float), or ValueError: a number > 0, an int in
+    0 .. 64, a number >= 0."""
+    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or not 0 <= int(max_iters) <= LEVEL_SET_MAX_ITERS:
+        raise ValueError(f"max_iters must be an int in 0 .. {LEVEL_SET_MAX_ITERS}, got {max_iters!r}")
+    try:
+        thresh_f, tol_f = float(sigma_thresh), float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"sigma_thresh must be a number > 0 and tol a number >= 0, got {sigma_thresh!r}, {tol!r}") from None
+    if not thresh_f > 0.0:                        # refuses a NaN too
+        raise ValueError(f"sigma_thresh must be a number > 0, got {sigma_thresh!r}")
+    if not tol_f >= 0.0:
+        raise ValueError(f"tol must be a number >= 0, got {tol!r}")
+    return thresh_f, int(max_iters), tol_f
+
+
+def field_level_set(desc: _lib.FieldDesc, origins, dirs, lo, hi, times, thresh: float = 1.0, max_iters: int = 32,
+                    tol: float = 0.0, want=(True, True, True, True, True, True)):
+    """ced_field_level_set: per row the bisection of the density along o + d * t on the bracket [lo, hi], from one launch.
+    origins / dirs [n,3], lo / hi [n], times [n] or [1] (one time for all rows) -> (t [n], x [n,3], sigma [n], width [n],
+    status [n] int32, evals [n] int32): status 0 = a crossing, sigma(t - width) < thresh <= sigma(t) = `sigma`; 1 = the
+    bracket starts at or above the threshold (t = lo); 2 = it never reaches it (t = hi).  sigma has `field_forward`'s bits
+    (include/cednerf_hip.h states every operation).  want = which of the six to compute; the others come back as None."""
+    thresh, max_iters, tol = check_level_set(thresh, max_iters, tol)
+    _chk(origins, torch.float32, "origins"); _chk(dirs, torch.float32, "dirs")
+    _chk(lo, torch.float32, "lo"); _chk(hi, torch.float32, "hi"); _chk(times, torch.float32, "times")
+    n = origins.shape[0]
+    if origins.shape != (n, 3) or dirs.shape != (n, 3) or lo.shape != (n,) or hi.shape != (n,) or times.numel() not in (1, n):
+        raise ValueError(f"field_level_set: origins / dirs [n,3], lo / hi [n], times [n] or [1]: got {list(origins.shape)}, "
+                         f"{list(dirs.shape)}, {list(lo.shape)}, {list(hi.shape)}, {list(times.shape)}")
+    t_per_row = int(times.numel() == n and n != 1)
+    outs = _outputs(_LEVEL_SET, n, origins.device, want, None, "field_level_set")
+    rc = _lib.lib().ced_field_level_set(C.byref(desc), n, _p(origins), _p(dirs), _p(lo), _p(hi), _p(times), t_per_row, thresh,
+                                        max_iters, tol, *[_p(o) for o in outs], _stream())
+    _lib.check(rc, "field_level_set")
+    return tuple(outs)
+
+
 def occ_time_slices_workspace(n_bins: int, levels: int, res: int, device) -> torch.Tensor:
     """The zeroed `hit` workspace of one build of time slices (ced_occ_time_slices_workspace_bytes)."""
     need = int(_lib.lib().ced_occ_time_slices_workspace_bytes(int(n_bins), int(levels), int(res)))

@@ -330,6 +330,102 @@ def render_normals(
 
 
 @torch.no_grad()
+def render_surface(
+    radiance_field: torch.nn.Module,
+    estimator: OccGridEstimator,
+    rays: Rays,
+    sigma_thresh: float = 1.0,
+    near_plane: float = 0.0,
+    far_plane: float = 1e10,
+    render_step_size: float = 1e-3,
+    cone_angle: float = 0.0,
+    test_chunk_size: int = 8192,
+    timestamps: Optional[torch.Tensor] = None,
+    max_iters: int = 32,
+    tol: float = 0.0,
+    render_bkgd: Optional[torch.Tensor] = None,
+    normals: bool = True,
+    colors: bool = True,
+):
+    """The visible surface as a level set of the density: per ray the FIRST point at which the density reaches
+    sigma_thresh, located to float32 resolution -- where `render_image`'s depth is a weighted mean that floats in front of
+    or behind the surface wherever the density is soft.  Eval frames only (one time per frame).  Per pass of rays:
+    every sample of the grid is marched to the far plane (`estimator.march`, no visibility filter), the density is taken
+    at every sample (`query_rays`), ced_surface_first_crossing finds each ray's first sample at or above the threshold
+    and the bracket before it, and ced_field_level_set bisects the density on that bracket (`query_level_set` states the
+    verdicts), all rows of the pass in one launch.
+    "First" means first at the marching step: structure thinner than render_step_size that lies between two samples'
+    midpoints can be missed, exactly as `render_image` can miss it, and the bracket then closes on a later crossing.
+    Returns a dict shaped like `rays` ([H,W,.] or flat [N,.]):
+        hit [..,1] bool       status 0 or 1: a crossing, or a first sample that already lies at or above the threshold
+        depth [..,1]          the distance t along the ray; 0 on misses
+        position [..,3]       origin + direction * depth in float32 (a multiply, then an add); 0 on misses
+        normal [..,3]         `query_normals`(position, t)[0]; 0 on misses, and without normals=True
+        rgb [..,3]            the field's colour at `position` seen along the ray's direction; on misses render_bkgd if
+                              given, else 0; 0 without colors=True
+        sigma, width [..,1]   the density at `position` and the width of the final bracket (the bisection's, also for
+                              status 2; 0 for status -1)
+        status [..,1] int32   0 / 1 / 2 as `query_level_set`; -1: no sample of the ray reaches the threshold.  Status 2 (the
+                              density at the candidate's midpoint, re-evaluated, is below the threshold) counts as a miss
+        sample [..,1] int64   the index, within the ray's marched samples, of the candidate sample; -1 if none
+        n_samples, n_evals    Python ints: samples marched, density evaluations of the bisection."""
+    estimator = grid_for(estimator, timestamps)
+    _check_eval_frame(radiance_field, timestamps, "render_surface")
+    thresh, max_iters, tol = ops.check_level_set(sigma_thresh, max_iters, tol)
+    rays, rays_shape, num_rays = _flatten_rays(rays)
+    dev = rays.origins.device
+    ts = timestamps.reshape(-1).float().contiguous()[:1]
+    pass_rays = max(test_chunk_size, (_EVAL_PASS_RAYS // test_chunk_size) * test_chunk_size)
+    bk = None if render_bkgd is None else render_bkgd.to(dev, torch.float32).reshape(-1)
+    out = {k: torch.zeros((num_rays, c), device=dev, dtype=dt) for k, c, dt in (
+        ("depth", 1, torch.float32), ("position", 3, torch.float32), ("normal", 3, torch.float32), ("rgb", 3, torch.float32),
+        ("sigma", 1, torch.float32), ("width", 1, torch.float32))}
+    out["status"] = torch.full((num_rays, 1), -1, device=dev, dtype=torch.int32)
+    out["sample"] = torch.full((num_rays, 1), -1, device=dev, dtype=torch.int64)
+    n_samples = n_evals = 0
+    for i in range(0, num_rays, pass_rays):
+        o = rays.origins[i:i + pass_rays].contiguous().float()
+        d = rays.viewdirs[i:i + pass_rays].contiguous().float()
+        t_starts, t_ends, ray_indices, packed = estimator.march(
+            o, d, near_plane=near_plane, far_plane=far_plane, render_step_size=render_step_size, stratified=False,
+            cone_angle=cone_angle)
+        n_samples += int(t_starts.shape[0])
+        if t_starts.shape[0] == 0:
+            continue
+        sigmas = radiance_field.query_rays(o, d, ray_indices, t_starts, t_ends, ts, want_rgb=False)[1]
+        k, lo, hi = ops.surface_first_crossing(packed, t_starts, t_ends, sigmas.reshape(-1), thresh)
+        cand = torch.nonzero(k >= 0).squeeze(1)
+        if cand.numel() == 0:
+            continue
+        oc, dc = o[cand].contiguous(), d[cand].contiguous()
+        t, x, sg, width, status, evals = ops.field_level_set(radiance_field._descriptor(), oc, dc, lo[cand].contiguous(),
+                                                             hi[cand].contiguous(), ts, thresh, max_iters, tol)
+        n_evals += int(evals.sum().item())
+        rows = cand + i
+        ok = status < 2
+        out["status"][rows, 0] = status
+        out["sample"][rows, 0] = k[cand] - packed[cand, 0]
+        out["sigma"][rows, 0] = sg
+        out["width"][rows, 0] = width
+        out["depth"][rows, 0] = torch.where(ok, t, torch.zeros_like(t))
+        out["position"][rows] = torch.where(ok[:, None], x, torch.zeros_like(x))
+        hit_rows, xh = rows[ok], x[ok].contiguous()
+        if hit_rows.numel() and (normals or colors):
+            th = ts.expand(xh.shape[0]).contiguous()
+            if normals:
+                out["normal"][hit_rows] = radiance_field.query_normals(xh, th)[0]
+            if colors:
+                out["rgb"][hit_rows] = radiance_field(xh, th, dc[ok].contiguous())[0]
+    hit = (out["status"] == 0) | (out["status"] == 1)
+    if bk is not None:
+        out["rgb"] = torch.where(hit, out["rgb"], bk.expand(num_rays, 3))
+    out["hit"] = hit
+    res = {k: v.view((*rays_shape[:-1], v.shape[-1])) for k, v in out.items()}
+    res["n_samples"], res["n_evals"] = n_samples, n_evals
+    return res
+
+
+@torch.no_grad()
 def render_scene_flow(
     radiance_field: torch.nn.Module,
     estimator: OccGridEstimator,

@@ -19,7 +19,7 @@ import torch
 from . import ops
 from .dist import PipelinedRenderer, ShardedRenderer
 from .nerfacc_api import TimeSlicedOccGrid
-from .utils import Rays, render_motion, render_normals, render_optical_flow, render_scene_flow
+from .utils import Rays, render_motion, render_normals, render_optical_flow, render_scene_flow, render_surface
 
 
 def frame_to_uint8(rgb: torch.Tensor, depth: torch.Tensor, flip_w: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -32,7 +32,8 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
                  n_frames: int, max_samples: int = 1024, render_kwargs: Optional[Dict] = None, frames_in_flight: int = 3,
                  flip_w: bool = True, to_host: bool = False, keep_float: bool = False, frames_per_call: int = 1,
                  motion: bool = False, normals: bool = False, scene_flow: bool = False,
-                 optical_flow: Optional[Tuple[Callable[[int], Callable], float]] = None) -> List[Dict]:
+                 optical_flow: Optional[Tuple[Callable[[int], Callable], float]] = None,
+                 surface: Optional[Dict] = None) -> List[Dict]:
     """Render frames 0..n_frames-1 of a path.
 
     rays_of_frame(i) -> Rays with [H,W,3] device tensors (e.g. `cameras.pinhole_rays(K, c2w_i, W, H)`; it is called on
@@ -51,6 +52,9 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
     optical_flow=(projector_of_frame, dt): likewise `flow_f32` [H,W,2] and `flow_coverage_f32` [H,W,1],
     `utils.render_optical_flow` with project = projector_of_frame(i) (e.g. `cameras.pinhole_projector(K, c2w_i)`) and the
     time step dt; the expected flow of the visible surface, in pixels per dt, is flow_f32 / flow_coverage_f32.
+    surface=dict(sigma_thresh=...[, max_iters=, tol=]): likewise `surface_depth_f32` [H,W,1], `surface_normals_f32` [H,W,3]
+    and `surface_hit` [H,W,1] bool: the first point of every ray at which the density reaches sigma_thresh
+    (`utils.render_surface`'s depth, normal and hit), not a weighted mean over the ray's samples.
     estimator may be a `TimeSlicedOccGrid`: every native call then marches through `estimator.at_time(the times of its
     frames)` -- the frames' times are read to the host once, before the pipeline starts -- and the post passes resolve
     their grid per frame (`utils.grid_for`)."""
@@ -117,4 +121,13 @@ def render_video(radiance_field, estimator, rays_of_frame: Callable[[int], Rays]
             flow, _, coverage, _ = render_optical_flow(radiance_field, estimator, rays_of_frame(i), projector_of_frame(i), dt,
                                                        timestamps=timestamps_of_frame(i), **kw)
             f.update(flow_f32=flow, flow_coverage_f32=coverage)
+    if surface is not None:
+        unknown = set(surface) - {"sigma_thresh", "max_iters", "tol"}
+        if unknown:
+            raise ValueError(f"surface= takes sigma_thresh, max_iters and tol, got {sorted(unknown)}")
+        skw = {k: v for k, v in kw.items() if k != "alpha_thre"}
+        for i, f in enumerate(frames):
+            s = render_surface(radiance_field, estimator, rays_of_frame(i), timestamps=timestamps_of_frame(i), colors=False,
+                               **skw, **surface)
+            f.update(surface_depth_f32=s["depth"], surface_normals_f32=s["normal"], surface_hit=s["hit"])
     return frames

@@ -469,6 +469,42 @@ int ced_occ_time_slices(int64_t n, const int64_t *cell_ids, const float *max_sig
                         float thre, int32_t levels, int32_t res, const uint8_t *union_binaries, int32_t dilate,
                         uint8_t *out, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- the density's level set along rays: the first crossing per ray, then bisection on the field ----
+ * ced_surface_first_crossing: per ray of packed_info [n_rays, 2] int64 (first sample, count) over the samples t_starts /
+ * t_ends / sigmas [S]:
+ *     k  = the index (into the S samples) of the ray's first sample with sigma >= thresh; a NaN never qualifies;
+ *          -1 if there is none or the ray has no samples
+ *     hi = (t_starts[k] + t_ends[k]) / 2
+ *     lo = (t_starts[k-1] + t_ends[k-1]) / 2 if sample k-1 belongs to the same ray and t_ends[k-1] == t_starts[k]
+ *          (contiguous), else t_starts[k]
+ *     lo = hi = 0 for k = -1
+ * each a single float32 operation.  k [n_rays] int64, lo / hi [n_rays] floats.  One lane per ray on the compositing
+ * kernels' sample walk, no atomics: deterministic.
+ *
+ * ced_field_level_set: per row a ray o + d * t, a bracket [lo, hi] and a time (times [n], or [1] with t_per_row == 0).
+ * With every line one float32 operation, no contraction,
+ *     p(t) = o + d * t                       (multiply, then add, per axis)
+ *     f(t) = sigma(p(t), time)               (ced_field_forward's bits in the descriptor's arithmetic, 0 outside the box)
+ *     s_lo = f(lo); s_hi = f(hi); evals = 2
+ *     status 1 if s_lo >= thresh:            t = lo, sigma = s_lo, width = 0
+ *     status 2 else if !(s_hi >= thresh):    t = hi, sigma = s_hi, width = hi - lo
+ *     status 0 otherwise; then at most max_iters rounds:
+ *         if hi - lo <= tol: stop
+ *         m = (lo + hi) / 2;  if m == lo or m == hi: stop
+ *         s = f(m); evals += 1
+ *         if s >= thresh: hi = m, s_hi = s   else: lo = m        (a NaN goes to lo)
+ *       t = hi, sigma = s_hi, width = hi - lo
+ * so that a status-0 row holds f(t - width) < thresh <= f(t).  Outputs, any of which may be NULL (not all): t [n],
+ * x [n,3] = p(t), sigma [n], width [n], status [n] int32, evals [n] int32.  A wave keeps its rows and their brackets in
+ * registers across the rounds; a row's outputs do not depend on n or on the other rows.  Limits: thresh > 0,
+ * 0 <= max_iters <= CED_LEVEL_SET_MAX_ITERS, tol >= 0, n >= 0; n == 0 launches nothing. */
+#define CED_LEVEL_SET_MAX_ITERS 64
+int ced_surface_first_crossing(int64_t n_rays, const int64_t *packed_info, const float *t_starts, const float *t_ends,
+                               const float *sigmas, float thresh, int64_t *k, float *lo, float *hi, void *stream);
+int ced_field_level_set(const ced_field_desc *desc, int64_t n, const float *origins, const float *dirs, const float *lo,
+                        const float *hi, const float *times, int32_t t_per_row, float thresh, int32_t max_iters, float tol,
+                        float *t, float *x, float *sigma, float *width, int32_t *status, int32_t *evals, void *stream);
+
 /* DNGPradianceField._query_rgb(dir, embedding, apply_act) -- cednerf/model.py:447-466: dirs [n,3] are normalised,
  * mapped to [0,1], SH degree 2; mlp_head on [SH(4), embedding(15)]; the sigmoid iff apply_act.  embedding [n,15] is what
  * ced_field_forward writes to `geo`; rgb [n,3].  The head runs in the arithmetic of desc->mlp_precision. */
