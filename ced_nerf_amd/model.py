@@ -112,6 +112,7 @@ class DNGPradianceField(torch.nn.Module):
         self.mlp_head = torch.nn.ParameterList([P(64, 19), P(64, 64), P(3, 64)])
         self._packed: Optional[torch.Tensor] = None
         self._packed_key = None
+        self._packed_src = None                              # the tensors `_packed_key` was taken from, kept alive
         self._desc: Optional[_lib.FieldDesc] = None
         self._desc_lock = __import__("threading").Lock()     # frames in flight share one field
 
@@ -152,21 +153,27 @@ class DNGPradianceField(torch.nn.Module):
 
     def __getstate__(self):            # copy.deepcopy / pickle: drop the device-side caches and the lock
         state = self.__dict__.copy()
-        for k in ("_desc_lock", "_desc", "_packed", "_packed_key"):
+        for k in ("_desc_lock", "_desc", "_packed", "_packed_key", "_packed_src"):
             state.pop(k, None)
         return state
 
     def __setstate__(self, state):
         self.__dict__.update(state)
-        self._packed, self._packed_key, self._desc = None, None, None
+        self._packed, self._packed_key, self._packed_src, self._desc = None, None, None, None
         self._desc_lock = __import__("threading").Lock()
 
     def _weights(self):
         return list(self.xyz_wrap) + list(self.mlp_base) + list(self.mlp_head)
 
     def weights_changed(self) -> None:
-        """Re-pack the MLP weights at the next launch.  The packed blob is keyed on the tensors' version counters; an
-        update that writes them without advancing the counters (torch's fused Adam) must say so here."""
+        """Re-pack the MLP weights and re-read the box at the next launch.  The packed blob is keyed on the tensors'
+        addresses and version counters; an update that writes them in place without advancing the counters must say so
+        here.  Two kinds do: an optimiser that steps outside autograd's bookkeeping (torch's fused Adam may), and every
+        in-place write through `.data` (`w.data.mul_(..)`, `w.data.copy_(..)`, `aabb.data.add_(..)`), which is as invisible
+        to the key as fused Adam's.  Followed without this call: in-place writes to the tensor itself under no_grad
+        (`w.copy_`, `w.mul_`), `load_state_dict`, the checkpoint loaders, `w.data = other`, `.to(device)`,
+        `set_mlp_precision`, and assignments to `MOVING_STEP`, `use_div_offsets` and `time_mode`.  The hash table is
+        read in place, so every write to it is seen by the next launch."""
         with self._desc_lock:
             self._packed_key = None
 
@@ -176,8 +183,13 @@ class DNGPradianceField(torch.nn.Module):
 
     def _descriptor_locked(self) -> _lib.FieldDesc:
         ws = self._weights()
+        # Everything the descriptor is made from: the packed tensors by (address, version), the table by address and type
+        # (it is read in place), and the python scalars written into it.  `_packed_src` keeps the storages the key was
+        # taken from alive, so that after `w.data = other` the allocator cannot hand the old address to the new tensor
+        # and re-issue a live key.
         key = (tuple((w.data_ptr(), w._version) for w in ws), self.hash_table.data_ptr(), str(self.hash_table.device),
-               self.aabb.data_ptr(), self.aabb._version, self.mlp_precision)
+               self.hash_table.dtype, self.aabb.data_ptr(), self.aabb._version, self.mlp_precision,
+               self.MOVING_STEP, self.use_div_offsets, self.time_mode)
         if self._desc is not None and key == self._packed_key:
             return self._desc
         dev = self.hash_table.device
@@ -204,6 +216,7 @@ class DNGPradianceField(torch.nn.Module):
         d.packed_floats = int(self._packed.numel())
         d.hash = hd
         self._desc = d
+        self._packed_src = [w.detach() for w in ws] + [self.aabb.detach()]
         self._packed_key = key
         return d
 

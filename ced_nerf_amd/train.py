@@ -292,8 +292,25 @@ class TrainableField(torch.nn.Module):
             self.mlp_feat_prediction = torch.nn.ParameterList([xavier(64, 32), xavier(2 * h["n_levels"], 64)])
         if self.use_weight_predict:
             self.mlp_weight_prediction = torch.nn.ParameterList([xavier(64, 32), xavier(1, 64)])
+        # the fp16 copy is not part of the state dict: it follows the master a load has just written
+        self.register_load_state_dict_post_hook(_sync_after_load)
 
-    hip_mlp = True                  # False: the layers' y and dx through the library (A/B reference of the tests)
+    def __getstate__(self):            # copy.deepcopy / pickle: the derived state is rebuilt from the copy's own tensors
+        state = self.__dict__.copy()
+        for k in ("_shared", "_aabb6", "_aabb6_key", "_aabb6_src", "_half_key"):
+            state.pop(k, None)
+        return state
+
+    def _apply(self, fn, *args, **kwargs):
+        """`.to(device)` / `.float()` ...: buffers are replaced by new objects, so whatever was derived from the old ones
+        (the shared inference module holds `aabb` and the fp16 table, `_aabb6` the box as python floats) is dropped and
+        rebuilt at the next use."""
+        out = super()._apply(fn, *args, **kwargs)
+        for k in ("_shared", "_aabb6", "_aabb6_key", "_aabb6_src", "_half_key"):
+            self.__dict__.pop(k, None)
+        return out
+
+    hip_mlp = True                 # False: the layers' y and dx through the library (A/B reference of the tests)
     hip_weight_grad = True          # (with hip_mlp False) False: dW through the library as well
 
     def _mlp(self, x, weights):
@@ -333,10 +350,12 @@ class TrainableField(torch.nn.Module):
 
     def _forward_core(self, pos, enc, sh, tt, return_internal):
         # the box as python floats for the fused warp kernel, re-read whenever the buffer is replaced or written in place
-        # (load_state_dict, a checkpoint load, aabb.copy_): keyed like DNGPradianceField._descriptor
+        # (load_state_dict, a checkpoint load, aabb.copy_, aabb.data = ...): keyed like DNGPradianceField._descriptor, the
+        # storage the key was taken from kept alive so that its address cannot come back under a replacement
         key = (self.aabb.data_ptr(), self.aabb._version)
         if getattr(self, "_aabb6_key", None) != key:
             object.__setattr__(self, "_aabb6", [float(v) for v in self.aabb.detach().cpu().tolist()])
+            object.__setattr__(self, "_aabb6_src", self.aabb.detach())
             object.__setattr__(self, "_aabb6_key", key)
         mo = self._mlp(enc, list(self.xyz_wrap))
         xn, move, sel = _WarpFn.apply(pos, mo, self._aabb6, self.moving_step, self.use_div_offsets)   # model.py:356-383
@@ -409,8 +428,20 @@ class TrainableField(torch.nn.Module):
         if self.table_f16:
             with torch.no_grad():
                 self.hash_table_half.copy_(self.hash_table)
+            object.__setattr__(self, "_half_key", (self.hash_table.data_ptr(), self.hash_table._version,
+                                                   self.hash_table_half.data_ptr()))
+
+    def _follow_master_table(self) -> None:
+        """fp16-table fields: refresh the evaluated copy if the master was replaced or written since the last refresh
+        (`hash_table.copy_`, `load_state_dict`, `hash_table.data = ...`), as far as its address and version counter
+        show.  A write that advances neither (a fused optimiser step, a write through `.data`) needs `sync_half_table()`,
+        which `train_step` calls for that reason."""
+        if self.table_f16 and getattr(self, "_half_key", None) != (
+                self.hash_table.data_ptr(), self.hash_table._version, self.hash_table_half.data_ptr()):
+            self.sync_half_table()
 
     def _table_eval(self):
+        self._follow_master_table()
         return self.hash_table_half if self.table_f16 else None
 
     def export_params(self) -> Dict:
@@ -429,7 +460,10 @@ class TrainableField(torch.nn.Module):
     def shared_inference(self):
         """A fused-kernel module on the SAME parameter tensors (no copy): its weight blob is re-packed whenever an
         optimiser step has changed them (the descriptor is keyed on the tensors' versions).  Used for the
-        gradient-free density queries of the sampling pass and of the occupancy-grid refresh."""
+        gradient-free density queries of the sampling pass and of the occupancy-grid refresh.  Ask for it again after
+        a load or a move to another device rather than keeping the returned module: the call is where an fp16 table's
+        evaluated copy catches up with its master, and a device move builds a new module on the new buffers."""
+        self._follow_master_table()
         if getattr(self, "_shared", None) is None:
             from .model import DNGPradianceField
             h = self.hash_cfg
@@ -443,6 +477,11 @@ class TrainableField(torch.nn.Module):
             m.aabb = self.aabb
             object.__setattr__(self, "_shared", m.eval())          # not a sub-module: the parameters are ours
         return self._shared
+
+
+def _sync_after_load(module: TrainableField, _incompatible_keys) -> None:
+    """load_state_dict post-hook: `hash_table_half` is a non-persistent buffer, so a load writes only the master."""
+    module.sync_half_table()
 
 
 def next_num_rays(num_rays: int, n_rendering_samples: int, target_sample_batch_size: int) -> int:
