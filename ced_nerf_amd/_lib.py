@@ -273,7 +273,7 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         _lib = handle
         # process-wide options from the environment: CED_OPTIONS="field_spread_tiles=0,march_two_pass=1" (ced_set_option:
-        # field_spread_tiles, march_two_pass, hash_grad_blocks)
+        # field_spread_tiles, march_two_pass, hash_grad_blocks, frame_sh_per_ray)
         for item in filter(None, os.environ.get("CED_OPTIONS", "").split(",")):
             key, _, value = item.partition("=")
             if handle.ced_set_option(key.strip().encode(), int(value)) != 0:

@@ -15,6 +15,7 @@ namespace ced {
 // Options of ced_set_option: process-wide, read by concurrently rendering threads -> atomics (relaxed: each is an
 // independent launch property; no setting changes a result).
 std::atomic<int> g_field_spread_tiles{ 2 };     // field kernels: tile -> wave mapping (field_device.hpp: field_tile_range)
+std::atomic<int> g_frame_sh_per_ray{ 1 };       // frame renderers: FieldArgs::sh_ray from the per-ray set-up launch (0: per sample in the field kernel)
 std::atomic<int> g_march_two_pass{ -1 };        // frame renderer: first iteration as culling pass + marching of the rest (-1: when there are several grid levels)
 
 int launch_field(const ced_field_desc *d, FieldArgs &A, void *stream)
@@ -87,6 +88,11 @@ extern "C" int ced_set_option(const char *key, int value)
     if (strcmp(key, "march_two_pass") == 0) {
         CED_REQUIRE(value >= -1 && value <= 1, "set_option: march_two_pass must be -1 (automatic), 0 or 1");
         ced::g_march_two_pass = value;
+        return CED_OK;
+    }
+    if (strcmp(key, "frame_sh_per_ray") == 0) {
+        CED_REQUIRE(value == 0 || value == 1, "set_option: frame_sh_per_ray must be 0 or 1");
+        ced::g_frame_sh_per_ray = value;
         return CED_OK;
     }
     if (strcmp(key, "hash_grad_blocks") == 0) {

@@ -62,6 +62,9 @@ struct FieldArgs {
                                                       // rays-mode call (ray_idx32, t0, t1, rgb, sigma) start there
     const float *pos, *t, *dir;                       // explicit mode
     const float *rays_o, *rays_d;                     // rays mode
+    const float *sh_ray;                              // optional (rays mode): [n_rays, 3] colour-head SH inputs of lane groups
+                                                      // 1..3, computed once per ray (field_device.hpp: sh_ray_store); NULL:
+                                                      // the kernel computes them per sample from rays_d
     const int64_t *ray_idx;
     const int32_t *ray_idx32;                         // alternative 32-bit ray indices (frame renderer)
     const float *t0, *t1, *timestamps;
@@ -82,6 +85,7 @@ struct FieldArgs {
 // options of ced_set_option (field.hip)
 extern std::atomic<int> g_march_two_pass;
 extern std::atomic<int> g_field_spread_tiles;
+extern std::atomic<int> g_frame_sh_per_ray;
 extern std::atomic<int> g_hash_grad_blocks;           // hash.hip
 constexpr int kFieldBlocksDefault = 256;      // one persistent workgroup per CU
 

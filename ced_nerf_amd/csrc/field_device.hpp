@@ -136,65 +136,16 @@ __device__ __forceinline__ LevelConst load_level(const uint32_t *lt)
     return L;
 }
 
-// Trilinear gather of one level for one point (hash_encoder_half.py:112-161; temporal variant
-// hash_encoder_inter.py:148-197).  x already clamped to [0,1].  MODE: 0 = this lane's level may be
-// dense or hashed (both index forms computed, selected per lane), 1 = dense, 2 = hashed, 3 = dense with the x-corner
-// pairs fetched by one load each (non-temporal tables, levels followed by another level).
-template <bool F16, bool TEMPORAL, int MODE>
-__device__ __forceinline__ void hash_level(const LevelConst &L, const void *__restrict__ table, const float (&x)[3],
-                                           int k_lo, float t_frac, float &f0, float &f1)
+// The eight corner values of hash_level at byte offsets off[c] (c = cx + 2 cy + 4 cz), both features of a corner as one
+// register pair; a temporal table's key-frames k_lo and k_lo + 1 are interpolated here.  PAIRS (non-temporal): the two x
+// corners of a (y, z) corner come from ONE 16-byte (fp16 table: 8-byte) load at off[2q]; ADJACENT says the caller knows
+// off[2q + 1] == off[2q] + entry size on every lane, otherwise a lane where that fails re-reads its second corner.
+template <bool F16, bool TEMPORAL, bool PAIRS, bool ADJACENT>
+__device__ __forceinline__ void load_corners(const char *__restrict__ tb, const uint32_t (&off)[8], int k_lo, float t_frac,
+                                             f2 (&v)[8])
 {
-    uint32_t g[3];
-    float fr[3], om[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        // p >= 0.5: the conversion truncates = floor, and p - floor(p) is exact, which is what v_fract_f32 returns
-        const float p = x[a] * L.scale + 0.5f;
-        g[a] = (uint32_t)p;
-        fr[a] = __builtin_amdgcn_fractf(p);
-        om[a] = 1.0f - fr[a];
-    }
-    // byte strides: x is the entry size (a power of two: a shift); dense levels have res^2 * EB < 2^24, so
-    // their products are single full-rate 24-bit multiplies; hashed levels need the 32-bit wrap-around product
-    constexpr uint32_t EB = EntryBytes<F16, TEMPORAL>::value;
-    const uint32_t x0 = g[0] * EB;
-    const uint32_t y0 = (MODE == 1 || MODE == 3) ? __umul24(g[1], L.syb) : g[1] * L.syb;
-    const uint32_t z0 = (MODE == 1 || MODE == 3) ? __umul24(g[2], L.szb) : g[2] * L.szb;
-    const uint32_t xs[2] = { x0, x0 + EB };
-    const uint32_t ys[2] = { y0, y0 + L.syb };
-    const uint32_t zs[2] = { z0, z0 + L.szb };
-    const bool hashed = L.hashed != 0;
-    // y/z combinations are shared by the two x corners
-    uint32_t yz_x[4], yz_a[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if constexpr (MODE != 1 && MODE != 3) yz_x[q] = ys[q & 1] ^ zs[q >> 1];
-        if constexpr (MODE != 2) yz_a[q] = ys[q & 1] + zs[q >> 1];
-    }
-    const float wxy[4] = { om[0] * om[1], fr[0] * om[1], om[0] * fr[1], fr[0] * fr[1] };   // index cx + 2*cy
-    uint32_t off[8];
-    float w[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int cx = c & 1, cy = (c >> 1) & 1, cz = (c >> 2) & 1;
-        uint32_t hb = 0, db = 0;
-        if constexpr (MODE != 1 && MODE != 3) hb = (xs[cx] ^ yz_x[cy + 2 * cz]) & L.maskb;
-        if constexpr (MODE != 2) {
-            // idx % size with idx < 2 * size: the unsigned difference wraps to a huge value when idx < size
-            const uint32_t dx = xs[cx] + yz_a[cy + 2 * cz];
-            const uint32_t dw = dx - L.sizeb;
-            db = dx < dw ? dx : dw;
-        }
-        const uint32_t idxb = (MODE == 1 || MODE == 3) ? db : (MODE == 2) ? hb : (hashed ? hb : db);
-        off[c] = L.offb + idxb;
-        w[c] = wxy[cx + 2 * cy] * (cz ? fr[2] : om[2]);
-    }
-    const char *tb = reinterpret_cast<const char *>(table);
-    // both features of a corner travel as one register pair: the interpolation is 8 packed FMAs
-    // (v_pk_fma_f32 is the same IEEE fma per component as two scalar ones)
-    f2 v[8];
     if constexpr (!TEMPORAL) {
-        if constexpr (MODE == 3) {
+        if constexpr (PAIRS) {
             // dense level (not the table's last: field_args.hpp, hash_level_modes): the two x corners of a (y, z) corner are adjacent entries -- ONE
             // 16-byte (fp16 table: 8-byte) load instead of two on the same cache line.  The one exception is the reference's
             // `% size` acting between the two (the +x corner is the level's entry 0): that lane re-reads its second corner.
@@ -205,12 +156,14 @@ __device__ __forceinline__ void hash_level(const LevelConst &L, const void *__re
                     const f4 pr = *reinterpret_cast<const f4 *>(tb + off[2 * q]);
                     v[2 * q] = f2{ pr[0], pr[1] };
                     v[2 * q + 1] = f2{ pr[2], pr[3] };
-                    if (off[2 * q + 1] != off[2 * q] + EBp) v[2 * q + 1] = *reinterpret_cast<const f2 *>(tb + off[2 * q + 1]);
+                    if constexpr (!ADJACENT)
+                        if (off[2 * q + 1] != off[2 * q] + EBp) v[2 * q + 1] = *reinterpret_cast<const f2 *>(tb + off[2 * q + 1]);
                 } else {
                     typedef uint32_t u2v __attribute__((ext_vector_type(2)));
                     const u2v u = *reinterpret_cast<const u2v *>(tb + off[2 * q]);
                     uint32_t u1 = u[1];
-                    if (off[2 * q + 1] != off[2 * q] + EBp) u1 = *reinterpret_cast<const uint32_t *>(tb + off[2 * q + 1]);
+                    if constexpr (!ADJACENT)
+                        if (off[2 * q + 1] != off[2 * q] + EBp) u1 = *reinterpret_cast<const uint32_t *>(tb + off[2 * q + 1]);
                     v[2 * q] = f2{ half_bits_to_float((uint16_t)(u[0] & 0xffffu)), half_bits_to_float((uint16_t)(u[0] >> 16)) };
                     v[2 * q + 1] = f2{ half_bits_to_float((uint16_t)(u1 & 0xffffu)), half_bits_to_float((uint16_t)(u1 >> 16)) };
                 }
@@ -248,6 +201,91 @@ __device__ __forceinline__ void hash_level(const LevelConst &L, const void *__re
                 v[c] = a * omt2 + b * tf2;
             }
         }
+    }
+}
+
+// Trilinear gather of one level for one point (hash_encoder_half.py:112-161; temporal variant
+// hash_encoder_inter.py:148-197).  x already clamped to [0,1].  MODE: 0 = this lane's level may be
+// dense or hashed (both index forms computed, selected per lane), 1 = dense, 2 = hashed, 3 = dense with the x-corner
+// pairs fetched by one load each (non-temporal tables, levels followed by another level).
+template <bool F16, bool TEMPORAL, int MODE>
+__device__ __forceinline__ void hash_level(const LevelConst &L, const void *__restrict__ table, const float (&x)[3],
+                                           int k_lo, float t_frac, float &f0, float &f1)
+{
+    uint32_t g[3];
+    float fr[3], om[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        // p >= 0.5: the conversion truncates = floor, and p - floor(p) is exact, which is what v_fract_f32 returns
+        const float p = x[a] * L.scale + 0.5f;
+        g[a] = (uint32_t)p;
+        fr[a] = __builtin_amdgcn_fractf(p);
+        om[a] = 1.0f - fr[a];
+    }
+    // byte strides: x is the entry size (a power of two: a shift); dense levels have res^2 * EB < 2^24, so
+    // their products are single full-rate 24-bit multiplies; hashed levels need the 32-bit wrap-around product
+    constexpr uint32_t EB = EntryBytes<F16, TEMPORAL>::value;
+    const uint32_t x0 = g[0] * EB;
+    const uint32_t y0 = (MODE == 1 || MODE == 3) ? __umul24(g[1], L.syb) : g[1] * L.syb;
+    const uint32_t z0 = (MODE == 1 || MODE == 3) ? __umul24(g[2], L.szb) : g[2] * L.szb;
+    const uint32_t xs[2] = { x0, x0 + EB };
+    const uint32_t ys[2] = { y0, y0 + L.syb };
+    const uint32_t zs[2] = { z0, z0 + L.szb };
+    const bool hashed = L.hashed != 0;
+    // y/z combinations are shared by the two x corners
+    uint32_t yz_x[4], yz_a[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if constexpr (MODE != 1 && MODE != 3) yz_x[q] = ys[q & 1] ^ zs[q >> 1];
+        if constexpr (MODE != 2) yz_a[q] = ys[q & 1] + zs[q >> 1];
+    }
+    const float wxy[4] = { om[0] * om[1], fr[0] * om[1], om[0] * fr[1], fr[0] * fr[1] };   // index cx + 2*cy
+    float w[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) w[c] = wxy[c & 3] * ((c >> 2) ? fr[2] : om[2]);
+    const char *tb = reinterpret_cast<const char *>(table);
+    uint32_t off[8];
+    f2 v[8];
+    if constexpr (MODE == 1 || MODE == 3) {
+        // Dense level: the reference's `% size` acts only on a corner index >= size, and size >= res^3 while the corner
+        // coordinates reach res -- only cells on the level's far y / z boundary get there.  All strides are positive and
+        // the largest index, corner (1, 1, 1), is below 2 * size (no 32-bit carry), so when xs[1] + yz_a[3] < sizeb
+        // every corner's dx is below sizeb: dx - sizeb wraps to dx + (2^32 - sizeb) > dx and the min below returns dx
+        // itself.  ONE wave-uniform test per call then takes the wrap (add / subtract / min per corner) off the common
+        // path; without it the x corners are xs[0] and xs[0] + EB, adjacent entries, so the pair load needs no re-read
+        // test either, and the level's first byte goes into the four (y, z) sums instead of the eight corners (integer
+        // sums, re-associated: the same byte offsets).
+        if (__ballot(xs[1] + yz_a[3] >= L.sizeb) == 0ull) {
+            uint32_t yz_o[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) yz_o[q] = yz_a[q] + L.offb;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) off[c] = xs[c & 1] + yz_o[c >> 1];
+            load_corners<F16, TEMPORAL, MODE == 3, true>(tb, off, k_lo, t_frac, v);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                // idx % size with idx < 2 * size: the unsigned difference wraps to a huge value when idx < size
+                const uint32_t dx = xs[c & 1] + yz_a[c >> 1];
+                const uint32_t dw = dx - L.sizeb;
+                off[c] = L.offb + (dx < dw ? dx : dw);
+            }
+            load_corners<F16, TEMPORAL, MODE == 3, false>(tb, off, k_lo, t_frac, v);
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const uint32_t hb = (xs[c & 1] ^ yz_x[c >> 1]) & L.maskb;
+            uint32_t idxb = hb;
+            if constexpr (MODE == 0) {
+                const uint32_t dx = xs[c & 1] + yz_a[c >> 1];
+                const uint32_t dw = dx - L.sizeb;
+                const uint32_t db = dx < dw ? dx : dw;
+                idxb = hashed ? hb : db;
+            }
+            off[c] = L.offb + idxb;
+        }
+        load_corners<F16, TEMPORAL, false, false>(tb, off, k_lo, t_frac, v);
     }
     f2 acc = { 0.0f, 0.0f };
 #pragma unroll
@@ -343,6 +381,32 @@ __device__ __forceinline__ void hash_level_dx(const LevelConst &L, const void *_
     const float s = L.scale * dscale;
     d0[0] = gx[0] * s; d0[1] = gy[0] * s; d0[2] = gz[0] * s;
     d1[0] = gx[1] * s; d1[1] = gy[1] * s; d1[2] = gz[1] * s;
+}
+
+// The colour head's SH(4) input of lane group g from the view direction (model.py:447-459; Y00 const, Y1-1 ~ -y,
+// Y10 ~ z, Y11 ~ -x; tcnn maps the unit vector to [0,1] and back): only component g is normalised.  Group 0's constant
+// aside, it depends on the ray alone: the frame renderers compute groups 1..3 once per ray (FieldArgs::sh_ray, entry
+// 3 r + g - 1, written by sh_ray_store) with these very operations, and the field kernels then load instead of recompute.
+__device__ __forceinline__ float sh_head_input(const float (&dv)[3], int g)
+{
+    const float nrm = __builtin_sqrtf((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]);
+    const float comp = (g == 1) ? dv[1] : (g == 2) ? dv[2] : dv[0];
+    const float u = (comp / nrm + 1.0f) / 2.0f;
+    const float vv = u * 2.0f - 1.0f;
+    const float coef = (g == 2) ? 0.48860251190291987f : -0.48860251190291987f;
+    return (g == 0) ? 0.28209479177387814f : coef * vv;
+}
+__device__ __forceinline__ void sh_ray_store(const float *__restrict__ rays_d, int64_t r, float *__restrict__ sh_ray)
+{
+    const float dv[3] = { rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2] };
+#pragma unroll
+    for (int g = 1; g < 4; ++g) sh_ray[3 * r + g - 1] = sh_head_input(dv, g);
+}
+// lane group g's SH input of ray r from that array (group 0 reads entry 0 of the ray and keeps the constant)
+__device__ __forceinline__ float sh_ray_load(const float *__restrict__ sh_ray, int64_t r, int g)
+{
+    const float v = sh_ray[3 * r + (g ? g - 1 : 0)];
+    return (g == 0) ? 0.28209479177387814f : v;
 }
 
 __device__ __forceinline__ void temporal_keyframe(float tq, int &k_lo, float &t_frac)

@@ -265,21 +265,21 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
 
         if (A.want_rgb) {
             // --- head input [SH(4), geo(15)] (model.py:447-459): element 0 = SH_g, 1..4 = this lane's geo ---
+            // lane group g feeds SH coefficient g (field_device.hpp: sh_head_input): one load where the caller computed it per
+            // ray (frame renderers), else from the direction (wave-uniform choice)
+            const bool sh_per_ray = A.rays_mode && A.sh_ray;
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                float dv[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-                    dv[a] = A.rays_mode ? A.rays_d[3 * ridx[j] + a] : A.dir[3 * (tile_base + sofs[j]) + a];
-                const float nrm = __builtin_sqrtf((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]);
-                // lane group g feeds SH coefficient g: only that direction component is normalised (as field_kernel.hpp)
-                const float comp = (g == 1) ? dv[1] : (g == 2) ? dv[2] : dv[0];
-                const float u = (comp / nrm + 1.0f) / 2.0f;
-                const float vv = u * 2.0f - 1.0f;
-                const float coef = (g == 2) ? 0.48860251190291987f : -0.48860251190291987f;
-                const float sh = (g == 0) ? 0.28209479177387814f : coef * vv;
                 float hin[8];
-                hin[0] = sh;
+                if (sh_per_ray) {
+                    hin[0] = sh_ray_load(A.sh_ray, ridx[j], g);
+                } else {
+                    float dv[3];
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+                        dv[a] = A.rays_mode ? A.rays_d[3 * ridx[j] + a] : A.dir[3 * (tile_base + sofs[j]) + a];
+                    hin[0] = sh_head_input(dv, g);
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hin[1 + r] = __builtin_amdgcn_fmed3f(D[j][0][r], -kHalfMax, kHalfMax);
                 hin[4] = (g == 3) ? 0.0f : hin[4];

@@ -387,17 +387,16 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
                 h8 Bh[NT][2], Bl[NT][2];
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    float dv[3];
-#pragma unroll
-                    for (int a = 0; a < 3; ++a)
-                        dv[a] = A.rays_mode ? A.rays_d[3 * ridx[j] + a] : A.dir[3 * sidx[j] + a];
-                    const float nrm = __builtin_sqrtf((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]);
-                    const float comp = (g == 1) ? dv[1] : (g == 2) ? dv[2] : dv[0];
-                    const float u = (comp / nrm + 1.0f) / 2.0f;
-                    const float vv = u * 2.0f - 1.0f;
-                    const float coef = (g == 2) ? 0.48860251190291987f : -0.48860251190291987f;
                     float hin[8];
-                    hin[0] = (g == 0) ? 0.28209479177387814f : coef * vv;
+                    if (A.rays_mode && A.sh_ray) {           // computed once per ray by the caller (field_device.hpp: sh_head_input)
+                        hin[0] = sh_ray_load(A.sh_ray, ridx[j], g);
+                    } else {
+                        float dv[3];
+#pragma unroll
+                        for (int a = 0; a < 3; ++a)
+                            dv[a] = A.rays_mode ? A.rays_d[3 * ridx[j] + a] : A.dir[3 * sidx[j] + a];
+                        hin[0] = sh_head_input(dv, g);
+                    }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) hin[1 + r] = __builtin_amdgcn_fmed3f(D[j][0][r], -kHalfMax, kHalfMax);
                     hin[4] = (g == 3) ? 0.0f : hin[4];
@@ -430,18 +429,17 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const float geo_tail = (g == 3) ? 0.0f : D[j][0][0];
-                float dv[3];
+                // lane group g feeds SH coefficient g (field_device.hpp: sh_head_input): loaded where the caller computed
+                // it once per ray, else from the direction
+                if (A.rays_mode && A.sh_ray) {
+                    B[j][0] = sh_ray_load(A.sh_ray, ridx[j], g);
+                } else {
+                    float dv[3];
 #pragma unroll
-                for (int a = 0; a < 3; ++a)
-                    dv[a] = A.rays_mode ? A.rays_d[3 * ridx[j] + a] : A.dir[3 * sidx[j] + a];
-                const float nrm = __builtin_sqrtf((dv[0] * dv[0] + dv[1] * dv[1]) + dv[2] * dv[2]);
-                // lane group g feeds SH coefficient g: only that one direction component is normalised here
-                // (Y00 const, Y1-1 ~ -y, Y10 ~ z, Y11 ~ -x; tcnn maps the unit vector to [0,1] and back)
-                const float comp = (g == 1) ? dv[1] : (g == 2) ? dv[2] : dv[0];
-                const float u = (comp / nrm + 1.0f) / 2.0f;
-                const float vv = u * 2.0f - 1.0f;
-                const float coef = (g == 2) ? 0.48860251190291987f : -0.48860251190291987f;
-                B[j][0] = (g == 0) ? 0.28209479177387814f : coef * vv;
+                    for (int a = 0; a < 3; ++a)
+                        dv[a] = A.rays_mode ? A.rays_d[3 * ridx[j] + a] : A.dir[3 * sidx[j] + a];
+                    B[j][0] = sh_head_input(dv, g);
+                }
                 B[j][1] = D[j][0][1];
                 B[j][2] = D[j][0][2];
                 B[j][3] = D[j][0][3];

@@ -24,6 +24,7 @@
 #include "ced_common.hpp"
 #include "composite_core.hpp"
 #include "field_args.hpp"
+#include "field_device.hpp"
 #include "march_accel.hpp"
 
 #ifdef CED_MARCH_DIAG
@@ -206,17 +207,18 @@ __global__ __launch_bounds__(256) void frame_times_kernel(int64_t n_rays, int ra
 }
 
 // Per-ray setup of cednerf/utils.py:197-225: zero the pixel accumulators, near planes, ray/AABB intersection per grid
-// level and the stably sorted entry/exit event list.
+// level and the stably sorted entry/exit event list; the colour head's per-ray SH inputs (FieldArgs::sh_ray).
 __global__ __launch_bounds__(256) void frame_prep_kernel(int64_t n_rays, const float *__restrict__ rays_o,
                                                          const float *__restrict__ rays_d, int m,
                                                          const float *__restrict__ aabbs, float near_plane,
                                                          float *__restrict__ t_sorted, uint8_t *__restrict__ t_indices,
                                                          uint8_t *__restrict__ hits, float *__restrict__ near_planes,
-                                                         float *__restrict__ rgb,
+                                                         float *__restrict__ sh_ray, float *__restrict__ rgb,
                                                          float *__restrict__ opacity, float *__restrict__ depth)
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
+    sh_ray_store(rays_d, r, sh_ray);
     const float o[3] = { rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2] };
     const float inv_d[3] = { 1.0f / rays_d[3 * r], 1.0f / rays_d[3 * r + 1], 1.0f / rays_d[3 * r + 2] };
     float ev[2 * kMaxGrids];
@@ -248,13 +250,15 @@ __global__ __launch_bounds__(256) void frame_prep_kernel(int64_t n_rays, const f
 }
 
 // One grid level: the marching recomputes the ray/box interval itself (march_accel.hpp, SINGLE), so the set-up is only
-// the zeroing of the accumulators and the near planes.
-__global__ __launch_bounds__(256) void frame_prep_single_kernel(int64_t n_rays, float near_plane, float *__restrict__ near_planes,
-                                                                float *__restrict__ rgb, float *__restrict__ opacity,
-                                                                float *__restrict__ depth)
+// the zeroing of the accumulators, the near planes and the colour head's per-ray SH inputs (FieldArgs::sh_ray).
+__global__ __launch_bounds__(256) void frame_prep_single_kernel(int64_t n_rays, const float *__restrict__ rays_d,
+                                                                float near_plane, float *__restrict__ near_planes,
+                                                                float *__restrict__ sh_ray, float *__restrict__ rgb,
+                                                                float *__restrict__ opacity, float *__restrict__ depth)
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
+    sh_ray_store(rays_d, r, sh_ray);
     near_planes[r] = near_plane;
     rgb[3 * r] = 0.0f; rgb[3 * r + 1] = 0.0f; rgb[3 * r + 2] = 0.0f;
     opacity[r] = 0.0f;
@@ -663,13 +667,15 @@ struct ImageState {
     int32_t *kept;       // kept samples of the ray so far
 };
 
-__global__ __launch_bounds__(256) void image_prep_kernel(int64_t n_rays, ImageState st, float *__restrict__ rgb,
+__global__ __launch_bounds__(256) void image_prep_kernel(int64_t n_rays, ImageState st, const float *__restrict__ rays_d,
+                                                         float *__restrict__ sh_ray, float *__restrict__ rgb,
                                                          float *__restrict__ opacity, float *__restrict__ depth)
 {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rays) return;
     st.cursor[r] = 0; st.acc_all[r] = 0.0f; st.acc_kept[r] = 0.0f; st.kept[r] = 0;
     if (rgb) {
+        sh_ray_store(rays_d, r, sh_ray);            // the colour head's per-ray SH inputs (FieldArgs::sh_ray)
         rgb[3 * r] = 0.0f; rgb[3 * r + 1] = 0.0f; rgb[3 * r + 2] = 0.0f;
         opacity[r] = 0.0f;
         depth[r] = 0.0f;
@@ -945,6 +951,7 @@ struct FrameWorkspace {
     float *ts_ray;                  // per-ray time of a multi-frame call
     float *t0, *t1; int32_t *ridx; float *sigma, *rgbs;
     uint8_t *accel;                 // brick distance field when the caller did not bring one
+    float *sh_ray;                  // [n, 3] colour-head SH inputs per ray (FieldArgs::sh_ray)
     size_t bytes;
 };
 
@@ -987,6 +994,7 @@ static FrameWorkspace carve(void *base, int64_t n, int m, int64_t cap, int max_i
     w.rgbs = c.take<float>((size_t)cap * 3);
     const int64_t nbk = (res + kBrick - 1) / kBrick;
     w.accel = c.take<uint8_t>((size_t)(2 * m * nbk * nbk * nbk));       // brick field + scratch (no accel from the caller)
+    w.sh_ray = c.take<float>((size_t)n * 3);
     w.bytes = c.off;
     return w;
 }
@@ -1125,10 +1133,11 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
     const dim3 blk(256), grd((unsigned)((n_rays + 255) / 256));
 
     if (n_grids == 1)
-        hipLaunchKernelGGL(frame_prep_single_kernel, grd, blk, 0, stream, n_rays, near_plane, W.near, rgb, opacity, depth);
+        hipLaunchKernelGGL(frame_prep_single_kernel, grd, blk, 0, stream, n_rays, rays_d, near_plane, W.near, W.sh_ray, rgb,
+                           opacity, depth);
     else
         hipLaunchKernelGGL(frame_prep_kernel, grd, blk, 0, stream, n_rays, rays_o, rays_d, (int)n_grids, aabbs, near_plane,
-                           W.t_sorted, W.t_indices, W.hits, W.near, rgb, opacity, depth);
+                           W.t_sorted, W.t_indices, W.hits, W.near, W.sh_ray, rgb, opacity, depth);
     if (frame_times)
         hipLaunchKernelGGL(frame_times_kernel, grd, blk, 0, stream, n_rays, (int)rays_per_frame, frame_times, W.ts_ray);
     const int nb = (res + kBrick - 1) / kBrick;
@@ -1206,6 +1215,7 @@ static int render_frames_impl(const ced_field_desc *field, int n_frames, int64_t
         F.n = cap;                          // host-side upper bound; the kernel reads the exact count from the plan
         F.n_dev = &plan->total_samples;
         F.rays_o = rays_o; F.rays_d = rays_d; F.ray_idx32 = W.ridx;
+        F.sh_ray = g_frame_sh_per_ray ? W.sh_ray : nullptr;
         F.t0 = W.t0; F.t1 = W.t1;
         F.timestamps = frame_times ? W.ts_ray : timestamps;
         F.rays_mode = 1; F.t_per_ray = (frame_times || t_per_ray) ? 1 : 0; F.want_rgb = 1;
@@ -1289,6 +1299,7 @@ struct ImageWorkspace {
     int32_t *packed, *alive_a, *alive_b;
     IterPlan *plans;
     float *t0, *t1; int32_t *ridx; float *sigma, *rgbs, *w, *tr, *al; int32_t *rank;
+    float *sh_ray;                  // [n, 3] colour-head SH inputs per ray (FieldArgs::sh_ray)
     size_t bytes;
 };
 
@@ -1314,6 +1325,7 @@ static ImageWorkspace carve_image(void *base, int64_t n, int64_t cap)
     w.tr = c.take<float>((size_t)cap);
     w.al = c.take<float>((size_t)cap);
     w.rank = c.take<int32_t>((size_t)cap);
+    w.sh_ray = c.take<float>((size_t)n * 3);
     w.bytes = c.off;
     return w;
 }
@@ -1348,7 +1360,7 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
     CED_REQUIRE((int64_t)W.bytes <= workspace_bytes, "%s: workspace too small (%lld < %lld bytes)", who,
                 (long long)workspace_bytes, (long long)W.bytes);
     const dim3 blk(256), grd((unsigned)((n_rays + 255) / 256));
-    hipLaunchKernelGGL(image_prep_kernel, grd, blk, 0, stream, n_rays, W.st, rgb, opacity, depth);
+    hipLaunchKernelGGL(image_prep_kernel, grd, blk, 0, stream, n_rays, W.st, rays_d, W.sh_ray, rgb, opacity, depth);
     volatile long long *pub = (volatile long long *)host_stats;
     std::vector<long long> plan_seq((size_t)kImageMaxIters + 1);  // publication of plan k
     plan_seq[0] = ++g_publish_seq;
@@ -1382,6 +1394,7 @@ static int render_image_impl(const ced_field_desc *field, int64_t n_rays, const 
         F.n_dev = &plan->total_samples;
         F.base_dev = &plan->sample_base;
         F.rays_o = rays_o; F.rays_d = rays_d; F.ray_idx32 = W.ridx;
+        F.sh_ray = (full && g_frame_sh_per_ray) ? W.sh_ray : nullptr;
         F.t0 = W.t0; F.t1 = W.t1;
         F.timestamps = timestamps;
         F.rays_mode = 1; F.t_per_ray = t_per_ray ? 1 : 0; F.want_rgb = full ? 1 : 0;

@@ -76,7 +76,7 @@ int ced_version(void);
 const char *ced_last_error_string(void);
 
 /* Process-wide options; results are identical for every setting (launch properties that callers vary per call, such
- * as the workgroup count of a field launch, are descriptor fields instead).  Three keys; any other key returns -1:
+ * as the workgroup count of a field launch, are descriptor fields instead).  Four keys; any other key returns -1:
  * "field_spread_tiles": 1 deals the sample tiles of a launch across all CUs in groups of four before any CU takes
  * more (shorter last round, lower frame latency); 2 (default) does the same inside each XCD, the eight XCDs taking eight
  * contiguous parts of the sample stream (one L2 per table line instead of up to eight); 0 = contiguous tiles per workgroup;
@@ -84,7 +84,11 @@ const char *ced_last_error_string(void);
  * marching pass over the rays it could not rule out: 1 / 0, -1 (default) = when there are several grid levels;
  * "hash_grad_blocks": cap on the workgroups per level of the hash-table gradient (ced_hash_encode_backward[_temporal]),
  * 0 (default) = no cap, one per 64 samples; a small cap lets the atomics run beside compute-bound kernels of another
- * stream.
+ * stream;
+ * "frame_sh_per_ray": 1 (default) = the frame renderers (ced_render_image_test / _frames_test / _sharded,
+ * ced_render_image) hand the field kernel the colour head's direction inputs computed once per ray in their set-up launch;
+ * 0 = the field kernel computes them per sample from rays_d, as it does for ced_field_forward_rays (the same operations:
+ * the tests compare the two).
  * (Round 3's "march_sm" -- that pass on persistent waves with lane-level ray fetch -- was bit-exact and 3x slower; removed
  * in round 4, HISTORY 4.2 keeps the measurements.) */
 int ced_set_option(const char *key, int value);
@@ -879,7 +883,10 @@ typedef struct ced_frame_trace {
 /* Rate of the device wall clock the field_stamps are taken on (hipDeviceAttributeWallClockRate), in kHz; < 0 on error. */
 int64_t ced_wall_clock_khz(void);
 
-/* Device bytes ced_render_image_test needs in `workspace` (negative on bad arguments). */
+/* Device bytes ced_render_image_test needs in `workspace` (negative on bad arguments).  Besides the per-ray marching
+ * state and the per-sample arrays of one iteration this holds 3 floats per ray (each array rounded up to 256 bytes): the
+ * colour head's direction inputs, computed once per ray in the call's set-up launch and read by the field kernel.  The
+ * same holds for the workspaces of ced_render_frames_test(_sharded) and ced_render_image below: always ask the entry. */
 int64_t ced_render_image_test_workspace_bytes(int64_t n_rays, int32_t n_grids, int32_t res, float cone_angle,
                                               int32_t max_samples);
 
