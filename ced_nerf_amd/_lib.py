@@ -13,7 +13,7 @@ from typing import List, Optional
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("CED_NERF_LIB", os.path.join(_PKG, "libcednerf_hip.so"))
-SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "hash.hip", "field_half.hip", "field_mixed.hip", "field_move.hip", "field_jacobian.hip", "field_density_gradient.hip", "field_time_max.hip", "field_level_set.hip", "surface.hip", "frame.hip", "occgrid.hip",
+SOURCES = ["runtime.hip", "march.hip", "composite.hip", "field.hip", "hash.hip", "field_half.hip", "field_mixed.hip", "field_move.hip", "field_jacobian.hip", "field_density_gradient.hip", "field_time_max.hip", "field_level_set.hip", "surface.hip", "frame_loop.hip", "frame.hip", "image.hip", "march_all.hip", "occgrid.hip",
            "raygen.hip", "wgrad.hip", "pixels.hip", "accel.hip", "linear.hip", "mlp.hip", "train_glue.hip", "losses.hip",
            "metrics.hip", "train_batch.hip", "importance.hip", "bake.hip", "mesh.hip"]
 MLP_F32, MLP_F16X2, MLP_F16, MLP_F32_HEAD16X2 = 0, 1, 2, 3          # ced_field_desc.mlp_precision

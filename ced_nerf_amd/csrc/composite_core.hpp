@@ -1,5 +1,5 @@
 // The front-to-back compositing recurrence, once, for every kernel that walks a ray's samples: composite.hip (the
-// nerfacc-shaped entries), frame.hip (frame renderer, eval renderer) and losses.hip (the fused distortion loss).
+// nerfacc-shaped entries), frame.hip (frame renderer), image.hip (eval renderer) and losses.hip (the fused distortion loss).
 // Per sample, in this order and each a single float32 operation (-ffp-contract=off; det_expf is ced_common.hpp's):
 //   sd = sigma * (t1 - t0);  a = 1 - exp(-sd);  T = exp(-acc) [* the ray's prefix];  w = T * a;
 //   c += w * rgb;  op += w;  dp += w * ((t0 + t1) / 2);  acc += sd.

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(THREADS) void field_kernel(FieldArgs A)
         const int64_t nd = *A.n_dev;
         n_eff = nd < n_eff ? nd : n_eff;
     }
-    // the call's window of persistent per-sample arrays (render_image, frame.hip): ray_idx / t0 / t1 / sigma / rgb
+    // the call's window of persistent per-sample arrays (render_image, image.hip): ray_idx / t0 / t1 / sigma / rgb
     // entry s of the call is entry sbase + s of the arrays.  (Kept as an index offset: adding it to the pointers of
     // the by-value argument block would make the compiler keep the whole block in scratch.)
     const int64_t sbase = A.base_dev ? *A.base_dev : 0;

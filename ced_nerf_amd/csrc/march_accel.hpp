@@ -2,7 +2,7 @@
 // (look_ahead, load_batch), the samples of one occupied cell (emit_cell), on the segment decoder, slab test and skip
 // marches of march_core.hpp.  Two compositions of these pieces emit the per-ray sample sets of nerfacc.traverse_grids
 // (restated independently by the CPU oracle; call site cednerf/utils.py:241-264):
-//   traverse_ray_frame  the walker of the frame renderer and the one-shot march (frame.hip) and of the host twin
+//   traverse_ray_frame  the walker of the frame renderer (frame.hip), the one-shot march (march_all.hip) and the host twin
 //                       (accel.hip): skips applied lazily, and -- with distance fields -- empty space at O(1) per stretch;
 //   traverse_ray        ced_traverse_grids' (march.hip): no distance fields, skips marched eagerly, the termination
 //                       plane of every ray.  It is a special case of the former in what it computes (checked bit for

@@ -1940,6 +1940,79 @@ def test_frame_renderer_edge_cases(oracle):
         render_image_test(8, f, est, Rays(torch.from_numpy(o), torch.from_numpy(d)), timestamps=ts)
 
 
+def _simulate_frame_schedule(ref, n_padding, max_samples):
+    """The frame loop's schedule on a float64 march reference (march64.march_reference), counts only: every ray's samples
+    are its occupied lattice intervals, an iteration gives every alive ray its next N_samples = clamp(N_rays // N_alive,
+    1, 64) of them, and a ray stays alive while it fills its budget (the opacity is not simulated: with early_stop_eps =
+    0 it ends only a ray whose float32 opacity rounds past 1, which can only shorten a later iteration's list).
+    n_padding more rays march nothing.  Returns ([(alive, N_samples)], pieces): pieces = the (ray, iteration) pairs whose
+    samples of that iteration form more than four runs of consecutive lattice intervals."""
+    occ = [np.flatnonzero(o) for o in ref["occupied"]]
+    n_rays = len(occ) + n_padding
+    pos = np.zeros(len(occ), np.int64)
+    alive = np.ones(len(occ), bool)
+    n_alive, used, schedule, pieces = n_rays, 0, [], 0
+    while used < max_samples and n_alive > 0:
+        n_samples = max(min(n_rays // n_alive, 64), 1)
+        used += n_samples
+        schedule.append((n_alive, n_samples))
+        for r in np.flatnonzero(alive):
+            piece = occ[r][pos[r]:pos[r] + n_samples]
+            pos[r] += piece.size
+            alive[r] = piece.size == n_samples
+            pieces += int(piece.size > 0 and 1 + int((np.diff(piece) != 1).sum()) > 4)
+        n_alive = int(alive.sum())
+    return schedule, pieces
+
+
+def test_frame_loop_walks_again_when_a_piece_has_more_runs_than_fit(oracle):
+    """march_frame_kernel remembers a ray's samples of one iteration as up to four runs; a piece with more walks a second
+    time, storing directly (pack_ray_samples).  Frames of real scenes never get there -- N_samples stays small while most
+    rays are alive -- so: the 257 rays of march64's speckle16_L1 (single occupied cells, 30 % fill) plus 63 x 257 rays
+    that miss the box.  After the first iteration (N_samples = 1) only 165 of 16448 rays are alive and N_samples jumps
+    to 64.  The float64 simulation of the schedule gives (alive, N_samples) = (16448, 1), (165, 64), (68, 64) and 70 + 2
+    pieces with more than four runs; the 248 undecided midpoints of the case cannot bring 72 below the 10 asserted.
+    Pixels and the sample total against the oracle's loop, bit for bit, in both forms of the first iteration."""
+    import march64 as M
+    from ced_nerf_amd import _lib, ops
+    from ced_nerf_amd.model import DNGPradianceField
+    from ced_nerf_amd.nerfacc_api import OccGridEstimator
+    from ced_nerf_amd.utils import Rays, render_image_test
+    c = M.case("speckle16_L1")
+    n_pad = 63 * M.N_RAYS
+    schedule, pieces = _simulate_frame_schedule(c["ref"], n_pad, 1024)
+    print("simulated schedule", schedule, "pieces with more than four runs", pieces)
+    assert pieces >= 10 and 64 in [s for _, s in schedule], (schedule, pieces)
+    o = np.concatenate([c["o"], np.tile(c["o"][M.MISS], (n_pad, 1))])
+    d = np.concatenate([c["d"], np.tile(c["d"][M.MISS], (n_pad, 1))])
+    assert o.shape == (16448, 3)
+    sc = _scene("dnerf", 4, 4, "trained", log2_hashmap_size=14)            # a toy field on [-1.5, 1.5]^3: contains the ROI
+    kw = dict(near_plane=0.0, far_plane=1e10, render_step_size=c["step"], cone_angle=c["cone_angle"], alpha_thre=0.0,
+              early_stop_eps=0.0)
+    bkgd = np.array([0.25, 0.5, 0.75], np.float32)
+    oest = oracle.OracleEstimator(M.ROI, 16, 1, c["binaries"])
+    w = oracle.render_image_test(1024, oracle.OracleField(sc["params"]), oest, o, d, timestamps=sc["timestamps"],
+                                 render_bkgd=bkgd, **kw)
+    f = DNGPradianceField.from_params(sc["params"], DEV).eval()
+    est = OccGridEstimator(M.ROI, 16, 1).to(DEV)
+    est.set_binaries(T(c["binaries"]))
+    L = _lib.lib()
+    try:
+        for two in (0, 1):
+            assert L.ced_set_option(b"march_two_pass", two) == 0
+            tracer = ops.FrameTracer(capacity=1100, with_events=False)
+            g = render_image_test(1024, f, est, Rays(T(o), T(d)), timestamps=T(sc["timestamps"]), render_bkgd=T(bkgd),
+                                  tracer=tracer, **kw)
+            torch.cuda.synchronize()
+            print("march_two_pass", two, "iterations", tracer.iterations(), "total", g[3], "oracle", w[3])
+            assert g[3] == w[3], (two, g[3], w[3])
+            assert 64 in [it["n_samples"] for it in tracer.iterations()], (two, tracer.iterations())
+            for i, nm in enumerate(("rgb", "opacity", "depth")):
+                assert_bitexact(N(g[i]), w[i], f"{nm} (march_two_pass={two})")
+    finally:
+        L.ced_set_option(b"march_two_pass", -1)
+
+
 def _two_rank_bench(extra):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 """Where the marching kernel of the frame renderer spends its waves (diagnostic build, -DCED_MARCH_DIAG):
-   SRCS=frame tools/build_variant.sh diag -DCED_MARCH_DIAG
+   SRCS=frame tools/build_variant.sh diag -DCED_MARCH_DIAG        (frame.hip: march_frame_kernel + csrc/march_diag.hpp)
    CED_NERF_LIB=build/variants/libcednerf_hip.diag.so python tools/march_diag.py [dnerf|hypernerf|dynerf]
 Per phase of the walk: passes of a wave through it, lanes active in those passes, cycles until the wave's next tick.
 First the first iteration alone (max_samples = min_samples), then the whole frame."""
