@@ -97,6 +97,9 @@ PROTOTYPES = {
     "ced_host_count_steps": (_i32, [C.POINTER(C.c_float), _f, _f, _i32, C.POINTER(C.c_float)]),
     "ced_host_march_frame": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _f, _f, _f, _i32, _vp, _vp, _vp, _vp, _i32, _i32,
                                        _i32, _vp, _vp, _vp, _vp]),
+    "ced_host_march_frame_hinted": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _f, _f, _f, _i32, _vp, _vp, _vp, _vp, _i32,
+                                              _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ced_host_ray_group_clear": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f, _f, _vp]),
     "ced_hash_encode": (C.c_int, [C.POINTER(HashDesc), _i64, _vp, _vp, _vp, _vp]),
     "ced_hash_encode_backward": (C.c_int, [C.POINTER(HashDesc), _i64, _vp, _vp, _vp, _vp, _i32, _vp]),
     "ced_hash_encode_backward_temporal": (C.c_int, [C.POINTER(HashDesc), _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -307,12 +307,13 @@ extern "C" int32_t ced_host_count_steps(float *x, float d, float tau, int32_t kc
     return ced::count_steps(*x, d, tau, kcap, *prev);
 }
 
-extern "C" int ced_host_march_frame(int64_t n_rays, const float *rays_o, const float *rays_d, const uint8_t *binaries,
-                                    int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes,
-                                    float far_plane, float step_size, float cone_angle, int32_t limit,
-                                    const float *t_sorted, const int64_t *t_indices, const uint8_t *hits,
-                                    const uint8_t *accel_host, int32_t accel_mode, int32_t use_lattice, int32_t walk,
-                                    int32_t *counts, float *t_starts, float *t_ends, float *t_term)
+// t_hint: per ray, or NULL (no hints)
+static int host_march_frame(int64_t n_rays, const float *rays_o, const float *rays_d, const uint8_t *binaries,
+                            int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes,
+                            float far_plane, float step_size, float cone_angle, int32_t limit,
+                            const float *t_sorted, const int64_t *t_indices, const uint8_t *hits,
+                            const uint8_t *accel_host, int32_t accel_mode, int32_t use_lattice, int32_t walk,
+                            const float *t_hint, int32_t *counts, float *t_starts, float *t_ends, float *t_term)
 {
     CED_REQUIRE(n_rays >= 0 && n_grids >= 1 && res >= 1 && limit >= 1, "host_march_frame: bad sizes");
     CED_REQUIRE(rays_o && rays_d && binaries && aabbs && near_planes && t_sorted && t_indices && hits && counts &&
@@ -339,15 +340,77 @@ extern "C" int ced_host_march_frame(int64_t n_rays, const float *rays_o, const f
         // the ray/box interval; walk 1 traces first in the looking-loop form, walk 2 traces first, walk 0 does not.
         // walk 3: traverse_ray, what ced_traverse_grids' kernel runs (LOOK = 8, every termination plane exact).
         const float near = near_planes[r];
+        const float hint = t_hint ? t_hint[r] : -__builtin_inff();
         float &tt = t_term[r];
         if (walk == 3)
             counts[r] = ced::traverse_ray(G, o, d, near, far_plane, ts, ti, hr, emit, tt);
         else if (n_grids == 1)
-            counts[r] = walk == 1 ? ced::traverse_ray_frame<ced::kFrameLook, true, true>(G, S, true, o, d, near, far_plane, ts, ti, hr, emit, tt)
-                                  : ced::traverse_ray_frame<ced::kFrameLook, true, false>(G, S, walk != 0, o, d, near, far_plane, ts, ti, hr, emit, tt);
+            counts[r] = walk == 1 ? ced::traverse_ray_frame<ced::kFrameLook, true, true>(G, S, true, o, d, near, far_plane, ts, ti, hr, emit, tt, hint)
+                                  : ced::traverse_ray_frame<ced::kFrameLook, true, false>(G, S, walk != 0, o, d, near, far_plane, ts, ti, hr, emit, tt, hint);
         else
-            counts[r] = walk == 1 ? ced::traverse_ray_frame<ced::kFrameLook, false, true>(G, S, true, o, d, near, far_plane, ts, ti, hr, emit, tt)
-                                  : ced::traverse_ray_frame<ced::kFrameLook, false, false>(G, S, walk != 0, o, d, near, far_plane, ts, ti, hr, emit, tt);
+            counts[r] = walk == 1 ? ced::traverse_ray_frame<ced::kFrameLook, false, true>(G, S, true, o, d, near, far_plane, ts, ti, hr, emit, tt, hint)
+                                  : ced::traverse_ray_frame<ced::kFrameLook, false, false>(G, S, walk != 0, o, d, near, far_plane, ts, ti, hr, emit, tt, hint);
+    }
+    return CED_OK;
+}
+
+extern "C" int ced_host_march_frame(int64_t n_rays, const float *rays_o, const float *rays_d, const uint8_t *binaries,
+                                    int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes,
+                                    float far_plane, float step_size, float cone_angle, int32_t limit,
+                                    const float *t_sorted, const int64_t *t_indices, const uint8_t *hits,
+                                    const uint8_t *accel_host, int32_t accel_mode, int32_t use_lattice, int32_t walk,
+                                    int32_t *counts, float *t_starts, float *t_ends, float *t_term)
+{
+    return host_march_frame(n_rays, rays_o, rays_d, binaries, n_grids, res, aabbs, near_planes, far_plane, step_size, cone_angle,
+                            limit, t_sorted, t_indices, hits, accel_host, accel_mode, use_lattice, walk, nullptr, counts, t_starts,
+                            t_ends, t_term);
+}
+
+extern "C" int ced_host_march_frame_hinted(int64_t n_rays, const float *rays_o, const float *rays_d, const uint8_t *binaries,
+                                           int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes,
+                                           float far_plane, float step_size, float cone_angle, int32_t limit,
+                                           const float *t_sorted, const int64_t *t_indices, const uint8_t *hits,
+                                           const uint8_t *accel_host, int32_t accel_mode, int32_t use_lattice, int32_t walk,
+                                           const float *t_hint, int32_t *counts, float *t_starts, float *t_ends,
+                                           float *t_term)
+{
+    CED_REQUIRE(t_hint != nullptr, "host_march_frame_hinted: null t_hint");
+    return host_march_frame(n_rays, rays_o, rays_d, binaries, n_grids, res, aabbs, near_planes, far_plane, step_size, cone_angle,
+                            limit, t_sorted, t_indices, hits, accel_host, accel_mode, use_lattice, walk, t_hint, counts, t_starts,
+                            t_ends, t_term);
+}
+
+extern "C" int ced_host_ray_group_clear(int32_t n_frames, int64_t rays_per_frame, const int32_t *local_rays,
+                                        const float *rays_o, const float *rays_d, int32_t n_grids, int32_t res,
+                                        const float *aabbs, const uint8_t *accel_host, int32_t accel_mode, float near_plane,
+                                        float far_plane, float *t_clear)
+{
+    CED_REQUIRE(n_frames >= 1 && rays_per_frame >= 0 && n_grids >= 1 && n_grids <= 8 && res >= 1, "host_ray_group_clear: bad sizes");
+    CED_REQUIRE(rays_o && rays_d && aabbs && accel_host && t_clear, "host_ray_group_clear: null pointer");
+    CED_REQUIRE(accel_mode == 1 || accel_mode == 2, "host_ray_group_clear: accel_mode 1 (bricks), 2 (cells)");
+    const ced::AccelSpec S = ced::accel_view(accel_host, n_grids, res, accel_mode == 2);
+    const int64_t gpf = (rays_per_frame + ced::kGroupRays - 1) / ced::kGroupRays;
+    const float inf = __builtin_inff();
+    for (int64_t G = 0; G < (int64_t)n_frames * gpf; ++G) {
+        const int64_t f = G / gpf, k0 = (G % gpf) * ced::kGroupRays;
+        const int64_t count = local_rays ? local_rays[f] : rays_per_frame;
+        if (k0 >= count) { t_clear[G] = inf; continue; }             // no member: nobody reads it
+        const int members = (int)((count - k0 < ced::kGroupRays) ? count - k0 : ced::kGroupRays);
+        const int64_t rc = f * rays_per_frame + k0 + ced::group_reference(members);
+        ced::RayGroupBounds B;
+        for (int a = 0; a < 3; ++a) { B.oc[a] = rays_o[3 * rc + a]; B.dc[a] = rays_d[3 * rc + a]; }
+        float v[6 + 2 * ced::kGroupMaxLevels], lim[2 * ced::kGroupMaxLevels];
+        for (float &x : v) x = -inf;
+        bool bad = false;
+        for (int64_t r = f * rays_per_frame + k0; r < f * rays_per_frame + k0 + members; ++r) {
+            const float o[3] = { rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2] };
+            const float d[3] = { rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2] };
+            ced::group_member(o, d, B.oc, B.dc, n_grids, aabbs, v, bad);
+        }
+        for (int a = 0; a < 3; ++a) { B.dev_o[a] = v[a]; B.dev_d[a] = v[3 + a]; }
+        for (int l = 0; l < n_grids; ++l) { lim[2 * l] = -v[6 + 2 * l]; lim[2 * l + 1] = v[7 + 2 * l]; }
+        if (bad) B.dev_o[0] = inf;                                   // group_clear then claims nothing
+        t_clear[G] = ced::group_clear(S, n_grids, res, aabbs, B, lim, near_plane, far_plane);
     }
     return CED_OK;
 }

@@ -102,7 +102,109 @@ struct MarchArgs {
     int32_t *ray_idx;              // ray of every sample
     int32_t *packed;               // [n_rays, 2] (first sample, count) of the ray in this iteration
     int32_t *cand;                 // first iteration in two passes: the rays march_cull_kernel could not rule out
+    const float *t_clear;          // first iteration: [n_frames, groups_per_frame] group clearances (march_accel.hpp)
+    int groups_per_frame;
 };
+
+// Group clearance, phase A: one wave per group of kGroupRays consecutive rays of a frame (its last group may be
+// partial; the padding rays of a sharded frame, local_rays, are no members).  Every lane folds its ray against the
+// group's reference ray (group_member) into NV maxima -- 6 deviations and 2 limits per level, padded to a power of
+// two -- and the wave reduces them with a halving butterfly: at the step with lane distance 2^s a lane keeps one half of
+// its values and trades the other half with its partner, so the first log2(NV) steps take NV - 1 shuffles in all
+// instead of NV each, and lane j < NV ends with one value (`mine`), which it stores itself.
+constexpr int kGroupThreads = 256;
+static_assert(kGroupMaxLevels == kMaxGrids, "group_member's per-level limits");
+static_assert(kSlotAlign % kGroupRays == 0 && kGroupRays == 64, "a wave's slots of the first iteration are one group");
+template <int NV>
+__global__ __launch_bounds__(kGroupThreads) void ray_group_bounds_kernel(
+    int n_frames, int rays_per_frame, int groups_per_frame, const int32_t *__restrict__ local_rays,
+    const float *__restrict__ rays_o, const float *__restrict__ rays_d, int m, const float *__restrict__ aabbs,
+    RayGroupBounds *__restrict__ bounds, float *__restrict__ limits)
+{
+    static_assert(NV == 8 || NV == 16 || NV == 32, "6 + 2 m values, padded");
+    const int lane = threadIdx.x & 63;
+    const int64_t n_groups = (int64_t)n_frames * groups_per_frame;
+    const float inf = __builtin_inff();
+    int mine = 0;                                            // the value lane j < NV ends up with
+#pragma unroll
+    for (int s = 0; (NV >> s) > 1; ++s) mine += ((lane >> s) & 1) * (NV >> (s + 1));
+    for (int64_t g = (int64_t)blockIdx.x * (kGroupThreads / 64) + (threadIdx.x >> 6); g < n_groups;
+         g += (int64_t)gridDim.x * (kGroupThreads / 64)) {
+        const int f = (int)(g / groups_per_frame);
+        const int k0 = (int)(g % groups_per_frame) * kGroupRays;
+        const int count = local_rays ? local_rays[f] : rays_per_frame;
+        const int members = count - k0 < kGroupRays ? count - k0 : kGroupRays;
+        if (members <= 0) continue;                          // no member (the whole wave): phase B writes +inf
+        const int64_t r = (int64_t)f * rays_per_frame + k0 + (lane < members ? lane : 0);
+        const float o[3] = { rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2] };
+        const float d[3] = { rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2] };
+        const int ref = group_reference(members);
+        const float oc[3] = { __shfl(o[0], ref, 64), __shfl(o[1], ref, 64), __shfl(o[2], ref, 64) };
+        const float dc[3] = { __shfl(d[0], ref, 64), __shfl(d[1], ref, 64), __shfl(d[2], ref, 64) };
+        float v[6 + 2 * kMaxGrids > NV ? 6 + 2 * kMaxGrids : NV];
+#pragma unroll
+        for (float &x : v) x = -inf;
+        bool bad = false;
+        if (lane < members) group_member(o, d, oc, dc, m, aabbs, v, bad);
+#pragma unroll
+        for (int s = 0; (NV >> s) > 1; ++s) {
+            const int half = NV >> (s + 1);
+            const bool up = (lane >> s) & 1;
+#pragma unroll
+            for (int k = 0; k < half; ++k) {
+                const float keep = up ? v[k + half] : v[k], send = up ? v[k] : v[k + half];
+                v[k] = fmaxf(keep, __shfl_xor(send, 1 << s, 64));
+            }
+        }
+#pragma unroll
+        for (int off = NV; off < 64; off <<= 1) v[0] = fmaxf(v[0], __shfl_xor(v[0], off, 64));
+        bad = __any(bad);
+        float *B = reinterpret_cast<float *>(bounds + g);    // oc[3], dc[3], dev_o[3], dev_d[3]
+        if (lane == ref) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { B[a] = oc[a]; B[3 + a] = dc[a]; }
+        }
+        if (lane < NV) {
+            if (mine < 6) B[6 + mine] = (bad && mine == 0) ? inf : v[0];          // bad: group_clear then claims nothing
+            else if (mine < 6 + 2 * m) limits[g * 2 * m + (mine - 6)] = (mine & 1) ? v[0] : -v[0];
+        }
+    }
+}
+
+// Phase B: one LANE per group traces the group's cone (group_clear) -- 64 times fewer wave-instructions than the per-ray
+// traces of the groups it clears.  A group without members gets +inf (nobody reads it).
+__global__ __launch_bounds__(kGroupThreads) void ray_group_clear_kernel(
+    int n_frames, int rays_per_frame, int groups_per_frame, const int32_t *__restrict__ local_rays, AccelSpec S, int m, int res,
+    const float *__restrict__ aabbs, const RayGroupBounds *__restrict__ bounds, const float *__restrict__ limits,
+    float near_plane, float far_plane, float *__restrict__ t_clear)
+{
+    const int64_t g = (int64_t)blockIdx.x * kGroupThreads + threadIdx.x;
+    if (g >= (int64_t)n_frames * groups_per_frame) return;
+    const int count = local_rays ? local_rays[g / groups_per_frame] : rays_per_frame;
+    const bool empty = (int)(g % groups_per_frame) * kGroupRays >= count;
+    const RayGroupBounds B = bounds[g];
+    t_clear[g] = empty ? __builtin_inff() : group_clear(S, m, res, aabbs, B, limits + g * 2 * m, near_plane, far_plane);
+}
+
+// First iteration, the groups of the workgroup whose first slot is s0 (kWaves groups: a frame's slots start at a
+// multiple of kSlotAlign, so a wave's 64 slots are one group): the clearance of wave `wave`'s own group, and whether
+// every group of the workgroup is cleared to the far plane -- from wave-uniform loads, so the answer is the same in
+// every thread of the workgroup.
+template <int kWaves>
+__device__ __forceinline__ bool workgroup_clearance(const MarchArgs &A, const IterPlan &P, int f, int64_t s0, int wave, float &t_own)
+{
+    const int idx0 = (int)(s0 - P.slot_base[f]);
+    const float *row = A.t_clear + (int64_t)f * A.groups_per_frame + (idx0 >> 6);
+    bool all_clear = true;
+    t_own = 0.0f;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        const float tc = idx0 + 64 * w < P.count[f] ? row[w] : __builtin_inff();       // no member in this wave's slots
+        all_clear = all_clear && tc == __builtin_inff();
+        t_own = w == wave ? tc : t_own;
+    }
+    return all_clear;
+}
 
 // First iteration of a frame, pass one of two.  Nine rays in ten see nothing (the scene fills a few percent of the
 // grid), and what decides that is only the sphere trace through the distance field: this pass runs the trace of every
@@ -125,8 +227,20 @@ __global__ __launch_bounds__(kCullThreads) void march_cull_kernel(MarchArgs A, I
         const int64_t idx = s0 + threadIdx.x - P.slot_base[f];
         const bool active = idx < P.count[f];
         const int64_t r = (int64_t)f * A.rays_per_frame + (active ? idx : 0);
+        // group clearance: a workgroup of cleared groups is done before it loads a ray (the same decision in all its
+        // threads: no barrier below is skipped by a part of it); a cleared group among others takes no trace
+        float t_hint = 0.0f;
+        if (A.t_clear) {
+            const bool all_clear = workgroup_clearance<kCullThreads / 64>(A, P, f, s0, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), t_hint);
+            if (all_clear) {
+                if (active) { A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0; }
+                continue;
+            }
+        }
         bool cand = false;
-        if (active) {
+        if (active && t_hint == __builtin_inff()) {
+            A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0;
+        } else if (active) {
             float o[3], d[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) { o[a] = A.rays_o[3 * r + a]; d[a] = A.rays_d[3 * r + a]; }
@@ -143,7 +257,7 @@ __global__ __launch_bounds__(kCullThreads) void march_cull_kernel(MarchArgs A, I
                 const float t0 = fmaxf(seg_a, near), t1 = fminf(seg_b, A.far_plane);
                 if (t0 >= t1) continue;
                 float t_stop, cells;
-                cand = !coarse_advance(A.accel, lvl, res, A.grid.aabbs + 6 * lvl, o, d, t0, t1, t_stop, cells);
+                cand = !coarse_advance(A.accel, lvl, res, A.grid.aabbs + 6 * lvl, o, d, t0, t1, t_stop, cells, t_hint);
             }
             if (!cand) { A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0; }
         }
@@ -173,10 +287,14 @@ __global__ __launch_bounds__(kMarchThreads, (SINGLE && !CAND) ? 4 : 3) void marc
         int f = 0;
         bool active;
         int64_t r = 0;
+        float t_hint = 0.0f;                                 // FIRST: the group clearance of the lane's ray
         if constexpr (CAND) {
             const int64_t slot = s0 + wave * kCandLanes + lane;
             active = lane < kCandLanes && slot < total;
-            if (active) { r = A.cand[slot]; f = (int)(r / A.rays_per_frame); }
+            if (active) {
+                r = A.cand[slot]; f = (int)(r / A.rays_per_frame);
+                if (A.t_clear) t_hint = A.t_clear[(int64_t)f * A.groups_per_frame + (r - (int64_t)f * A.rays_per_frame) / kGroupRays];
+            }
         } else {
             f = frame_of_slot(P, A.n_frames, s0);
             if (f < 0) continue;                             // padding between two frames' slot ranges (whole workgroup)
@@ -184,6 +302,22 @@ __global__ __launch_bounds__(kMarchThreads, (SINGLE && !CAND) ? 4 : 3) void marc
             active = idx < P.count[f];
             const int64_t first = (int64_t)f * A.rays_per_frame;
             r = active ? (A.alive ? (int64_t)A.alive[first + idx] : first + idx) : 0;
+            if constexpr (FIRST) {
+                // group clearance (all rays alive, slot order = ray order): a workgroup of cleared groups is done before
+                // it loads a ray -- the same decision in all its threads, so no barrier below is skipped by a part of
+                // it; a cleared group among others goes through the pack step as inactive lanes do, with no samples
+                if (A.t_clear) {
+                    const bool all_clear = workgroup_clearance<kWaves>(A, P, f, s0, __builtin_amdgcn_readfirstlane(wave), t_hint);
+                    if (all_clear) {
+                        if (active) { A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0; }
+                        continue;
+                    }
+                    if (t_hint == __builtin_inff()) {        // the wave's group is cleared: its lanes are inactive lanes
+                        if (active) { A.packed[2 * r] = 0; A.packed[2 * r + 1] = 0; }
+                        active = false;
+                    }
+                }
+            }
         }
         const int limit = P.limit[f];
         GridSpec grid = A.grid;
@@ -201,7 +335,7 @@ __global__ __launch_bounds__(kMarchThreads, (SINGLE && !CAND) ? 4 : 3) void marc
             const int n = traverse_ray_frame<kFrameLook, SINGLE, FIRST>(
                 grid, A.accel, FIRST, o, d, near, A.far_plane,
                 SINGLE ? nullptr : A.t_sorted + r * 2 * m, SINGLE ? (const uint8_t *)nullptr : A.t_indices + r * 2 * m,
-                SINGLE ? nullptr : A.hits + r * m, emit, t_term);
+                SINGLE ? nullptr : A.hits + r * m, emit, t_term, t_hint);
             if constexpr (decltype(first)::value) A.near_planes[r] = t_term;
             return n;
         };
@@ -284,6 +418,9 @@ struct FrameWorkspace {
     float *t0, *t1; int32_t *ridx; float *sigma, *rgbs;
     uint8_t *accel;                 // brick distance field when the caller did not bring one
     float *sh_ray;                  // [n, 3] colour-head SH inputs per ray (FieldArgs::sh_ray)
+    float *group_clear;             // [groups] clearance per group of kGroupRays rays (march_accel.hpp: group_clear), from
+    RayGroupBounds *group_bounds;   // [groups] the group's reference ray and deviations and
+    float *group_limits;            // [groups, 2 m] its per-level entry / exit limits
     size_t bytes;
 };
 
@@ -305,8 +442,12 @@ static inline int64_t sample_capacity(int n_frames, int64_t rays_per_frame, int 
     return per * n_frames;
 }
 
-static FrameWorkspace carve(void *base, int64_t n, int m, int64_t cap, int max_iters, int res, bool per_ray_times = false)
+static inline int64_t groups_of(int64_t rays_per_frame) { return (rays_per_frame + kGroupRays - 1) / kGroupRays; }
+
+static FrameWorkspace carve(void *base, int n_frames, int64_t rays_per_frame, int m, int64_t cap, int max_iters, int res,
+                            bool per_ray_times = false)
 {
+    const int64_t n = (int64_t)n_frames * rays_per_frame, groups = (int64_t)n_frames * groups_of(rays_per_frame);
     FrameWorkspace w{};
     Carver c{ (char *)base };
     w.t_sorted = c.take<float>((size_t)n * 2 * m);
@@ -327,6 +468,9 @@ static FrameWorkspace carve(void *base, int64_t n, int m, int64_t cap, int max_i
     const int64_t nbk = (res + kBrick - 1) / kBrick;
     w.accel = c.take<uint8_t>((size_t)(2 * m * nbk * nbk * nbk));       // brick field + scratch (no accel from the caller)
     w.sh_ray = c.take<float>((size_t)n * 3);
+    w.group_clear = c.take<float>((size_t)groups);
+    w.group_bounds = c.take<RayGroupBounds>((size_t)groups);
+    w.group_limits = c.take<float>((size_t)groups * 2 * m);
     w.bytes = c.off;
     return w;
 }
@@ -386,7 +530,7 @@ static int render_frames_impl(const FrameCall &c)
     const int64_t cap = sample_capacity(c.n_frames, c.rays_per_frame, min_samples, c.xch ? c.xch->global_rays_per_frame : 0);
     CED_REQUIRE(cap < (1ll << 31) - 64, "%s: too many samples per iteration for 32-bit sample indices", c.who);
     const int max_iters = max_iterations(c.max_samples, min_samples);
-    FrameWorkspace W = carve(c.workspace, n_rays, c.n_grids, cap, max_iters, c.res, c.frame_times != nullptr);
+    FrameWorkspace W = carve(c.workspace, c.n_frames, c.rays_per_frame, c.n_grids, cap, max_iters, c.res, c.frame_times != nullptr);
     CED_REQUIRE((int64_t)W.bytes <= c.workspace_bytes, "%s: workspace too small (%lld < %lld bytes)", c.who,
                 (long long)c.workspace_bytes, (long long)W.bytes);
     if (c.xch) {
@@ -413,6 +557,24 @@ static int render_frames_impl(const FrameCall &c)
         int rc = build_brick_accel(c.binaries, c.n_grids, c.res, W.accel, W.accel + (size_t)c.n_grids * nb * nb * nb, stream);
         if (rc) return rc;
         acc = AccelSpec{ W.accel, nb, nullptr };
+    }
+    // group clearances of the rays passed in, once per call: the first iteration skips the groups that see nothing and
+    // starts the others' traces where their group's ends (march_accel.hpp)
+    // (near plane >= 0 is the bound's precondition: with a negative one nothing is computed and the walks take no hint)
+    const int gpf = (int)groups_of(c.rays_per_frame);
+    const bool clear_groups = acc.bdist && c.near_plane >= 0.0f;
+    if (clear_groups) {
+        const int64_t n_groups = (int64_t)c.n_frames * gpf;
+        const int32_t *local = c.xch ? c.xch->local_rays : nullptr;
+        int64_t agrid = (n_groups + kGroupThreads / 64 - 1) / (kGroupThreads / 64);
+        if (agrid > 16384) agrid = 16384;
+        const auto bounds_kernel = c.n_grids == 1 ? ray_group_bounds_kernel<8>
+                                   : (c.n_grids <= 5 ? ray_group_bounds_kernel<16> : ray_group_bounds_kernel<32>);
+        hipLaunchKernelGGL(bounds_kernel, dim3((unsigned)agrid), dim3(kGroupThreads), 0, stream, c.n_frames,
+                           (int)c.rays_per_frame, gpf, local, c.rays_o, c.rays_d, (int)c.n_grids, c.aabbs, W.group_bounds, W.group_limits);
+        hipLaunchKernelGGL(ray_group_clear_kernel, dim3((unsigned)((n_groups + kGroupThreads - 1) / kGroupThreads)), dim3(kGroupThreads),
+                           0, stream, c.n_frames, (int)c.rays_per_frame, gpf, local, acc, (int)c.n_grids, (int)c.res, c.aabbs,
+                           W.group_bounds, W.group_limits, c.near_plane, c.far_plane, W.group_clear);
     }
     const bool use_lattice = c.cone_angle == 0.0f && c.step_size > 0.0f && c.near_plane >= 0.0f;
     if (use_lattice) build_lattice(c.near_plane, c.step_size, reinterpret_cast<float *>(c.host_stats + kHostLatticeWord));
@@ -442,7 +604,7 @@ static int render_frames_impl(const FrameCall &c)
         MarchArgs M{ c.rays_o, c.rays_d,
                      GridSpec{ c.binaries, c.aabbs, c.n_grids, c.res, c.step_size, c.cone_angle, 0, use_lattice ? W.lattice : nullptr },
                      acc, W.near, c.far_plane, cur_list, c.n_frames, (int)c.rays_per_frame, W.t_sorted, W.t_indices, W.hits,
-                     W.t0, W.t1, W.ridx, W.packed, W.alive_b };
+                     W.t0, W.t1, W.ridx, W.packed, W.alive_b, (it == 0 && clear_groups) ? W.group_clear : nullptr, gpf };
         int64_t mgrid = (slot_bound + kMarchThreads - 1) / kMarchThreads;
         if (mgrid > 8192) mgrid = 8192;
         const dim3 mblk(kMarchThreads);
@@ -554,7 +716,7 @@ extern "C" int64_t ced_render_image_test_workspace_bytes(int64_t n_rays, int32_t
 {
     if (n_rays < 0 || n_grids < 1 || n_grids > ced::kMaxGrids || res < 1 || res > 1024 || max_samples < 0) return -1;
     const int ms = ced::min_samples_of(cone_angle);
-    return (int64_t)ced::carve(nullptr, n_rays, n_grids, n_rays * ms, ced::max_iterations(max_samples, ms), res).bytes;
+    return (int64_t)ced::carve(nullptr, 1, n_rays, n_grids, n_rays * ms, ced::max_iterations(max_samples, ms), res).bytes;
 }
 
 extern "C" int ced_render_image_test(const ced_field_desc *field, int64_t n_rays, const float *rays_o,
@@ -613,9 +775,8 @@ extern "C" int64_t ced_render_frames_test_sharded_workspace_bytes(int32_t n_fram
     if (n_frames < 1 || n_frames > ced::kMaxFrames || rays_per_frame < 0 || global_rays_per_frame < rays_per_frame ||
         n_grids < 1 || n_grids > ced::kMaxGrids || res < 1 || res > 1024 || max_samples < 0)
         return -1;
-    const int64_t n_rays = (int64_t)n_frames * rays_per_frame;
     const int ms = ced::min_samples_of(cone_angle);
-    return (int64_t)ced::carve(nullptr, n_rays, n_grids, ced::sample_capacity(n_frames, rays_per_frame, ms, global_rays_per_frame),
+    return (int64_t)ced::carve(nullptr, n_frames, rays_per_frame, n_grids, ced::sample_capacity(n_frames, rays_per_frame, ms, global_rays_per_frame),
                                ced::max_iterations(max_samples, ms), res, true).bytes;
 }
 

@@ -19,6 +19,10 @@
 //     is computed per axis with integer arithmetic -- bit for bit the state the cell-by-cell walk has when it gets
 //     there.  Every float the emitted samples depend on (t_last lattice, cell boundaries t_trav) is therefore
 //     unchanged; only which empty cells were looked at differs.
+//   * that is also all a GROUP CLEARANCE changes (group_clear: one cone per 64 consecutive rays, traced once per call
+//     through the same fields): a group cleared to the far plane marches nothing, and any other clearance is only where
+//     a segment's first trace starts probing (t_hint) -- the DDA set-up, cells_skipped and the re-entry are still taken
+//     from the segment's start.
 //
 // Contract of traverse_ray_frame (what the frame loop observes): the emitted (t_start, t_end) pairs and their count
 // n <= limit are those of the reference walk; t_term is exact when n == limit (the ray may stay alive and its
@@ -153,8 +157,14 @@ CED_HD int empty_radius(const AccelSpec &S, int lvl, int res, int c0, int c1, in
 // the point at t_stop is within three cells of an occupied one (t_stop == t_from: no skip possible).
 // A probe in cell c with empty radius D: every cell within D-1 of c is empty; travelling s cells per axis reaches cells
 // at most floor(s)+1 away from c, and the exact DDA's cell is at most one more from the ideal line: s = D - 3.
+// t_probe (the group clearance, below): the caller knows that nothing occupied can be met in [t_from, t_probe), and the
+// probes start at max(t_from, t_probe); cells_skipped still counts from t_from, which is where the caller's DDA stands.
+// Only a POSITIVE t_probe is such a claim: clearances are computed for near planes >= 0 only, 0 is their "nothing is
+// claimed", and a segment that starts below 0 (a negative near plane) must not have its start moved by it.  The default,
+// -inf, is no claim for any segment; the trace inside a segment (from t_c) never takes one.
 CED_HD bool coarse_advance(const AccelSpec &S, int lvl, int res, const float *__restrict__ ab, const float (&o)[3],
-                           const float (&d)[3], float t_from, float t_to, float &t_stop, float &cells_skipped)
+                           const float (&d)[3], float t_from, float t_to, float &t_stop, float &cells_skipped,
+                           float t_probe = -__builtin_inff())
 {
     const float resf = (float)res;
     float sc[3], g = 0.0f;
@@ -167,7 +177,8 @@ CED_HD bool coarse_advance(const AccelSpec &S, int lvl, int res, const float *__
     cells_skipped = 0.0f;
     if (!(g > 0.0f) || !(g < 3.0e38f) || !(t_to - t_from < 3.0e38f)) return false;
     const float inv_g = 1.0f / g;
-    float t = t_from;
+    float t = t_probe > 0.0f ? fmaxf(t_from, t_probe) : t_from;
+    if (t >= t_to) return true;
     for (int guard = 0; guard < 8192; ++guard) {
         CED_DIAG_TICK(2);
         int c[3];
@@ -180,6 +191,130 @@ CED_HD bool coarse_advance(const AccelSpec &S, int lvl, int res, const float *__
     }
     t_stop = t_from;            // not reached in practice (every probe advances at least one cell)
     return false;
+}
+
+// ---- Group clearance: the same sphere trace, once for a bundle of rays ------------------------------------------------
+// A frame's rays arrive in groups of kGroupRays consecutive indices (an 8x8-pixel tile when the caller deals tiles, but
+// nothing here assumes a camera).  Per group ONE cone is traced through the distance field of every level, and the
+// result t_clear promises: no member ray meets an occupied cell of any level at a parameter t < t_clear (+inf: nowhere
+// between the near and far planes; 0: nothing is claimed).  The first iteration of a frame skips the groups with +inf
+// and hands the others' t_clear to traverse_ray_frame as t_hint.  PRECONDITION: near plane >= 0 -- every trace then runs
+// over t >= 0, where the bound below holds and t_clear >= 0; with a negative near plane every group gets 0 and the
+// renderers compute and pass nothing.
+//
+// The bound.  The group is described by a reference ray (oc, dc) -- one of its members, group_reference -- and per axis a
+// the largest deviations of the members from it, dev_o[a] = max_i |o_i - oc|, dev_d[a] = max_i |d_i - dc|.
+// With the probe at the reference point of parameter t, every member at parameter t' in [t, t + D] lies on axis a within
+//     sc_a * (dev_o[a] + dev_d[a] * t' + |dc_a| * (t' - t))        cells
+// of the probe.  As in coarse_advance, a probe cell with empty radius R lets every point within R - 3 cells on every axis
+// walk only empty cells (one cell for the probe's position inside its cell, one for the exact DDA straying from the
+// ideal line, and R - 1 is the last empty ring).  The expression grows with t', so the largest admissible D solves it at
+// t' = t + D, axis by axis.
+// A reference point outside the level's box is probed at the clamped cell: clamping an axis moves the probe towards
+// the box, so no member point INSIDE the box gets farther from it on any axis (a contraction in the Chebyshev metric),
+// and a member is only ever inside a level between its own entry and exit, which is where the trace runs; cells outside
+// the grid count as empty.
+// ALL FLOAT SLACK IS HERE: every position above is a handful of binary32 operations on numbers no larger than
+// M_a = |oc_a| + dev_o[a] + max|box_a| + (|dc_a| + dev_d[a]) * t', each rounding at most 2^-24 of that; that covers the
+// rounding of dev_*, of the probe's position and its conversion to a cell, and of t itself (the next probe
+// stands at fl(t + D), at most 2^-24 t' beyond t + D).  kClearRel = 2^-20 of sc_a * M_a is sixteen such roundings.
+// The division that solves for D and the sums of the bound's terms round relative to at most 255 * 8 cells: below
+// 2^-12 cells in all, inside the constant kClearAbs = 1/16 cell.
+constexpr int kGroupRays = 64;
+constexpr int kGroupMaxLevels = 8;             // the renderers' kMaxGrids: group_member's v holds 6 + 2 * this at most
+constexpr float kClearRel = 1.0f / 1048576.0f;
+constexpr float kClearAbs = 0.0625f;
+constexpr float kClearMinCells = 1.0f;         // a probe that allows less than this ends the trace (and bounds its length)
+
+struct RayGroupBounds {
+    float oc[3], dc[3], dev_o[3], dev_d[3];
+};
+
+CED_HD bool finite3(const float (&v)[3])
+{
+    return fabsf(v[0]) < __builtin_inff() && fabsf(v[1]) < __builtin_inff() && fabsf(v[2]) < __builtin_inff();
+}
+
+// The member that serves as the group's reference ray: at 9/16 of the group (ray 36 of 64: the centre pixel of an 8x8
+// tile dealt in raster order, next to the middle of a 64-pixel strip).  Any member is sound; a central one halves dev_d.
+CED_HD int group_reference(int members) { return members * 9 / 16; }
+
+// One member's share of its group's maxima against the reference ray (oc, dc): v[0..2] = |o - oc|, v[3..5] = |d - dc|,
+// and per level l the interval of the set-up's own slab test (frame_prep_kernel / decode_segment<SINGLE>: the same
+// arithmetic, so a level the walk visits is a level counted here) as v[6 + 2l] = -entry, v[7 + 2l] = exit -- every
+// entry of v is a maximum over the members (-inf before the first).  The host folds the members one after the other;
+// on the device every lane folds its own ray and the wave reduces.  `bad`: a non-finite component.
+CED_HD void group_member(const float (&o)[3], const float (&d)[3], const float (&oc)[3], const float (&dc)[3], int n_grids,
+                         const float *__restrict__ aabbs, float *v, bool &bad)
+{
+    bad = bad || !finite3(o) || !finite3(d);
+    const float inv_d[3] = { 1.0f / d[0], 1.0f / d[1], 1.0f / d[2] };
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        v[a] = fmaxf(v[a], fabsf(o[a] - oc[a]));
+        v[3 + a] = fmaxf(v[3 + a], fabsf(d[a] - dc[a]));
+    }
+#pragma unroll
+    for (int l = 0; l < kGroupMaxLevels; ++l) {        // (unrolled: v stays in registers on the device)
+        float t0, t1;
+        if (l >= n_grids || !slab_test(o, inv_d, aabbs + 6 * l, t0, t1)) continue;
+        v[6 + 2 * l] = fmaxf(v[6 + 2 * l], -t0);
+        v[7 + 2 * l] = fmaxf(v[7 + 2 * l], t1);
+    }
+}
+
+// One level: [t_lo, t_hi] = the union of the members' own [entry, exit] in this level's box, clamped to the near and far
+// planes.  Returns +inf when the whole of it is proven empty, else a t up to which it is.
+CED_HD float group_clear_level(const AccelSpec &S, int lvl, int res, const float *__restrict__ ab, const RayGroupBounds &B,
+                               float t_lo, float t_hi)
+{
+    if (!(t_lo < t_hi)) return __builtin_inff();          // no member is inside this level between the planes
+    const float resf = (float)res;
+    float sc[3], slope[3], base[3], per_t[3], g = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        sc[a] = resf / (ab[3 + a] - ab[a]);
+        const float reach = fabsf(B.dc[a]) + B.dev_d[a];   // units per unit t: any member against a fixed point
+        slope[a] = sc[a] * reach * (1.0f + kClearRel);
+        base[a] = sc[a] * (B.dev_o[a] + kClearRel * (fabsf(B.oc[a]) + B.dev_o[a] + fmaxf(fabsf(ab[a]), fabsf(ab[3 + a])))) + kClearAbs;
+        per_t[a] = sc[a] * (B.dev_d[a] + kClearRel * reach);
+        g = fmaxf(g, slope[a]);
+    }
+    if (!(g > 0.0f) || !(g < 3.0e38f) || !(t_hi < 3.0e38f) || !(base[0] + base[1] + base[2] < 3.0e38f)) return t_lo;
+    float t = t_lo;
+    for (int guard = 0; guard < 8192; ++guard) {
+        int c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            c[a] = clampi((int)fminf(fmaxf((B.oc[a] + B.dc[a] * t - ab[a]) * sc[a], -1.0f), resf), 0, res - 1);
+        const float room = (float)(empty_radius(S, lvl, res, c[0], c[1], c[2]) - 3);
+        float adv = __builtin_inff();
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float left = room - (base[a] + per_t[a] * t);
+            if (slope[a] > 0.0f) adv = fminf(adv, left / slope[a]);
+            else if (!(left >= 0.0f)) adv = -1.0f;
+        }
+        if (!(adv * g >= kClearMinCells)) return t;
+        t += adv;
+        if (t >= t_hi) return __builtin_inff();
+    }
+    return t;
+}
+
+// t_clear of a group: lim[2 * lvl], lim[2 * lvl + 1] = the smallest entry and the largest exit of the members that hit
+// level lvl's box (slab_test; +inf / -inf when none does).
+CED_HD float group_clear(const AccelSpec &S, int n_grids, int res, const float *__restrict__ aabbs, const RayGroupBounds &B,
+                         const float *__restrict__ lim, float near, float far)
+{
+    // near >= 0 is a precondition of the bound: the deviation term dev_d * t' (group_clear_level) is |t'| for real, and
+    // 0 is only "nothing is claimed" when no segment starts below it.  With a negative (or NaN) near plane: no claim.
+    if (!(near >= 0.0f)) return 0.0f;
+    if (!(finite3(B.oc) && finite3(B.dc) && finite3(B.dev_o) && finite3(B.dev_d))) return 0.0f;
+    float t_clear = __builtin_inff();
+    for (int lvl = 0; lvl < n_grids; ++lvl)
+        t_clear = fminf(t_clear, group_clear_level(S, lvl, res, aabbs + 6 * lvl, B, fmaxf(lim[2 * lvl], near), fminf(lim[2 * lvl + 1], far)));
+    return t_clear;
 }
 
 // The exact DDA of one segment: per axis the time of the next boundary crossing, the time between crossings, the cell
@@ -338,12 +473,14 @@ CED_HD bool emit_cell(const GridSpec &G, MarchCursor &C, float t_trav, Emit &emi
 // occupied cells).  LOOK: cells the exact walk looks ahead.  SINGLE: one grid level (decode_segment).  PHASED: the exact
 // walk as a looking loop and an emission phase (a frame's first iteration: rays travel to their first occupied cell,
 // each for its own number of batches); otherwise the emission inline in the batch (rays that stand inside the object
-// and emit in every batch).  Same operations per ray in the same order either way.
+// and emit in every batch).  Same operations per ray in the same order either way.  t_hint: nothing occupied is met
+// before it (the ray's group clearance; 0 or less, and the default -inf: no claim) -- the trace at a segment's start
+// probes from there.
 template <int LOOK, bool SINGLE, bool PHASED, class Idx, class Emit>
 CED_HD int traverse_ray_frame(const GridSpec &G, const AccelSpec &S, bool start_coarse, const float (&o)[3],
                               const float (&d)[3], float near, float far, const float *__restrict__ ts_row,
                               const Idx *__restrict__ ti_row, const uint8_t *__restrict__ hit_row, Emit &&emit,
-                              float &t_term)
+                              float &t_term, float t_hint = -__builtin_inff())
 {
     const float inv_d[3] = { 1.0f / d[0], 1.0f / d[1], 1.0f / d[2] };
     const int n_grids = SINGLE ? 1 : G.n_grids, res = G.res;
@@ -366,7 +503,7 @@ CED_HD int traverse_ray_frame(const GridSpec &G, const AccelSpec &S, bool start_
         bool traced = false;
         float t_stop0 = 0.0f, cells0 = 0.0f;
         if (coarse) {
-            if (coarse_advance(S, lvl, res, ab, o, d, this_tmin, this_tmax, t_stop0, cells0)) {
+            if (coarse_advance(S, lvl, res, ab, o, d, this_tmin, this_tmax, t_stop0, cells0, t_hint)) {
                 C.continuous = false;          // the whole segment is empty cells
                 continue;
             }

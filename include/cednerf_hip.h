@@ -220,6 +220,29 @@ int ced_host_march_frame(int64_t n_rays, const float *rays_o, const float *rays_
                          int32_t use_lattice, int32_t walk, int32_t *counts, float *t_starts, float *t_ends,
                          float *t_term);
 
+/* HOST functions (validation aids): the group clearance of the frame renderer's first iteration (csrc/march_accel.hpp,
+ * group_clear), with the code the device runs.  ced_host_ray_group_clear: for every frame and every group of 64
+ * consecutive rays of it (the last group may be partial; with local_rays [n_frames], host, only the first local_rays[f]
+ * rays of frame f are members) one float t_clear[f * ceil(rays_per_frame / 64) + k]: no member ray meets an occupied
+ * cell of any level at a parameter t < t_clear (+inf: nowhere between the planes; 0: nothing is claimed, e.g. a
+ * non-finite ray component).  Precondition near_plane >= 0 (the cone bound holds for t >= 0): with a negative near plane
+ * every group gets 0, and the renderers compute nothing and pass no hint.  accel_mode 1 = brick field only, 2 = brick +
+ * cell fields.
+ * ced_host_march_frame_hinted: ced_host_march_frame with a hint per ray, t_hint [n_rays] -- nothing occupied is met
+ * before it (a ray's group clearance); a hint of 0 or less claims nothing and never moves the start of a segment, so
+ * segments below 0 (negative near planes) walk as without hints.  The trace at a segment's start probes from there.  Same samples, counts
+ * and termination planes as without hints (walks 0..2; walk 3 takes no hint). */
+int ced_host_ray_group_clear(int32_t n_frames, int64_t rays_per_frame, const int32_t *local_rays, const float *rays_o,
+                             const float *rays_d, int32_t n_grids, int32_t res, const float *aabbs,
+                             const uint8_t *accel_host, int32_t accel_mode, float near_plane, float far_plane,
+                             float *t_clear);
+int ced_host_march_frame_hinted(int64_t n_rays, const float *rays_o, const float *rays_d, const uint8_t *binaries,
+                                int32_t n_grids, int32_t res, const float *aabbs, const float *near_planes,
+                                float far_plane, float step_size, float cone_angle, int32_t limit, const float *t_sorted,
+                                const int64_t *t_indices, const uint8_t *hits, const uint8_t *accel_host,
+                                int32_t accel_mode, int32_t use_lattice, int32_t walk, const float *t_hint,
+                                int32_t *counts, float *t_starts, float *t_ends, float *t_term);
+
 /* HOST function (validation aid): the kernels' empty-space skip -- advance t_last by whole steps
  * dt = clamp(t*cone_angle, step_size, 1e10) until t_last + dt/2 >= target -- evaluated on the host
  * with the same code the device runs (closed form when cone_angle == 0). */
