@@ -32,6 +32,70 @@
 
 namespace ced {
 
+// Rays-mode front end of a tile: two batches of loads, each issued together and waited for once.  The forms of a call
+// must not put a branch between the loads of a batch -- the compiler moves no load across one, and each block then
+// waits for its own: the 32- or 64-bit ray indices are the one branch, around the index loads alone and after the
+// loads that do not depend on it; an unused slot's values are dropped by a select; shared time is entry 0 of the array.
+//
+// First batch, addressed by the slot alone: t0, t1 and the ray index of every j.  Every slot below n_eff is valid
+// memory, so an unused slot (negative ray index) loads its t0 / t1 too; what they hold is discarded (a select, not a
+// product: the memory may hold NaN) and the slot is evaluated on ray 0 at t = 0.  Returns whether the lane has a used slot.
+template <int NT>
+__device__ __forceinline__ bool load_tile_slots(const FieldArgs &A, int64_t first, const int (&sofs)[NT], int64_t (&ridx)[NT],
+                                                float (&tm2)[NT])
+{
+    int64_t r_in[NT];
+    float t0[NT], t1[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        t0[j] = A.t0[first + sofs[j]];
+        t1[j] = A.t1[first + sofs[j]];
+    }
+    if (A.ray_idx32) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) r_in[j] = (int64_t)A.ray_idx32[first + sofs[j]];
+    } else {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) r_in[j] = A.ray_idx[first + sofs[j]];
+    }
+    bool any_used = false;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const bool used = r_in[j] >= 0;
+        any_used = any_used || used;
+        ridx[j] = used ? r_in[j] : 0;
+        const float sum = t0[j] + t1[j];
+        tm2[j] = used ? sum : 0.0f;
+    }
+    return any_used;
+}
+
+// Second batch, addressed by the ray: origin, direction and timestamp of every j, then the sample positions.
+template <int NT>
+__device__ __forceinline__ void load_tile_rays(const FieldArgs &A, const int64_t (&ridx)[NT], const float (&tm2)[NT],
+                                               float (&px)[NT][3], float (&tq)[NT])
+{
+    float o[NT][3], d[NT][3];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            o[j][a] = A.rays_o[3 * ridx[j] + a];
+            d[j][a] = A.rays_d[3 * ridx[j] + a];
+        }
+        tq[j] = A.timestamps[A.t_per_ray ? ridx[j] : 0];
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) px[j][a] = o[j][a] + (d[j][a] * tm2[j]) / 2.0f;
+    }
+    // the timestamps are this batch's: without a use here the compiler merges their loads with the explicit mode's
+    // loads of t into one after the two modes join, a round trip of its own
+#pragma unroll
+    for (int j = 0; j < NT; ++j) asm volatile("" : "+v"(tq[j]));
+}
+
 template <bool TE, bool F16, bool TEMPORAL, bool SPLIT, int NT, int THREADS>
 __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
 {
@@ -116,31 +180,24 @@ __global__ __launch_bounds__(THREADS) void field_half_kernel(FieldArgs A)
         int sofs[NT];
         int64_t ridx[NT];
         float px[NT][3], tq[NT];
-        bool any_used = !A.rays_mode;
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            sofs[j] = 16 * j + c < in_tile ? 16 * j + c : in_tile - 1;
-            const int64_t s = tile_base + sofs[j];
-            if (A.rays_mode) {
-                // negative ray index = unused sample slot (see field_kernel.hpp)
-                const int64_t r_in = A.ray_idx32 ? (int64_t)A.ray_idx32[sbase + s] : A.ray_idx[sbase + s];
-                const bool used = r_in >= 0;
-                const int64_t r = used ? r_in : 0;
-                any_used = any_used || used;
-                ridx[j] = r;
-                const float tm2 = used ? A.t0[sbase + s] + A.t1[sbase + s] : 0.0f;
+        for (int j = 0; j < NT; ++j) sofs[j] = 16 * j + c < in_tile ? 16 * j + c : in_tile - 1;
+        if (A.rays_mode) {
+            // negative ray index = unused sample slot (see field_kernel.hpp); two batches of loads (load_tile_slots)
+            float tm2[NT];
+            const bool any_used = load_tile_slots(A, sbase + tile_base, sofs, ridx, tm2);
+            if (__ballot(any_used) == 0ull) continue;        // a tile of unused slots only (wave-uniform)
+            load_tile_rays(A, ridx, tm2, px, tq);
+        } else {
 #pragma unroll
-                for (int a = 0; a < 3; ++a) px[j][a] = A.rays_o[3 * r + a] + (A.rays_d[3 * r + a] * tm2) / 2.0f;
-                tq[j] = A.t_per_ray ? A.timestamps[r] : A.timestamps[0];
-            } else {
+            for (int j = 0; j < NT; ++j) {
+                const int64_t s = tile_base + sofs[j];
                 ridx[j] = s;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) px[j][a] = A.pos[3 * s + a];
                 tq[j] = A.t[s];
             }
         }
-
-        if (__ballot(any_used) == 0ull) continue;            // a tile of unused slots only (wave-uniform)
 
         h8 Bh[NT][2], Bl[NT][2];
         f4 D[NT][4];
