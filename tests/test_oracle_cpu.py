@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import field_variants as _variants
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -184,7 +186,8 @@ def test_kat_composite_test(oracle):
 # ---- (3) independent PyTorch restatement --------------------------------------------------------
 @pytest.mark.parametrize("flags", [dict(), dict(use_div_offsets=True, use_time_embedding=True, use_time_attenuation=True),
                                    dict(use_time_embedding=True, table_dtype=np.float16),
-                                   dict(temporal_hash=True)])
+                                   dict(temporal_hash=True)]
+                         + [_variants.variant_kw(sel) for sel in _variants.SELS])   # every table / time variant
 @pytest.mark.parametrize("regime", ["init", "trained"])
 def test_c_oracle_matches_torch_oracle_field(oracle, flags, regime):
     from ced_nerf_amd import synthetic as S
