@@ -192,8 +192,10 @@ PROTOTYPES = {
     "ced_mlp_backward_dw_workspace_bytes": (_i64, [_i64, _i32, C.POINTER(_i32)]),
     "ced_mlp_backward_dw": (C.c_int, [_i64, _i32, _vp, C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp, _i64, _vp]),
     "ced_train_inputs": (C.c_int, [_i64] + [_vp] * 13),
+    "ced_train_inputs_backward": (C.c_int, [_i64, _i64] + [_vp] * 17),
     "ced_train_warp": (C.c_int, [_i64, _vp, _vp, _i32, _i32, _f, C.POINTER(C.c_float), _vp, _vp, _vp, _vp]),
     "ced_train_warp_backward": (C.c_int, [_i64, _vp, _vp, _i32, _i32, _f, C.POINTER(C.c_float), _vp, _vp, _vp, _vp]),
+    "ced_train_warp_backward_pos": (C.c_int, [_i64, _vp, _vp, _i32, _i32, _f, C.POINTER(C.c_float), _vp, _vp, _vp]),
     "ced_train_head_in": (C.c_int, [_i64] + [_vp] * 6),
     "ced_train_head_in_backward": (C.c_int, [_i64] + [_vp] * 6),
     "ced_render_image_gather": (C.c_int, [_i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -3,6 +3,7 @@
 // the ~35 torch element-wise / gather / cat kernels per direction they replace:
 //   ced_train_inputs        sample positions from the rays, Frequency(4) of (x, t) for the motion MLP, SH(2) of the
 //                           direction for the colour head                              (model.py:354-356, 447-455)
+//   ced_train_inputs_backward  its gradient at the rays (or positions / directions / times), summed per ray
 //   ced_train_warp[_bwd]    x' = x + move, normalised into the box, clamped; selector   (model.py:356-383)
 //   ced_train_head_in[_bwd] density = exp(raw - 1) * selector (trunc_exp, utils.py:27-43), colour-head input
 //                           [SH(4), geo(15)]                                             (model.py:414-417, 455)
@@ -67,6 +68,156 @@ __global__ __launch_bounds__(256) void train_inputs_kernel(TrainInputsArgs A)
     else A.t_out[i] = t;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Backward of train_inputs_kernel: the gradient at (positions, directions, time) per sample, and in rays mode its
+// sum over each ray's samples.  The lane layout is the forward's: lane q of a sample's four owns input dimension q
+// (x, y, z, t), reads that dimension's eight d_enc floats with two 16-byte loads and recomputes their sin / cos.
+// ---------------------------------------------------------------------------------------------------------------
+struct TrainInputsBwdArgs {
+    int64_t n, n_rays;
+    const float *rays_o, *rays_d;        // rays mode: [n_rays, 3]
+    const int64_t *ray_idx;              // [n], non-decreasing, or NULL (explicit mode)
+    const float *t0, *t1, *ts;
+    const float *pos_in, *dir_in;        // explicit mode: [n, 3]
+    const int64_t *packed;               // rays mode: [n_rays, 2] (first sample, count)
+    const float *d_pos, *d_enc, *d_sh, *d_t;     // [n,3], [n,32], [n,4], [n]; each may be NULL (= zero)
+    float *g_o, *g_d, *g_t;              // rays mode: [n_rays,3], [n_rays,3], [n_rays]; explicit mode: [n,3], [n,3], [n]
+};
+
+// Lane q of sample i, v its Frequency input (p[q] or t), d the direction:
+//   ga = d_pos[i, q] (q < 3) or d_t[i] (q = 3), plus sum_k pi 2^k (d_enc[i, 8q + 2k] cos_k - d_enc[i, 8q + 2k + 1] sin_k)
+//   gb = component q of the direction's gradient (g_w - w (w . g_w)) / |d|, w as the forward forms it (q < 3; else 0)
+__device__ __forceinline__ void train_inputs_bwd_lane(const TrainInputsBwdArgs &A, int64_t i, int q, float v,
+                                                      const float (&d)[3], float &ga, float &gb)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    float g = 0.0f;
+    if (A.d_enc) {
+        const f4 *e = reinterpret_cast<const f4 *>(A.d_enc + i * 32 + 8 * q);
+        const f4 e0 = e[0], e1 = e[1];
+        float s, c;
+        det_sinpi_both(v * 1.0f, s, c); const float a0 = 3.14159274101257324f * (e0[0] * c - e0[1] * s);
+        det_sinpi_both(v * 2.0f, s, c); const float a1 = 6.28318548202514648f * (e0[2] * c - e0[3] * s);
+        det_sinpi_both(v * 4.0f, s, c); const float a2 = 12.5663709640502930f * (e1[0] * c - e1[1] * s);
+        det_sinpi_both(v * 8.0f, s, c); const float a3 = 25.1327419281005859f * (e1[2] * c - e1[3] * s);
+        g = ((a0 + a1) + a2) + a3;
+    }
+    float up = 0.0f;
+    if (q < 3) { if (A.d_pos) up = A.d_pos[3 * i + q]; }
+    else if (A.d_t) up = A.d_t[i];
+    ga = up + g;
+    gb = 0.0f;
+    if (A.d_sh && q < 3) {
+        const f4 ds = *reinterpret_cast<const f4 *>(A.d_sh + 4 * i);
+        const float K = 0.48860251190291987f;
+        const float gw[3] = { -K * ds[3], -K * ds[1], K * ds[2] };
+        const float nrm = __builtin_sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        float w[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) w[a] = ((d[a] / nrm + 1.0f) / 2.0f) * 2.0f - 1.0f;
+        const float dot = (w[0] * gw[0] + w[1] * gw[1]) + w[2] * gw[2];
+        const float wq = q == 0 ? w[0] : (q == 1 ? w[1] : w[2]);
+        const float gq = q == 0 ? gw[0] : (q == 1 ? gw[1] : gw[2]);
+        gb = (gq - wq * dot) / nrm;
+    }
+}
+
+__global__ __launch_bounds__(256) void train_inputs_bwd_kernel(TrainInputsBwdArgs A)
+{
+    // explicit mode: one row of each output per sample
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = gid >> 2;
+    const int q = (int)(gid & 3);
+    if (i >= A.n) return;
+    float d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) d[a] = A.dir_in[3 * i + a];
+    const float v = q < 3 ? A.pos_in[3 * i + q] : A.ts[i];
+    float ga, gb;
+    train_inputs_bwd_lane(A, i, q, v, d, ga, gb);
+    if (q < 3) { A.g_o[3 * i + q] = ga; A.g_d[3 * i + q] = gb; }
+    else A.g_t[i] = ga;
+}
+
+constexpr int kInputsBwdChunk = 64;      // samples a wave answers for: it sums every ray that STARTS among them
+
+// Rays mode.  The samples of a ray are consecutive (ray_idx is non-decreasing), so a ray's gradient is a segmented sum
+// over the sample stream.  Each wave takes 64 consecutive samples and owns the rays whose first sample is among them: it
+// skips the head samples of a ray that began earlier (that ray's owner runs on into this chunk) and runs on past its
+// chunk to the end of its last ray.  It walks its samples 16 at a time (four lanes each, as above); a pass is a segmented
+// inclusive scan over the 16 samples (shuffles at lane distances 4, 8, 16, 32, joined where the ray index agrees), the
+// open ray's partial sum is carried into the next pass in registers, and the lanes of a ray's last sample store its
+// rows.  No atomics, no LDS, no barrier, no workspace; the order of every sum is fixed by the inputs.  Blocks past the
+// sample blocks write the zero rows of the rays without samples.
+__global__ __launch_bounds__(256) void train_inputs_bwd_rays_kernel(TrainInputsBwdArgs A, unsigned sample_blocks)
+{
+    if (blockIdx.x >= sample_blocks) {
+        const int64_t r = (int64_t)(blockIdx.x - sample_blocks) * blockDim.x + threadIdx.x;
+        if (r < A.n_rays && A.packed[2 * r + 1] == 0) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { A.g_o[3 * r + a] = 0.0f; A.g_d[3 * r + a] = 0.0f; }
+            A.g_t[r] = 0.0f;
+        }
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int q = lane & 3, s = lane >> 2;
+    const int64_t c0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kInputsBwdChunk;
+    if (c0 >= A.n) return;
+    const int64_t c1 = c0 + kInputsBwdChunk < A.n ? c0 + kInputsBwdChunk : A.n;
+    int64_t first = c0;
+    if (c0 > 0) {
+        const int64_t r0 = A.ray_idx[c0];
+        if ((uint64_t)r0 >= (uint64_t)A.n_rays) return;
+        if (A.ray_idx[c0 - 1] == r0) first = A.packed[2 * r0] + A.packed[2 * r0 + 1];     // where the ray before ends
+        if (first < c0) first = c0;
+    }
+    if (first >= c1) return;                       // one earlier ray covers the whole chunk
+    const int64_t rl = A.ray_idx[c1 - 1];
+    if ((uint64_t)rl >= (uint64_t)A.n_rays) return;
+    int64_t end = A.packed[2 * rl] + A.packed[2 * rl + 1];
+    if (end > A.n) end = A.n;
+    float carry_a = 0.0f, carry_b = 0.0f;
+    int carry_ray = -1;
+    for (int64_t base = first; base < end; base += 16) {
+        const int64_t i = base + s;
+        const bool valid = i < end;
+        int ray = -2;                              // the low word of the ray index; -2: no sample
+        int64_t r = 0;
+        bool last = false;
+        float va = 0.0f, vb = 0.0f;
+        if (valid) {
+            r = A.ray_idx[i];
+            ray = (int)r;
+            last = i + 1 >= A.n || A.ray_idx[i + 1] != r;
+            if ((uint64_t)r >= (uint64_t)A.n_rays) { r = 0; last = false; }
+            const float tm = (A.t0[i] + A.t1[i]) / 2.0f;
+            float d[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) d[a] = A.rays_d[3 * r + a];
+            const float dq = q == 0 ? d[0] : (q == 1 ? d[1] : d[2]);
+            const float v = q < 3 ? A.rays_o[3 * r + q] + dq * tm : A.ts[r];
+            float gb;
+            train_inputs_bwd_lane(A, i, q, v, d, va, gb);
+            vb = va * tm + gb;                     // d_rays_d's term: g_pos t_mid + g_dir (unused by lane 3)
+            if (s == 0 && ray == carry_ray) { va = carry_a + va; vb = carry_b + vb; }
+        }
+#pragma unroll
+        for (int off = 4; off < 64; off <<= 1) {
+            const float ua = __shfl_up(va, off, 64), ub = __shfl_up(vb, off, 64);
+            const int ur = __shfl_up(ray, off, 64);
+            if (lane >= off && ur == ray) { va = ua + va; vb = ub + vb; }
+        }
+        if (valid && last) {
+            if (q < 3) { A.g_o[3 * r + q] = va; A.g_d[3 * r + q] = vb; }
+            else A.g_t[r] = va;
+        }
+        carry_a = __shfl(va, 60 + q, 64);
+        carry_b = __shfl(vb, 60 + q, 64);
+        carry_ray = __shfl(ray, 63, 64);
+    }
+}
+
 struct TrainWarpArgs {
     int64_t n;
     const float *pos, *mo;               // [n,3], [n,mo_w]
@@ -76,6 +227,7 @@ struct TrainWarpArgs {
     const float *d_xn, *d_move;          // backward inputs (d_move may be NULL)
     float *d_mo;                         // backward output [n, mo_w]
     const float *xn_raw_sel;             // unused
+    float *d_pos;                        // backward output [n, 3] (train_warp_bwd_pos_kernel)
 };
 
 __device__ __forceinline__ float det_tanhf(float x)
@@ -121,6 +273,21 @@ __global__ __launch_bounds__(256) void train_warp_bwd_kernel(TrainWarpArgs A)
         if (A.use_div) A.d_mo[i * A.mo_w + 3 + a] = (g * A.moving_step) * (1.0f - th * th);
     }
     for (int k = A.use_div ? 6 : 3; k < A.mo_w; ++k) A.d_mo[i * A.mo_w + k] = 0.0f;
+}
+
+// d_pos from d_xn: the same clamp rule, and d xn / d pos = 1 / (aabb_hi - aabb_lo); `move` does not depend on pos
+__global__ __launch_bounds__(256) void train_warp_bwd_pos_kernel(TrainWarpArgs A)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float mv = A.mo[i * A.mo_w + a] * A.moving_step;
+        if (A.use_div) mv = mv + det_tanhf(A.mo[i * A.mo_w + 3 + a]) * A.moving_step;
+        const float xn = ((A.pos[3 * i + a] + mv) - A.lo[a]) / A.ext[a];
+        const bool pass = xn >= 0.0f && xn <= 1.0f;
+        A.d_pos[3 * i + a] = pass ? A.d_xn[3 * i + a] / A.ext[a] : 0.0f;
+    }
 }
 
 struct TrainHeadArgs {
@@ -188,6 +355,36 @@ extern "C" int ced_train_inputs(int64_t n, const float *rays_o, const float *ray
     return ced::check_launch("train_inputs");
 }
 
+extern "C" int ced_train_inputs_backward(int64_t n, int64_t n_rays, const float *rays_o, const float *rays_d,
+                                         const int64_t *ray_indices, const float *t_starts, const float *t_ends,
+                                         const float *timestamps, const float *positions, const float *directions,
+                                         const int64_t *packed_info, const float *d_pos, const float *d_enc,
+                                         const float *d_sh, const float *d_t, float *d_origins, float *d_directions,
+                                         float *d_times, void *stream)
+{
+    CED_REQUIRE(n >= 0 && n_rays >= 0, "train_inputs_backward: n < 0 or n_rays < 0");
+    if (ray_indices ? n_rays == 0 : n == 0) return CED_OK;
+    CED_REQUIRE(timestamps && d_origins && d_directions && d_times, "train_inputs_backward: null pointer");
+    CED_REQUIRE(!d_enc || (reinterpret_cast<uintptr_t>(d_enc) & 15) == 0, "train_inputs_backward: d_enc must be 16-byte aligned");
+    CED_REQUIRE(!d_sh || (reinterpret_cast<uintptr_t>(d_sh) & 15) == 0, "train_inputs_backward: d_sh must be 16-byte aligned");
+    ced::TrainInputsBwdArgs A{ n, n_rays, rays_o, rays_d, ray_indices, t_starts, t_ends, timestamps, positions, directions,
+                               packed_info, d_pos, d_enc, d_sh, d_t, d_origins, d_directions, d_times };
+    if (!ray_indices) {
+        CED_REQUIRE(positions && directions, "train_inputs_backward: explicit mode needs positions and directions");
+        hipLaunchKernelGGL(ced::train_inputs_bwd_kernel, dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+        return ced::check_launch("train_inputs_backward");
+    }
+    CED_REQUIRE(n == 0 || (rays_o && rays_d && t_starts && t_ends), "train_inputs_backward: rays mode needs rays and sample intervals");
+    CED_REQUIRE(packed_info, "train_inputs_backward: rays mode needs packed_info");
+    CED_REQUIRE(n_rays < (int64_t)1 << 31, "train_inputs_backward: n_rays %lld", (long long)n_rays);
+    const int64_t per_block = 4 * ced::kInputsBwdChunk;
+    const unsigned sample_blocks = (unsigned)((n + per_block - 1) / per_block);
+    const unsigned ray_blocks = (unsigned)((n_rays + 255) / 256);
+    hipLaunchKernelGGL(ced::train_inputs_bwd_rays_kernel, dim3(sample_blocks + ray_blocks), dim3(256), 0, (hipStream_t)stream, A,
+                       sample_blocks);
+    return ced::check_launch("train_inputs_backward");
+}
+
 static int fill_warp(ced::TrainWarpArgs &A, int64_t n, const float *pos, const float *mo, int32_t mo_width,
                      int32_t use_div_offsets, float moving_step, const float *aabb_host, const char *who)
 {
@@ -224,6 +421,20 @@ extern "C" int ced_train_warp_backward(int64_t n, const float *pos, const float 
     A.d_xn = d_xn; A.d_move = d_move; A.d_mo = d_mo;
     hipLaunchKernelGGL(ced::train_warp_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
     return ced::check_launch("train_warp_backward");
+}
+
+extern "C" int ced_train_warp_backward_pos(int64_t n, const float *pos, const float *mo, int32_t mo_width,
+                                           int32_t use_div_offsets, float moving_step, const float *aabb_host,
+                                           const float *d_xn, float *d_pos, void *stream)
+{
+    ced::TrainWarpArgs A{};
+    int rc = fill_warp(A, n, pos, mo, mo_width, use_div_offsets, moving_step, aabb_host, "train_warp_backward_pos");
+    if (rc) return rc;
+    if (n == 0) return CED_OK;
+    CED_REQUIRE(d_xn && d_pos, "train_warp_backward_pos: null pointer");
+    A.d_xn = d_xn; A.d_pos = d_pos;
+    hipLaunchKernelGGL(ced::train_warp_bwd_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+    return ced::check_launch("train_warp_backward_pos");
 }
 
 extern "C" int ced_train_head_in(int64_t n, const float *bout, const float *sh, const float *selector, float *head_in,

@@ -951,6 +951,47 @@ def train_inputs(n, rays_o=None, rays_d=None, ray_indices=None, t_starts=None, t
     return pos, enc, sh, t
 
 
+def train_inputs_backward(n, rays_o=None, rays_d=None, ray_indices=None, t_starts=None, t_ends=None, timestamps=None,
+                          positions=None, directions=None, packed_info=None, d_pos=None, d_enc=None, d_sh=None, d_t=None):
+    """ced_train_inputs_backward: the forward's inputs and the gradients at its outputs (None = zero) ->
+    rays mode (d_rays_o [R,3], d_rays_d [R,3], d_timestamps [R]), R = rays_o.shape[0], with packed_info [R, 2] int64 the
+    (first sample, count) of the non-decreasing ray_indices; explicit mode (d_positions [n,3], d_directions [n,3],
+    d_timestamps [n])."""
+    rays = ray_indices is not None
+    ref = rays_o if rays else positions
+    dev, f32 = ref.device, torch.float32
+    for t_, nm in ((rays_o, "rays_o"), (rays_d, "rays_d"), (t_starts, "t_starts"), (t_ends, "t_ends"),
+                   (timestamps, "timestamps"), (positions, "positions"), (directions, "directions"), (d_pos, "d_pos"),
+                   (d_enc, "d_enc"), (d_sh, "d_sh"), (d_t, "d_t")):
+        _chk(t_, f32, nm, allow_none=True)
+    _chk(ray_indices, torch.int64, "ray_indices", allow_none=True)
+    _chk(packed_info, torch.int64, "packed_info", allow_none=True)
+    for t_, shape in ((d_pos, (n, 3)), (d_enc, (n, 32)), (d_sh, (n, 4)), (d_t, (n,))):
+        assert t_ is None or tuple(t_.shape) == shape, f"{tuple(t_.shape)} v.s. {shape}"
+    if rays:
+        rows = rays_o.shape[0]
+        assert ray_indices.shape == (n,) and t_starts.shape == (n,) and t_ends.shape == (n,)
+        assert rays_d.shape == (rows, 3) and timestamps.shape == (rows,) and tuple(packed_info.shape) == (rows, 2)
+    else:
+        rows = n
+        assert positions.shape == (n, 3) and directions.shape == (n, 3) and timestamps.shape == (n,)
+    if d_enc is not None and d_enc.data_ptr() % 16:
+        d_enc = d_enc.clone()
+    if d_sh is not None and d_sh.data_ptr() % 16:
+        d_sh = d_sh.clone()
+    if n == 0:                       # no sample: every row is zero (an empty ray_indices has no address to tell the mode by)
+        return torch.zeros((rows, 3), device=dev, dtype=f32), torch.zeros((rows, 3), device=dev, dtype=f32), \
+            torch.zeros((rows,), device=dev, dtype=f32)
+    g_o = torch.empty((rows, 3), device=dev, dtype=f32)
+    g_d = torch.empty((rows, 3), device=dev, dtype=f32)
+    g_t = torch.empty((rows,), device=dev, dtype=f32)
+    rc = _lib.lib().ced_train_inputs_backward(n, rows, _p(rays_o), _p(rays_d), _p(ray_indices), _p(t_starts), _p(t_ends),
+                                              _p(timestamps), _p(positions), _p(directions), _p(packed_info), _p(d_pos),
+                                              _p(d_enc), _p(d_sh), _p(d_t), _p(g_o), _p(g_d), _p(g_t), _stream())
+    _lib.check(rc, "train_inputs_backward")
+    return g_o, g_d, g_t
+
+
 def train_warp(pos, mo, aabb6, moving_step: float, use_div_offsets: bool):
     """ced_train_warp -> (xn clamped [n,3], move [n,3], selector [n] as 0 / 1 floats).  aabb6: six python floats."""
     _chk(pos, torch.float32, "pos"); _chk(mo, torch.float32, "mo")
@@ -972,6 +1013,17 @@ def train_warp_backward(pos, mo, aabb6, moving_step: float, use_div_offsets: boo
                                             _stream())
     _lib.check(rc, "train_warp_backward")
     return d_mo
+
+
+def train_warp_backward_pos(pos, mo, aabb6, moving_step: float, use_div_offsets: bool, d_xn):
+    """ced_train_warp_backward_pos -> d_pos [n,3]."""
+    _chk(pos, torch.float32, "pos"); _chk(mo, torch.float32, "mo"); _chk(d_xn, torch.float32, "d_xn")
+    assert d_xn.shape == pos.shape
+    d_pos = torch.empty_like(pos)
+    rc = _lib.lib().ced_train_warp_backward_pos(pos.shape[0], _p(pos), _p(mo), mo.shape[1], int(bool(use_div_offsets)),
+                                                float(moving_step), (C.c_float * 6)(*aabb6), _p(d_xn), _p(d_pos), _stream())
+    _lib.check(rc, "train_warp_backward_pos")
+    return d_pos
 
 
 def train_head_in(bout, sh, selector):

@@ -13,6 +13,9 @@ What runs where:
     `fused_glue = False` restores the torch statements they replaced, which the tests compare them with).  Only the
     sigmoid, the time encoders and the losses (huber, smooth-L1 / MSE, the opacity / entropy / weighted-colour
     regularisers) remain torch element-wise kernels; the distortion regulariser is HIP (ced_distortion_loss_density).
+  * gradients at the rays and times in FRONT of the field (`CameraRefinement`, `align_view`; nothing in the reference) -> HIP:
+    the input stage's backward with its per-ray sums (ced_train_inputs_backward, `_InputsFn`) and the warp's d_pos
+    (ced_train_warp_backward_pos), taken only when a ray origin, direction or time requires a gradient.
 `TrainableField` keeps the parameter names and layout of `DNGPradianceField` (hash_table, xyz_wrap, mlp_base,
 mlp_head as W[out][in]), so `to_inference()` hands the trained weights to the fused kernels unchanged, and
 `tests/test_gpu_parity.py` checks that the two forwards agree.  Mirrors cednerf/model.py:354-488 (forward) and the
@@ -180,6 +183,40 @@ class _MlpFn(torch.autograd.Function):
         return (dz if ctx.needs_input_grad[0] else None, *grads)
 
 
+class _InputsFn(torch.autograd.Function):
+    """ced_train_inputs as an autograd node, for the calls in which something in FRONT of the field is being learnt (a
+    camera pose, a time offset: `CameraRefinement`, `align_view`).  (a, b, ts) are (rays_o, rays_d, ts_per_ray) with
+    ray-packed samples, (positions, directions, t) with ray_indices None.  The backward is one launch
+    (ced_train_inputs_backward): per-sample gradients of the Frequency / SH encodings and of o + d t_mid, summed per ray
+    in a fixed order.  `TrainableField` applies it only when one of the three requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, ts, ray_indices, t_starts, t_ends):
+        a, b, ts = (v.detach().float().contiguous() for v in (a, b, ts))
+        if ray_indices is None:
+            saved = (a, b, ts)
+            out = ops.train_inputs(a.shape[0], positions=a, directions=b, timestamps=ts)
+        else:
+            saved = (a, b, ts, ray_indices.contiguous(), t_starts.detach().contiguous(), t_ends.detach().contiguous())
+            out = ops.train_inputs(saved[3].shape[0], a, b, saved[3], saved[4], saved[5], ts)
+        ctx.save_for_backward(*saved)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_pos, d_enc, d_sh, d_t):
+        c = lambda g: None if g is None else g.float().contiguous()
+        ups = dict(d_pos=c(d_pos), d_enc=c(d_enc), d_sh=c(d_sh), d_t=c(d_t))
+        if len(ctx.saved_tensors) == 3:
+            a, b, ts = ctx.saved_tensors
+            g = ops.train_inputs_backward(a.shape[0], positions=a, directions=b, timestamps=ts, **ups)
+        else:
+            a, b, ts, ri, t0, t1 = ctx.saved_tensors
+            g = ops.train_inputs_backward(ri.shape[0], a, b, ri, t0, t1, ts, packed_info=_packed_info_from(ri, a.shape[0]),
+                                          **ups)
+        return (*(gi if need else None for gi, need in zip(g, ctx.needs_input_grad[:3])), None, None, None)
+
+
 class _WarpFn(torch.autograd.Function):
     """move / normalise / clamp / selector of cednerf/model.py:356-383 in one launch per direction (ced_train_warp)."""
 
@@ -201,7 +238,10 @@ class _WarpFn(torch.autograd.Function):
             d_xn = torch.zeros_like(pos)
         d_mo = ops.train_warp_backward(pos, mo, aabb6, moving_step, use_div, d_xn.float().contiguous(),
                                        None if d_move is None else d_move.float().contiguous())
-        return None, d_mo, None, None, None
+        d_pos = None
+        if ctx.needs_input_grad[0]:
+            d_pos = ops.train_warp_backward_pos(pos, mo, aabb6, moving_step, use_div, d_xn.float().contiguous())
+        return d_pos, d_mo, None, None, None
 
 
 class _HeadInFn(torch.autograd.Function):
@@ -221,7 +261,10 @@ class _HeadInFn(torch.autograd.Function):
         b, sel = ctx.saved_tensors
         d_bout = ops.train_head_in_backward(b, sel, None if d_head_in is None else d_head_in.float().contiguous(),
                                             None if d_sigma is None else d_sigma.float().contiguous())
-        return d_bout, None, None
+        d_sh = None
+        if ctx.needs_input_grad[1] and d_head_in is not None:
+            d_sh = d_head_in[:, :4].float().contiguous()
+        return d_bout, d_sh, None
 
 
 class _LinearFn(torch.autograd.Function):
@@ -332,6 +375,9 @@ class TrainableField(torch.nn.Module):
         tt = t.reshape(-1).float()
         if tt.shape[0] == 1 and n != 1:
             tt = tt.expand(n)
+        if torch.is_grad_enabled() and (positions.requires_grad or directions.requires_grad or tt.requires_grad):
+            pos, enc, sh, tt = _InputsFn.apply(positions, directions, tt, None, None, None)
+            return self._forward_core(pos, enc, sh, tt, return_internal)
         pos, enc, sh, tt = ops.train_inputs(n, positions=positions.detach().float().contiguous(),
                                             directions=directions.detach().float().contiguous(), timestamps=tt.contiguous())
         return self._forward_core(pos, enc, sh, tt, return_internal)
@@ -343,6 +389,9 @@ class TrainableField(torch.nn.Module):
         if not self.fused_glue:
             pos = rays_o[ray_indices] + rays_d[ray_indices] * ((t_starts + t_ends)[:, None] / 2.0)
             return self._forward_torch(pos, ts_per_ray.reshape(-1, 1)[ray_indices], rays_d[ray_indices], return_internal)
+        if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad or ts_per_ray.requires_grad):
+            pos, enc, sh, tt = _InputsFn.apply(rays_o, rays_d, ts_per_ray.reshape(-1), ray_indices, t_starts, t_ends)
+            return self._forward_core(pos, enc, sh, tt, return_internal)
         pos, enc, sh, tt = ops.train_inputs(ray_indices.shape[0], rays_o.contiguous(), rays_d.contiguous(),
                                             ray_indices.contiguous(), t_starts.contiguous(), t_ends.contiguous(),
                                             ts_per_ray.reshape(-1).float().contiguous())
@@ -503,6 +552,54 @@ def refresh_occupancy(field: TrainableField, estimator, step: int, timestamps: t
     estimator.train(was_training)
 
 
+def rodrigues(rot: torch.Tensor) -> torch.Tensor:
+    """Axis-angle vectors [..., 3] -> rotation matrices [..., 3, 3]: R = I + a K + b K^2 with K = [rot]x,
+    a = sin(th) / th, b = (1 - cos(th)) / th^2 = (sin(th / 2) / (th / 2))^2 / 2, th = |rot|.  Below th = 1e-4 both come
+    from their Taylor series in th^2 (a = 1 - th^2 / 6 + th^4 / 120, b = 1 / 2 - th^2 / 24 + th^4 / 720), so the value and
+    the gradient at rot = 0 are finite and those of I + [rot]x."""
+    th2 = (rot * rot).sum(dim=-1)
+    small = th2 < 1e-8
+    th = torch.sqrt(torch.where(small, torch.ones_like(th2), th2))       # the branch not taken stays differentiable
+    half = 0.5 * th
+    a = torch.where(small, 1.0 - th2 / 6.0 + th2 * th2 / 120.0, torch.sin(th) / th)
+    b = torch.where(small, 0.5 - th2 / 24.0 + th2 * th2 / 720.0, 0.5 * (torch.sin(half) / half) ** 2)
+    x, y, z = rot.unbind(dim=-1)
+    o = torch.zeros_like(x)
+    K = torch.stack([torch.stack([o, -z, y], dim=-1), torch.stack([z, o, -x], dim=-1), torch.stack([-y, x, o], dim=-1)],
+                    dim=-2)
+    eye = torch.eye(3, dtype=rot.dtype, device=rot.device).expand(K.shape)
+    return eye + a[..., None, None] * K + b[..., None, None] * (K @ K)
+
+
+class CameraRefinement(torch.nn.Module):
+    """Per-view corrections of a capture's cameras, learnt with the field (or, with the field frozen, by `align_view`):
+    rot [V,3] an axis-angle rotation in the world frame about the camera centre, trans [V,3] a shift of the camera
+    centre, dt [V] a time offset; all zero at the start, where the module is the identity.  poses / times choose which
+    exist.  forward(rays_o, rays_d, timestamps, view_idx) -> (rays_o + trans[v], R(rot[v]) rays_d, timestamps + dt[v]);
+    times are not clamped.  Plain torch: three small per-ray operations; the per-sample work of their gradient is
+    ced_train_inputs_backward."""
+
+    def __init__(self, n_views: int, poses: bool = True, times: bool = True):
+        super().__init__()
+        self.n_views, self.poses, self.times = int(n_views), bool(poses), bool(times)
+        if self.poses:
+            self.rot = torch.nn.Parameter(torch.zeros(self.n_views, 3))
+            self.trans = torch.nn.Parameter(torch.zeros(self.n_views, 3))
+        if self.times:
+            self.dt = torch.nn.Parameter(torch.zeros(self.n_views))
+
+    def forward(self, rays_o, rays_d, timestamps, view_idx):
+        v = view_idx.reshape(-1).long()
+        if v.shape[0] == 1 and rays_o.shape[0] != 1:
+            v = v.expand(rays_o.shape[0])
+        if self.poses:
+            rays_o = rays_o + self.trans[v]
+            rays_d = (rodrigues(self.rot)[v] * rays_d[:, None, :]).sum(dim=-1)
+        if self.times:
+            timestamps = timestamps + self.dt[v].reshape(-1, *([1] * (timestamps.dim() - 1)))
+        return rays_o, rays_d, timestamps
+
+
 _COLOUR_LOSSES = {"smooth_l1": torch.nn.functional.smooth_l1_loss, "mse": torch.nn.functional.mse_loss}
 
 
@@ -519,7 +616,8 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
                render_bkgd: Optional[torch.Tensor] = None, grad_scaler=None, native_sampling: bool = True,
                overlap_table_grad: bool = True, rgb_loss: str = "smooth_l1", distortion_loss: bool = False,
                acc_entropy_loss: bool = False, opacity_loss: bool = False, weight_rgbper: bool = False,
-               loss_weights: Optional[Dict[str, float]] = None, skip_empty: bool = False) -> Dict:
+               loss_weights: Optional[Dict[str, float]] = None, skip_empty: bool = False,
+               refinement: Optional["CameraRefinement"] = None, view_indices: Optional[torch.Tensor] = None) -> Dict:
     """One optimisation step on a batch of rays (train_real.py:339-420): stratified occupancy-grid sampling with the
     current density (no gradient), differentiable field + compositing, colour loss, the enabled regularisers, optimiser
     step.
@@ -532,6 +630,9 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
       weight_rgbper    (-wr)  "weight_rgbper"  losses.weighted_rgb_loss with the (detached) rendering weights
     skip_empty: a batch whose rays keep no sample returns {"loss": nan, "n_samples": 0, "loss_terms": {}, "skipped": True}
     before any gradient, optimiser or scaler work (train_real.py:351-352); the default runs every step through.
+    refinement (a `CameraRefinement`, with view_indices [n_rays] the view of each ray): the rays and times are refined,
+    sampled as they then stand (no gradient), and rendered differentiably, so the module's parameters receive
+    gradients; the caller keeps them in a parameter group of `optimizer`.
     Returns {"loss", "n_samples", "loss_terms"}: loss_terms holds the unscaled value of every enabled term."""
     if rgb_loss not in _COLOUR_LOSSES:
         raise ValueError(f"rgb_loss={rgb_loss!r}: one of {sorted(_COLOUR_LOSSES)}")
@@ -544,6 +645,12 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
     ts = timestamps.reshape(-1, 1).float()
     if ts.shape[0] == 1:
         ts = ts.expand(n_rays, 1)
+    refined = None
+    if refinement is not None:
+        if view_indices is None:
+            raise ValueError("refinement needs view_indices: the view of each ray")
+        refined = refinement(rays_o, rays_d, ts, view_indices)
+        rays_o, rays_d, ts = (v.detach().contiguous() for v in refined)
 
     field.sync_half_table()                               # fp16-table fields: the evaluated copy follows the master
     fused = field.shared_inference()
@@ -565,7 +672,8 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
     with_heads = field.use_feat_predict or field.use_weight_predict
 
     def rgb_sigma_fn(t_starts, t_ends, ray_indices):
-        return field.forward_rays(rays_o, rays_d, ray_indices, t_starts, t_ends, ts, return_internal=with_heads)
+        o, d, t = (rays_o, rays_d, ts) if refined is None else refined
+        return field.forward_rays(o, d, ray_indices, t_starts, t_ends, t, return_internal=with_heads)
 
     packed = _packed_info_from(ray_indices, n_rays) if (distortion_loss or weight_rgbper) else None
     colors, opacities, depths, extras = rendering_train(t_starts, t_ends, ray_indices, n_rays, rgb_sigma_fn,
@@ -611,3 +719,69 @@ def train_step(field: TrainableField, estimator, optimizer, rays_o: torch.Tensor
         return {"loss": float(loss.detach()), "n_samples": int(t_starts.shape[0]), "loss_terms": {}}
     values = torch.stack([loss.detach()] + [v.detach().float() for v in terms.values()]).tolist()     # one read-back
     return {"loss": values[0], "n_samples": int(t_starts.shape[0]), "loss_terms": dict(zip(terms, values[1:]))}
+
+
+def align_view(field: TrainableField, estimator, pixels: torch.Tensor, rays_o: torch.Tensor, rays_d: torch.Tensor, t,
+               steps: int = 200, lr: float = 1e-2, num_rays: int = 1024, *, render_step_size: float,
+               near_plane: float = 0.0, far_plane: float = 1e10, cone_angle: float = 0.0, alpha_thre: float = 0.0,
+               render_bkgd: Optional[torch.Tensor] = None, poses: bool = True, times: bool = True,
+               rgb_loss: str = "mse", seed: int = 0, lr_time: Optional[float] = None,
+               stratified: bool = True) -> Dict:
+    """Pose and time of ONE image against a frozen field (iNeRF-style): a one-view `CameraRefinement` of the image's
+    nominal rays (rays_o, rays_d [P,3], pixels [P,3], one time t), Adam on it alone (learning rate lr for rot and trans,
+    lr_time -- default lr -- for dt: a radian and a unit of time rarely move the image alike) over random batches of
+    num_rays pixels, each sampled with the occupancy grid at the current estimate (stratified: jittered as in training;
+    False places every step's samples alike, which takes the sampling noise out of a loss between two renders of one
+    field) and rendered differentiably.  The field's parameters are frozen for the call (no weight gradient is computed)
+    and restored after it.
+    -> {"rot" [3], "trans" [3], "dt" (0-d), "history": the loss of every step}."""
+    dev = rays_o.device
+    pixels, rays_o, rays_d = (v.reshape(-1, 3).float().contiguous() for v in (pixels, rays_o, rays_d))
+    t0 = torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1)[:1]
+    ref = CameraRefinement(1, poses=poses, times=times).to(dev)
+    groups = [dict(params=[ref.rot, ref.trans], lr=lr)] if poses else []
+    if times:
+        groups.append(dict(params=[ref.dt], lr=lr if lr_time is None else lr_time))
+    opt = torch.optim.Adam(groups)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    view = torch.zeros(1, dtype=torch.int64, device=dev)
+    was = [p.requires_grad for p in field.parameters()]
+    history = []
+    field.sync_half_table()
+    fused = field.shared_inference()
+    try:
+        for p in field.parameters():
+            p.requires_grad_(False)
+        for _ in range(int(steps)):
+            idx = torch.randint(0, rays_o.shape[0], (int(num_rays),), device=dev, generator=gen)
+            refined = ref(rays_o[idx], rays_d[idx], t0.expand(idx.shape[0], 1), view)
+            o, d, ts = (v.detach().contiguous() for v in refined)
+            fused.train()
+
+            def sigma_fn(t_starts, t_ends, ray_indices):
+                return fused.query_rays(o, d, ray_indices, t_starts, t_ends, ts, want_rgb=False)[1]
+
+            ray_indices, t_starts, t_ends = estimator.sampling(o, d, sigma_fn=sigma_fn, near_plane=near_plane,
+                                                               far_plane=far_plane, render_step_size=render_step_size,
+                                                               stratified=stratified, cone_angle=cone_angle,
+                                                               alpha_thre=alpha_thre, sigma_field=(fused, ts, True))
+
+            def rgb_sigma_fn(t_starts, t_ends, ray_indices):
+                return field.forward_rays(refined[0], refined[1], ray_indices, t_starts, t_ends, refined[2])
+
+            colors, _, _, _ = rendering_train(t_starts, t_ends, ray_indices, idx.shape[0], rgb_sigma_fn,
+                                              render_bkgd=render_bkgd)
+            loss = colour_loss(colors, pixels[idx], rgb_loss)
+            history.append(loss.detach())
+            if not loss.requires_grad:                 # no ray of the batch kept a sample
+                continue
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+    finally:
+        for p, flag in zip(field.parameters(), was):
+            p.requires_grad_(flag)
+    zero3 = torch.zeros(3, device=dev)
+    return dict(rot=ref.rot.detach()[0].clone() if poses else zero3, trans=ref.trans.detach()[0].clone() if poses else zero3.clone(),
+                dt=ref.dt.detach()[0].clone() if times else torch.zeros((), device=dev),
+                history=torch.stack(history).tolist() if history else [])

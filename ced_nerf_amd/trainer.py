@@ -26,7 +26,7 @@ import torch
 from . import synthetic
 from .metrics import evaluate_views
 from .nerfacc_api import OccGridEstimator
-from .train import TrainableField, next_num_rays, refresh_occupancy, train_step
+from .train import CameraRefinement, TrainableField, next_num_rays, refresh_occupancy, train_step
 from .trainset import BKGD_MODES, CAMERA_PINHOLE, VIEW_MODES, TrainViews
 
 
@@ -100,7 +100,8 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
         acc_entropy_loss: bool = False, opacity_loss: bool = False, weight_rgbper: bool = False,
         eval_every: int = 0, log_every: int = 10000, save_path: Optional[str] = None, verbose: bool = True,
         sampling_weights: Optional[torch.Tensor] = None, weights_subsampled: int = 1,
-        ist_weights: Optional[torch.Tensor] = None, ist_from_step: Optional[int] = None, **overrides) -> Dict:
+        ist_weights: Optional[torch.Tensor] = None, ist_from_step: Optional[int] = None, refine_poses: bool = False,
+        refine_times: bool = False, refine_lr: float = 1e-3, **overrides) -> Dict:
     """Trains a field on `train_views` as train_real.py:185-520 does and evaluates it on `test_views`.
 
     Setup: OccGridEstimator(aabb, grid_resolution, grid_levels); a TrainableField with the reference's initialisation
@@ -118,8 +119,14 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
     switch_to_ist, which train_real.py:301-309 has commented out: by default ISG throughout).  The history records then
     carry "sampling": "isg" or "ist".  Without `sampling_weights` the batches are the uniform ones.
 
+    refine_poses / refine_times: a `train.CameraRefinement` over the training views (a rotation and a shift of the
+    camera, a time offset, per view; zero at the start) is trained with the field, in a parameter group of its own with
+    learning rate refine_lr under the same schedule; the batches then carry their view indices.  Evaluation uses the
+    test views' own poses.  The result's "refinement" is the module's state dict (None when off) and the saved file
+    gains a "camera_refinement" key.
+
     `overrides` replace preset constants (max_steps, target_sample_batch_size, lr, log2_hashmap_size, ...).
-    Returns {"field", "inference", "estimator", "train_seconds", "history", "eval", "evals", "config"}: history holds a
+    Returns {"field", "inference", "estimator", "train_seconds", "history", "eval", "evals", "config", "refinement"}: history holds a
     dict per step (step, lr, num_rays, n_samples, loss, scale, skipped, occ_refreshed, seconds: the loop's wall time
     when the step's loss had been read back, evaluations excluded); eval is evaluate_views' result
     on test_views after the last step (None without test views); evals the (step, result) pairs of every eval_every.
@@ -144,6 +151,10 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
     field = TrainableField(params, dev, use_feat_predict=use_feat_predict, use_weight_predict=use_weight_predict, seed=seed)
     inference = field.shared_inference()
     optimizer = torch.optim.Adam(field.parameters(), lr=cfg["lr"], eps=1e-15, weight_decay=cfg["weight_decay"], fused=True)
+    refinement = None
+    if refine_poses or refine_times:
+        refinement = CameraRefinement(len(train_views), poses=refine_poses, times=refine_times).to(dev)
+        optimizer.add_param_group(dict(params=list(refinement.parameters()), lr=float(refine_lr)))
     scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 10)
     scheduler = make_scheduler(optimizer, steps, cfg["milestones"])
     losses = dict(distortion_loss=distortion_loss, acc_entropy_loss=acc_entropy_loss, opacity_loss=opacity_loss,
@@ -156,6 +167,8 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
             return None
         return evaluate_views(inference, estimator, test_views.test_views(bkgd=cfg["test_bkgd"]), **render)
 
+    batch_extra = {} if refinement is None else dict(return_indices=True)
+    refine = lambda data: {} if refinement is None else dict(refinement=refinement, view_indices=data["indices"][:, 0])
     num_rays = int(cfg["init_batch_size"])
     target = int(cfg["target_sample_batch_size"])
     history, evals = [], []
@@ -166,11 +179,12 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
         field.train()
         estimator.train()
         if sampling_weights is None:
-            data = train_views.batch(num_rays, step, bkgd=cfg["train_bkgd"], view_mode=cfg["view_mode"], seed=seed)
+            data = train_views.batch(num_rays, step, bkgd=cfg["train_bkgd"], view_mode=cfg["view_mode"], seed=seed,
+                                     **batch_extra)
         else:
             use_ist = ist_from_step is not None and step >= ist_from_step
             data = train_views.batch_importance(num_rays, step, ist_weights if use_ist else sampling_weights,
-                                                weights_subsampled, bkgd=cfg["train_bkgd"], seed=seed)
+                                                weights_subsampled, bkgd=cfg["train_bkgd"], seed=seed, **batch_extra)
         rays, pixels, ts = data["rays"], data["pixels"], data["timestamps"]
         version = estimator.binaries._version
         refresh_occupancy(field, estimator, step, ts, cfg["render_step_size"])
@@ -179,7 +193,7 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
         out = train_step(field, estimator, optimizer, rays.origins, rays.viewdirs, ts, pixels, cfg["render_step_size"],
                          near_plane=cfg["near_plane"], far_plane=cfg["far_plane"], cone_angle=cfg["cone_angle"],
                          alpha_thre=cfg["alpha_thre"], render_bkgd=data["color_bkgd"], grad_scaler=scaler,
-                         rgb_loss="mse", skip_empty=True, **losses)
+                         rgb_loss="mse", skip_empty=True, **losses, **refine(data))
         skipped = bool(out.get("skipped", False))
         rec = dict(step=step, lr=lr, num_rays=num_rays, n_samples=out["n_samples"], loss=out["loss"],
                    scale=float(scaler.get_scale()), skipped=skipped, occ_refreshed=refreshed,
@@ -204,14 +218,18 @@ def fit(train_views: TrainViews, test_views: Optional[TrainViews] = None, preset
     train_seconds = time.time() - tic - eval_seconds
     field.sync_half_table()
     if save_path:
-        torch.save({"radiance_field": inference.state_dict(), "occupancy_grid": estimator.state_dict()}, save_path)
+        ckpt = {"radiance_field": inference.state_dict(), "occupancy_grid": estimator.state_dict()}
+        if refinement is not None:
+            ckpt["camera_refinement"] = refinement.state_dict()
+        torch.save(ckpt, save_path)
     result = evaluate()
     if result is not None:
         evals.append((steps, result))
         if verbose:
             print(f"evaluation: psnr_avg={result['psnr_avg']}, ssim_avg={result['ssim_avg']}", flush=True)
     return dict(field=field, inference=inference, estimator=estimator, train_seconds=train_seconds, history=history,
-                eval=result, evals=evals, config=cfg)
+                eval=result, evals=evals, config=cfg,
+                refinement=None if refinement is None else refinement.state_dict())
 
 
 def build_modules(cfg: Dict, device, *, use_div_offsets: bool = False, use_time_embedding: bool = False,
@@ -351,6 +369,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --render_video: render through B time slices of the occupancy grid (TimeSlicedOccGrid.from_field)")
     p.add_argument("--time_bin_samples", type=int, default=5, metavar="S", help="probe times per bin of --time_bins")
     p.add_argument("--ist_from_step", type=int, default=None, help="DyNeRF: sample by the IST map from this step on")
+    p.add_argument("--refine_poses", action="store_true", help="learn a rotation and a shift per training view")
+    p.add_argument("--refine_times", action="store_true", help="learn a time offset per training view")
+    p.add_argument("--refine_lr", type=float, default=1e-3, help="learning rate of --refine_poses / --refine_times")
     p.add_argument("-df", "--use_div_offsets", action="store_true")
     p.add_argument("-f", "--use_feat_predict", action="store_true")
     p.add_argument("-w", "--use_weight_predict", action="store_true")
@@ -413,7 +434,8 @@ def main(argv=None) -> int:
         log_every = 10000 if a.max_steps is None else max(1, min(10000, a.max_steps))
         res = fit(train, test, preset=kind, max_steps=a.max_steps, seed=a.seed, distortion_loss=a.distortion_loss,
                   acc_entropy_loss=a.acc_entorpy_loss, opacity_loss=a.use_opacity_loss, weight_rgbper=a.weight_rgbper,
-                  log_every=log_every, save_path=a.save_path, **flags, **sampling, **extra)
+                  log_every=log_every, save_path=a.save_path, refine_poses=a.refine_poses, refine_times=a.refine_times,
+                  refine_lr=a.refine_lr, **flags, **sampling, **extra)
         inference, estimator, cfg = res["inference"], res["estimator"], res["config"]
     if a.render_video:
         grid = estimator.eval()

@@ -1093,20 +1093,46 @@ int ced_mlp_backward_dw(int64_t n, int32_t n_layers, const float *dy, const int3
  * ced_train_inputs: per sample the position (rays mode, ray_indices != NULL: rays_o[r] + rays_d[r] * ((t_start + t_end) / 2),
  *   time timestamps[r]; explicit mode: positions / directions / timestamps per sample), enc_out [n, 32] = tcnn
  *   Frequency(4) of (x, y, z, t) ([dim][freq][sin, cos] of pi 2^k v), sh_out [n, 4] = SH degree 2 of the normalised
- *   direction, t_out [n].  No backward: nothing upstream has parameters. */
+ *   direction, t_out [n].  Its backward is ced_train_inputs_backward. */
 int ced_train_inputs(int64_t n, const float *rays_o, const float *rays_d, const int64_t *ray_indices,
                      const float *t_starts, const float *t_ends, const float *timestamps, const float *positions,
                      const float *directions, float *pos_out, float *enc_out, float *sh_out, float *t_out, void *stream);
+/* ced_train_inputs_backward: the gradient of ced_train_inputs at its inputs (a camera pose, a time offset), from the
+ *   gradients d_pos [n, 3], d_enc [n, 32], d_sh [n, 4], d_t [n] at its four outputs; each may be NULL (= zero).  The
+ *   forward's own inputs are passed again: sin / cos are recomputed as the forward computes them.  Per sample i, with
+ *   v_q the q-th of (x, y, z, t), s_k / c_k = sin / cos(pi 2^k v_q):
+ *     g_v[q] = ((a_0 + a_1) + a_2) + a_3,  a_k = fl(pi 2^k) * (d_enc[i, 8q + 2k] * c_k - d_enc[i, 8q + 2k + 1] * s_k)
+ *     g_pos  = d_pos[i] + g_v[0..2],   g_t = d_t[i] + g_v[3]
+ *     g_dir  = (g_w - w * ((w_x g_wx + w_y g_wy) + w_z g_wz)) / |d|,  w = ((d / |d| + 1) / 2) * 2 - 1 as in the forward,
+ *              g_w = (-K d_sh[i, 3], -K d_sh[i, 1], K d_sh[i, 2]),  K = 0.48860251190291987
+ *   Explicit mode (ray_indices == NULL; n_rays ignored): d_origins [n, 3] = g_pos, d_directions [n, 3] = g_dir,
+ *   d_times [n] = g_t.
+ *   Rays mode: per ray r the sums over its samples, t_mid = (t_start + t_end) / 2 as the forward rounds it and
+ *   t_starts / t_ends constants:  d_origins [n_rays, 3] = sum g_pos,  d_directions [n_rays, 3] = sum (g_pos * t_mid + g_dir),
+ *   d_times [n_rays] = sum g_t.  PRECONDITION: ray_indices is non-decreasing (what sampling produces) and packed_info
+ *   [n_rays, 2] int64 holds each ray's (first sample, count) -- nerfacc's packed_info of the same ray_indices.  Every
+ *   one of the n_rays rows is written (exact zeros for a ray without samples): the caller does not clear the outputs.
+ *   A segmented sum in a fixed order, no float atomics: the same bits on every launch.  n_rays < 2^31; d_enc and d_sh
+ *   16-byte aligned.  Explicit mode with n == 0 and rays mode with n_rays == 0 return CED_OK without a launch. */
+int ced_train_inputs_backward(int64_t n, int64_t n_rays, const float *rays_o, const float *rays_d,
+                              const int64_t *ray_indices, const float *t_starts, const float *t_ends,
+                              const float *timestamps, const float *positions, const float *directions,
+                              const int64_t *packed_info, const float *d_pos, const float *d_enc, const float *d_sh,
+                              const float *d_t, float *d_origins, float *d_directions, float *d_times, void *stream);
 /* ced_train_warp: move = mo[:, :3] * moving_step (+ tanh(mo[:, 3:6]) * moving_step with use_div_offsets),
  *   xn = clamp((pos + move - aabb_lo) / (aabb_hi - aabb_lo), 0, 1), selector = 1 where the unclamped xn lies strictly
  *   inside (0, 1) on all axes, else 0.  aabb_host: six floats on the HOST.
  * ced_train_warp_backward: d_mo [n, mo_width] from d_xn (passes where 0 <= unclamped xn <= 1, torch.clamp's rule) and
- *   d_move (may be NULL). */
+ *   d_move (may be NULL).
+ * ced_train_warp_backward_pos: d_pos [n, 3] = d_xn / (aabb_hi - aabb_lo) where 0 <= unclamped xn <= 1 (the same rule),
+ *   else 0; `move` does not depend on pos. */
 int ced_train_warp(int64_t n, const float *pos, const float *mo, int32_t mo_width, int32_t use_div_offsets,
                    float moving_step, const float *aabb_host, float *xn, float *move, float *selector, void *stream);
 int ced_train_warp_backward(int64_t n, const float *pos, const float *mo, int32_t mo_width, int32_t use_div_offsets,
                             float moving_step, const float *aabb_host, const float *d_xn, const float *d_move,
                             float *d_mo, void *stream);
+int ced_train_warp_backward_pos(int64_t n, const float *pos, const float *mo, int32_t mo_width, int32_t use_div_offsets,
+                                float moving_step, const float *aabb_host, const float *d_xn, float *d_pos, void *stream);
 /* ced_train_head_in: sigma = exp(bout[:, 0] - 1) * selector (trunc_exp, cednerf/utils.py:27-43), head_in [n, 19] =
  *   [sh (4), bout[:, 1:16]].  ced_train_head_in_backward: d_bout [n, 16] from d_head_in [n, 19] and d_sigma [n] (either may
  *   be NULL = zero); the density's derivative is exp(min(raw - 1, 15)) as in the reference's _TruncExp.backward. */
